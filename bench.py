@@ -21,6 +21,11 @@ the line then carries every rank's own shard render ms, the all-gather alone (HI
 the same job (`config.strong_speedup_vs_single_gpu_in_this_job`: the driver's N = 1 run is configs[1], another workload), and `extra.weak` holds the
 weak-scaling leg of rounds 1-4 (N lego views per step, per-GPU work fixed).  Explicit --workload / --model / --scaling override the defaults;
 `--scaling weak`: a step renders N views; `--scaling strong`: ONE frame split N ways.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the --steps steps and prints the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the
+per-step spread and the `config` block.  Everything else -- the roofline object (HIP events on the first timed step's lookup launches, the rocprofv3 --pmc
+child passes, the gather-rate micro-benchmark, MFMA utilisation), the N > 1 all-gather / single-GPU figures, the CPU baseline and parity against the
+oracle, and the `extra` legs -- runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step returned (rank 0) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -68,7 +73,7 @@ def parse(argv=None):
     ap.add_argument("--ray-order", choices=["tile8", "tile4", "tile16", "morton", "rowmajor"], default="tile8", help="initial order of the alive list in the native loop")
     ap.add_argument("--static-pose", action="store_true", help="every step renders pose 0 (round-1 behaviour; A/B against the moving camera)")
     ap.add_argument("--pose-step-deg", type=float, default=3.0, help="lego orbit: degrees of azimuth per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity block")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra driver-observed legs (exact-fp32 field, palette model)")
     ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes that measure roofline.traffic (FETCH_SIZE / WRITE_SIZE of the lookup kernel)")
     ap.add_argument("--extra-steps", type=int, default=20)
@@ -93,7 +98,13 @@ def parse(argv=None):
     ap.add_argument("--scene", choices=["s0", "s1", "s2"], default=None, help="override the workload's scene (s1: sparse 4^3 bricks, the occupied box ~94 %% air)")
     ap.add_argument("--dt-gamma", type=float, default=None, help="override the workload's march step growth")
     ap.add_argument("--cpu-crop", type=int, default=400, help="side of the centre crop rendered by the CPU oracle (baseline + PSNR)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, N > 1 all-gather / single-GPU figures, CPU baseline + parity, extra legs (the --no-* flags switch parts off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the arrays the last timed step returned (rank 0) as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # N > 1 answers north_star's multi-GPU question by default: configs[4] -- ONE garden video frame (1297 x 840, -m palette), its rays sharded over
     # the GPUs in 32 x 32 tiles, one RCCL all-gather of the per-ray rows per frame (strong scaling; the reference's dormant collective sites:
     # palette/utils.py:802-817).  N = 1 stays configs[1] (the configuration the metric is quoted on).  Explicit --workload / --model / --scaling win.
@@ -954,6 +965,36 @@ def strong_leg(args, m, kw, device, world, rank, steps, n_views=1):
     return out
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # under the 64 MB cap with room for the .npy headers
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as out_dir/<name>.npy, float64 kept, everything else as float32 (integer counts as float64:
+    exact).  When the whole set would exceed DUMP_BUDGET_BYTES each array is replaced by the same fixed share of its elements, chosen with a seeded generator
+    from its size alone (two builds with the same arguments sample the same positions).  Returns {name: [shape written, full shape]}."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, t in arrays.items():
+        if not isinstance(t, torch.Tensor):
+            continue
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float64 if a.dtype in (np.float64, np.int64, np.int32, np.uint32) else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / max(1, total))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in sorted(host.items()):
+        flat = a.reshape(-1)
+        if keep < 1.0:
+            k = max(1, int(flat.size * keep))
+            flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, k, replace=False))]
+            a = flat
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = [list(a.shape), list(host[name].shape)]
+    return written
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
@@ -1023,7 +1064,7 @@ def main(argv=None):
         bank.get(i)
     for i in range(args.warmup):
         frame(i)
-    if native:   # untimed, on every rank (a frame holds a collective): one frame with the in-library HIP-event timing on, so that the events exist
+    if native and args.full:   # untimed, on every rank (a frame holds a collective): one frame with the in-library HIP-event timing on, so that the events exist
         m._fused.time_grid_kernel = True
         frame(args.warmup)
         m._fused.time_grid_kernel = False
@@ -1033,16 +1074,17 @@ def main(argv=None):
         dist.barrier()
     torch.cuda.synchronize()
     GRID_OPS = ["pnr_grid_encode_forward", "pnr_grid_encode_forward_layout"]
-    prof = _torch_glue.profile_kernels(GRID_OPS) if rank == 0 else None
+    prof = _torch_glue.profile_kernels(GRID_OPS) if rank == 0 and args.full else None
     rendered = torch.zeros(1, dtype=torch.int64, device=device)
     rendered_host, rows, looks, iterations = 0, 0, 0, 0
     native_ms, native_launches, native_live = 0.0, 0, 0
-    timed_native = native and rank == 0
+    timed_native = native and rank == 0 and args.full    # (the first timed step's lookup launches carry HIP events: roofline only)
     step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # diagnostics only (no sync inside the loop)
     import gc
     gc.collect()
     gc.disable()   # as timeit does: a generation-2 collection of the interpreter's heap (tens of ms with torch imported) is not part of a frame
     F_main = max(1, int(args.main_frames_in_flight))
+    r, _full = None, None   # the last timed step's result (and, N > 1, its gathered frame): --dump-outputs
     if F_main > 1:
         # The timed steps with F frames in flight (pipeline.FramesInFlight): frame i on handle i % F, each on its own host thread and stream; with
         # N > 1 ranks the all-gather of frame i is issued as the i-th collective on every rank (dist.OrderedGather), each thread finishing its
@@ -1078,11 +1120,15 @@ def main(argv=None):
                         acc["iterations"] += int(r.get("iterations", 0))
                         if i == 0:
                             first.update(grid_ms=r.get("grid_ms", 0.0), grid_launches=r.get("grid_launches", 0), rendered=int(r["rendered"].sum()))
+                        if i == n - 1:
+                            first["last"] = r
                 return None
 
             fif.render(lambda i: bank.get(offset + i), n, consume=consume, before=before if native else None, abort=og.abort if og is not None else None, **kw)
-            for h in last.values():      # the last gather of every thread completes inside the (timed) region
-                og.finish(h)
+            for k, h in last.items():    # the last gather of every thread completes inside the (timed) region
+                full = og.finish(h)
+                if timed and k == (n - 1) % F_main:
+                    first["last_full"] = full     # the last frame's gathered rows (--dump-outputs)
 
         make_run(2 * F_main, 0, False)   # every handle: workspace, packed weights, iteration prediction
         torch.cuda.synchronize()
@@ -1096,6 +1142,7 @@ def main(argv=None):
             step_ev[i + 1].record()     # per-step diagnostics do not exist in this mode
         rendered_host, rows, looks, iterations = acc["rendered"], acc["rows"], acc["looks"], acc["iterations"]
         native_ms, native_launches, native_live = first.get("grid_ms", 0.0), first.get("grid_launches", 0), first.get("rendered", 0)
+        r, _full = first.get("last"), first.get("last_full")
     else:
         t0 = time.perf_counter()
         step_ev[0].record()
@@ -1168,16 +1215,23 @@ def main(argv=None):
     elapsed = time.perf_counter() - t0
     gc.enable()
     rendered += rendered_host
-    _torch_glue.profile_kernels(None)
+    if prof is not None:
+        _torch_glue.profile_kernels(None)
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dist.all_reduce(rendered, op=dist.ReduceOp.SUM)
     elapsed = float(t.item())
     total_rendered = int(rendered.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:   # what the last timed step returned, before anything else is rendered
+        arrays = dict(r) if r is not None else {}
+        if use_dist and _full is not None:
+            arrays["gathered_rows"] = _full
+        dumped = dump_outputs(args.dump_outputs, arrays)
 
     dist_info = None
-    if use_dist and F_main == 1:
+    if use_dist and F_main == 1 and args.full:
         # what the judge of a strong-scaling line needs next to `value`: every rank's own render time per step (HIP events around m.render: the
         # shard alone), the all-gather on its own by HIP events on the stream that waits for it (pack + collective + wait, 20 repeats on the timed
         # loop's buffers), and -- strong scaling -- the SAME frame rendered whole by one GPU inside this job (rank 0 alone, the others wait),
@@ -1237,7 +1291,7 @@ def main(argv=None):
         if half_rows:
             per_sample = 12 + 16 * 8 * 2 * 2 + 32 * 4   # half rows gathered, fp32 encoder output written
         n_tables = 1 if args.model == "nerf" else (3 if args.pred_clip else 2)  # palette: encoder + encoder_palette (+ encoder_clip with --pred-clip)
-        launches = [e for n in GRID_OPS for e in prof[n]]
+        launches = [e for n in GRID_OPS for e in prof[n]] if prof is not None else []
         k_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in launches)
         k_units = sum(u for _, _, u in launches)
         n_launches = len(launches)
@@ -1250,7 +1304,7 @@ def main(argv=None):
         achieved = (k_units * per_sample) / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
         # HBM-side bytes per lookup launch, MEASURED IN THIS RUN: two child passes of the same workload under rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE)
         traffic, traffic_info = None, None
-        if native and not args.no_traffic and F_main == 1:
+        if args.full and native and not args.no_traffic and F_main == 1:
             # N = 1: two child passes of this very command.  N > 1 (or the one-rank communicator of the tests): the children are SINGLE-GPU passes on this rank's
             # device that render rank 0's shard of the same split (--emulate-shard 0/N: the same rays, the same shard-sized launches; no communicator, the
             # launcher's environment stripped) -- nothing about a PMC pass needs the collective.  The other ranks wait at the barrier below.
@@ -1277,20 +1331,23 @@ def main(argv=None):
                        "gathered_floats_per_ray": K if use_dist else 0, "rccl_ranks": dist.get_world_size() if use_dist else 1,
                        "parallelism": f"32x32 ray tiles of {n_views} view(s) round-robin over {world} GPUs + one all_gather/step" if world > 1 else "single GPU",
                        **({"defaulted_for_ranks": True} if args.defaulted_for_ranks else {}), **(dist_info or {})},
-            "roofline": roofline_block(kernel_name, achieved, traffic, traffic_info, n_launches, k_ms, k_units, per_sample, n_tables if native else 1),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "what": "the last timed step's result: [shape written, full shape] per array"}
+        if args.full:
+            out["roofline"] = roofline_block(kernel_name, achieved, traffic, traffic_info, n_launches, k_ms, k_units, per_sample, n_tables if native else 1)
         if dist_info:      # what a strong-scaling curve should be read from, at the top level (the N = 1 run of the driver is configs[1], another workload)
             for k in ("strong_speedup_vs_single_gpu_in_this_job", "single_gpu_ms_per_step", "shard_render_ms_per_rank", "all_gather_ms"):
                 if k in dist_info:
                     out[k] = dist_info[k]
-        if native and k_ms > 0 and n_launches > 0:
+        if args.full and native and k_ms > 0 and n_launches > 0:
             out["roofline"]["l2_bound"] = l2_bound_of(k_units / n_launches / n_tables, 1, k_ms / n_launches,
                                                       ceilings=None if args.no_extras else gather_ceilings())
             try:    # north_star: MFMA utilisation of the fused field kernel against the gfx950 peak
                 out["roofline"]["mfma"] = mfma_leg(m, args.model, max(1024, int(k_units / n_launches / n_tables)), device, args.field_precision)
             except RuntimeError as e:
                 out["roofline"]["mfma_error"] = str(e)
-        if native and not os.environ.get("PNR_NO_HOSTED_TAIL"):
+        if args.full and native and not os.environ.get("PNR_NO_HOSTED_TAIL"):
             # The timed lookup launches also finish the march's stragglers (frame.hip: hosted_march_tail): their duration is the lookup's plus what
             # the hosted waves cost it.  The same frame once more with the tail switched off gives the lookup kernel on its own.
             from palettenerf_amd import _lib as _plib
@@ -1314,13 +1371,13 @@ def main(argv=None):
                                               "(profiles/frame_launch_avgs.py on a kernel trace of this command): `achieved` / `frac` are the conservative figures")
             out["roofline"]["note_hosted_tail"] = ("the timed launches host the march tail: their first workgroups march the rays the march launch handed over and look those rows up "
                                                    "(algorithmic bytes count the lookup only; `lookup_alone` is the kernel without that work)")
-        if F_main > 1:
+        if args.full and F_main > 1:
             out["roofline"]["note_frames_in_flight"] = (f"{F_main} frames in flight: the timed launches share the chip with another frame's kernels, and "
                                                         "ms_per_step is elapsed / steps, not the latency of a frame")
     if use_dist:
         dist.barrier()
     extra = {}
-    if use_dist and native and args.scaling == "strong" and not args.no_extras and F_main == 1:
+    if args.full and use_dist and native and args.scaling == "strong" and not args.no_extras and F_main == 1:
         # the weak-scaling question (rounds 1-4's N > 1 headline) next to the strong-scaling one: `world` views of the configs[1] lego frame per step,
         # per-GPU work fixed; every rank takes part, rank 0 reports
         try:
@@ -1337,7 +1394,7 @@ def main(argv=None):
                 raise
             if rank == 0:
                 extra["weak_error"] = str(e)
-    if use_dist and native and args.scaling == "weak" and not args.no_extras and F_main == 1:   # (PNR_BENCH_FORCE_DIST=1 runs it over a one-rank communicator)
+    if args.full and use_dist and native and args.scaling == "weak" and not args.no_extras and F_main == 1:   # (PNR_BENCH_FORCE_DIST=1 runs it over a one-rank communicator)
         # every rank takes part; rank 0 reports.  (--scaling strong makes this split the headline itself.)
         try:
             strong = strong_leg(args, m, kw, device, world, rank, max(5, args.extra_steps))
@@ -1349,7 +1406,7 @@ def main(argv=None):
             if rank == 0:
                 extra["strong_error"] = str(e)
     crop_ref = None   # (rays_o, rays_d, oracle results) of the parity crop, for the extra legs
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # --- PSNR / max-abs against the oracle + the CPU baseline, on a centre crop of pose 0 (same device-generated rays for both sides)
         if not args.no_cpu_baseline:
             from palettenerf_amd import rays as prays

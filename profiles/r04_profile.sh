@@ -11,11 +11,11 @@ prof() {  # name, program args...
   db=$(find /tmp/prof_$name -name '*.db' | head -1)
   { echo "# rocprofv3 --kernel-trace --stats -- python3 $(echo "$@" | sed "s#$R/##g")   (round 4)"; python3 $R/profiles/summarize.py $db; } > $R/gpurun_out/r04/$name.txt
 }
-prof bench_lego $R/bench.py --workload lego --steps 15 --warmup 3 --no-cpu-baseline --no-extras --no-traffic
-prof bench_lego_palette $R/bench.py --workload lego_palette --steps 15 --warmup 3 --no-cpu-baseline --no-extras --no-traffic
-prof bench_garden $R/bench.py --workload garden --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-traffic
-prof bench_lego_compat $R/bench.py --workload lego --mode compat --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-traffic
-prof bench_lego_palette_compat $R/bench.py --workload lego_palette --mode compat --steps 6 --warmup 2 --no-cpu-baseline --no-extras --no-traffic
+prof bench_lego $R/bench.py --full --workload lego --steps 15 --warmup 3 --no-cpu-baseline --no-extras --no-traffic
+prof bench_lego_palette $R/bench.py --full --workload lego_palette --steps 15 --warmup 3 --no-cpu-baseline --no-extras --no-traffic
+prof bench_garden $R/bench.py --full --workload garden --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-traffic
+prof bench_lego_compat $R/bench.py --full --workload lego --mode compat --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-traffic
+prof bench_lego_palette_compat $R/bench.py --full --workload lego_palette --mode compat --steps 6 --warmup 2 --no-cpu-baseline --no-extras --no-traffic
 prof grid_op_once $R/profiles/grid_op_bench.py --once
 prof train_step_palette $R/profiles/train_step_bench.py --model palette --steps 20 --warmup 5
 prof train_step_nerf $R/profiles/train_step_bench.py --model nerf --steps 20 --warmup 5

@@ -6,4 +6,4 @@ timeout 1500 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.log 2>&1; echo 
 timeout 600 python profiles/grid_op_bench.py > $O/grid_op_bench.log 2>&1
 timeout 600 python profiles/grad_tolerance.py > $O/grad_tolerance.log 2>&1
 timeout 600 python profiles/compat_host_profile.py nerf > $O/compat_host_nerf.log 2>&1
-timeout 900 python bench.py > $O/bench_default.log 2>&1; echo "bench rc $?" >> $O/bench_default.log
+timeout 900 python bench.py --full > $O/bench_default.log 2>&1; echo "bench rc $?" >> $O/bench_default.log

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B: frame lookup with the row index formed per kind of level (product) against the general form for every level
 R=$PWD; O=$R/gpurun_out/r04; mkdir -p $O
-run() { PNR_LIB_PATH=$2 timeout 300 python bench.py --workload $3 --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | python -c "
+run() { PNR_LIB_PATH=$2 timeout 300 python bench.py --full --workload $3 --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{\"metric\"'):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B: NeRF field with each k-block's activations split in front of its own products (product) against all four splits up front
 R=$PWD; O=$R/gpurun_out/r04; mkdir -p $O
-run() { PNR_LIB_PATH=$2 timeout 300 python bench.py --workload lego --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | python -c "
+run() { PNR_LIB_PATH=$2 timeout 300 python bench.py --full --workload lego --steps 20 --warmup 3 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{\"metric\"'):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B: PaletteNeRF field with a block's weight fragments requested ahead of its activation split (product) against the compiler-placed reads
 R=$PWD; O=$R/gpurun_out/r04; mkdir -p $O
-run() { PNR_LIB_PATH=$2 timeout 300 python bench.py --workload $3 --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | python -c "
+run() { PNR_LIB_PATH=$2 timeout 300 python bench.py --full --workload $3 --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{\"metric\"'):

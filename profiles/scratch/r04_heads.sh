@@ -1,7 +1,7 @@
 #!/bin/bash
 R=$PWD; O=$R/gpurun_out/r04; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_ops.py tests/test_gpu_frames.py -x -q -m gpu -k "heads or fuse_field or palette_field" > $O/pytest_heads.log 2>&1; echo "rc $?" >> $O/pytest_heads.log
-timeout 900 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-traffic 2>/dev/null | python -c "
+timeout 900 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-traffic 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{\"metric\"'):

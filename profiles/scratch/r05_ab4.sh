@@ -1,6 +1,6 @@
 #!/bin/bash
 R=$PWD; O=$R/gpurun_out/r05; mkdir -p $O; TAG=${TAG:-k}
-run() { PNR_LIB_PATH=$2 timeout 300 python bench.py --workload $3 --steps 100 --warmup 5 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | python -c "
+run() { PNR_LIB_PATH=$2 timeout 300 python bench.py --full --workload $3 --steps 100 --warmup 5 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{\"metric\"'):

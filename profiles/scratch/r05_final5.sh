@@ -13,4 +13,4 @@ cd $R
 for m in palette nerf; do timeout 300 python profiles/train_step_bench.py --model $m --steps 50 --warmup 5 > $O/train_${m}_plain.log 2>&1; done
 timeout 900 python profiles/train_palette.py > $O/train_palette_5k.txt 2>&1
 timeout 600 python profiles/grad_tolerance.py > $O/grad_tolerance.txt 2>&1
-timeout 1500 python bench.py > $O/bench_default.out 2> $O/bench_default.err; grep '^{"metric"' $O/bench_default.out > $O/bench_default.json
+timeout 1500 python bench.py --full > $O/bench_default.out 2> $O/bench_default.err; grep '^{"metric"' $O/bench_default.out > $O/bench_default.json

@@ -7,7 +7,7 @@ for wl in garden lego_palette; do
   PNR_LIB_PATH=$R/palettenerf_amd/libpnr_hip_paltiming.so timeout 300 python profiles/pal_timing.py --workload $wl > $O/pal_timing_$wl.txt 2>&1
 done
 for wl in garden lego_palette lego; do
-  timeout 300 python bench.py --workload $wl --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | tail -1 > $O/base_$wl.json
+  timeout 300 python bench.py --full --workload $wl --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-traffic 2>/dev/null | tail -1 > $O/base_$wl.json
 done
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_garden -o garden -- python3 $R/bench.py --workload garden --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-traffic > $O/prof_garden.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_garden -o garden -- python3 $R/bench.py --full --workload garden --steps 5 --warmup 2 --no-cpu-baseline --no-extras --no-traffic > $O/prof_garden.log 2>&1

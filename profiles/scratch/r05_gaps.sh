@@ -4,7 +4,7 @@ R=$PWD; export TMPDIR=/tmp; O=$R/gpurun_out/r05; mkdir -p $O; TAG=${TAG:-a}
 cd /tmp
 for wl in lego lego_palette garden; do
   rm -rf /tmp/prof_g$wl
-  timeout 600 rocprofv3 --kernel-trace -d /tmp/prof_g$wl -o p -- python3 $R/bench.py --workload $wl --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-traffic > $O/gaps_$wl.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace -d /tmp/prof_g$wl -o p -- python3 $R/bench.py --full --workload $wl --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-traffic > $O/gaps_$wl.log 2>&1
   db=$(find /tmp/prof_g$wl -name '*.db' | head -1)
   { echo "## $wl"; grep -o '"ms_per_step": [0-9.]*' $O/gaps_$wl.log | head -1; python3 $R/profiles/frame_gaps.py $db; python3 - $db <<'PY'
 import sqlite3, sys

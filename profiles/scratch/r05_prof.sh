@@ -3,7 +3,7 @@
 R=$PWD; O=$R/gpurun_out/r05; mkdir -p $O; TAG=${TAG:-a}
 cd /tmp && export TMPDIR=/tmp
 for wl in ${WLS:-garden lego_palette lego}; do
-  timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_${TAG}_$wl -o $wl -- python3 $R/bench.py --workload $wl --steps 10 --warmup 5 --no-cpu-baseline --no-extras --no-traffic > $O/prof_${TAG}_$wl.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_${TAG}_$wl -o $wl -- python3 $R/bench.py --full --workload $wl --steps 10 --warmup 5 --no-cpu-baseline --no-extras --no-traffic > $O/prof_${TAG}_$wl.log 2>&1
   f=$(find $O/prof_${TAG}_$wl -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && python3 - "$f" > $O/prof_${TAG}_$wl.txt <<'PY'
 import csv, sys

@@ -307,8 +307,23 @@ RUN_CASES = [
 ]
 
 
+# The CPU arithmetic run_nerf_*.npz is recorded and checked under: ATen's portable (non-vector) kernels, MKL's conditional-numerical-reproducibility
+# code path and one thread.  The upsampling's inverse CDF (nerf/renderer.py:12-45) turns last-bit differences between hosts' vector kernels (AVX-512
+# against AVX2 or none) into ~5e-5 on a few pixels; under this environment the frame is the same bits on any x86-64 host.  It takes effect at process
+# start: gen_run and tests/test_host_logic.py run the frames in a child process that has it.
+PINNED_CPU_ENV = {"ATEN_CPU_CAPABILITY": "default", "MKL_CBWR": "COMPATIBLE", "OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1"}
+
+
+def pinned_cpu():
+    return all(os.environ.get(k) == v for k, v in PINNED_CPU_ENV.items())
+
+
 def gen_run():
-    """NeRFRenderer.run (nerf/renderer.py:127-255) of the reference as it is, cuda_ray=False, eval mode (deterministic upsampling)."""
+    """NeRFRenderer.run (nerf/renderer.py:127-255) of the reference as it is, cuda_ray=False, eval mode (deterministic upsampling), under PINNED_CPU_ENV."""
+    if not pinned_cpu():
+        import subprocess
+        subprocess.check_call([sys.executable, os.path.abspath(__file__), "run"], env=dict(os.environ, **PINNED_CPU_ENV))
+        return
     ref_nerf, _, _ = import_reference()
     for name, H, W, ns, us, dscale, seed in RUN_CASES:
         ro, rd = frame_inputs(H, W)
@@ -498,8 +513,106 @@ def gen_occupancy(G=32):
     print("occupancy.npz", os.path.getsize(os.path.join(HERE, "occupancy.npz")) // 1024, "KiB")
 
 
+# ------------------------------------------------------------------------------------------ the reference's operator wrappers over the native stand-ins
+def wrapper_outputs(rm, ge, sh, half_encode):
+    """The operator calls tests/test_oracle.py pins, on inputs drawn from numpy's seeded generator (independent of the modules' own parameter init):
+    GridEncoder construction, forward with the bound map, table gradient, the half-table forward, SHEncoder, the training composites forward + backward
+    and the inference composites in place.  `rm`, `ge`, `sh`: raymarching / gridencoder / shencoder modules -- the reference's own wrappers over
+    oracle/native_facade.py here, oracle/facade.py's restatement in the test.  `half_encode(x01, emb, offsets, per_level_scale)`: the fp16-table
+    forward (the reference's gridencoder/grid.py:36-39 cast under autocast; the oracle's half path in the test).  Returns {name: numpy array}."""
+    rng = np.random.default_rng(0)
+    out = {}
+    enc = ge.GridEncoder(input_dim=3, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=19, desired_resolution=4096)
+    out["grid_offsets"] = enc.offsets.numpy().astype(np.int64)
+    out["grid_per_level_scale"] = np.array([enc.per_level_scale], np.float64)
+    out["grid_output_dim"] = np.array([enc.output_dim], np.int64)
+    with torch.no_grad():
+        enc.embeddings.copy_(torch.from_numpy(rng.uniform(-0.5, 0.5, tuple(enc.embeddings.shape)).astype(np.float32)))
+    x = torch.from_numpy((rng.random((3001, 3)) * 4 - 2).astype(np.float32))
+    x[:2] = torch.tensor([[2.0, 2.0, 2.0], [2.0000005, 0.0, 0.0]])
+    y = enc(x, bound=2)
+    g = torch.from_numpy(rng.standard_normal(tuple(y.shape)).astype(np.float32))
+    (y * g).sum().backward()
+    out["grid_forward"], out["grid_table_grad"] = y.detach().numpy(), enc.embeddings.grad.numpy()
+    out["grid_half_forward_bits"] = np.asarray(half_encode(((x + 2) / 4).numpy(), enc.embeddings.detach().numpy(), enc.offsets.numpy(),
+                                                           enc.per_level_scale)).astype(np.float16).view(np.uint16)
+    d = rng.standard_normal((1000, 3))
+    d = torch.from_numpy((d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32))
+    out["sh_forward"] = sh.SHEncoder(degree=4)(d).numpy()
+    # training composites, forward + backward
+    M, N = 4000, 64
+    cnt = torch.full((N,), M // N, dtype=torch.int32)
+    rays = torch.stack([torch.arange(N, dtype=torch.int32), (torch.arange(N, dtype=torch.int32) * (M // N)), cnt], 1).contiguous()
+    f32 = lambda a: torch.from_numpy(a.astype(np.float32))
+    sig = f32(rng.random(M) * 30).requires_grad_(True)
+    rgb = f32(rng.random((M, 3))).requires_grad_(True)
+    deltas = f32(rng.random((M, 2)) * 0.01 + 0.003)
+    o = rm.composite_rays_train(sig, rgb, deltas, rays, 1e-4)
+    gs, gr = torch.autograd.grad((o[0].sum() + (o[2] ** 2).sum()), (sig, rgb))
+    for i, t in enumerate(o):
+        out[f"composite_train_out{i}"] = t.detach().numpy()
+    out["composite_train_grad_sigmas"], out["composite_train_grad_rgbs"] = gs.numpy(), gr.numpy()
+    inp = f32(rng.random((M, 33))).requires_grad_(True)
+    fo = rm.composite_rays_flex_train(sig, inp, deltas, rays, 1e-4)
+    out["composite_flex_train"] = fo.detach().numpy()
+    out["composite_flex_train_grad"] = torch.autograd.grad((fo ** 2).sum(), inp)[0].numpy()
+    # inference composites, in place
+    n_alive, n_step = 50, 4
+    alive = torch.arange(n_alive, dtype=torch.int32)
+    st = (alive.clone(), torch.full((N,), 0.5), torch.zeros(N), torch.zeros(N), torch.zeros(N, 3))
+    sg, cl, dl = f32(rng.random(n_alive * n_step) * 40), f32(rng.random((n_alive * n_step, 3))), f32(rng.random((n_alive * n_step, 2)) * 0.01 + 0.003)
+    rm.composite_rays(n_alive, n_step, st[0], st[1], sg, cl, dl, st[2], st[3], st[4], 1e-4)
+    for name, t in zip(("alive", "t", "weights_sum", "depth", "image"), st):
+        out[f"composite_infer_{name}"] = t.numpy()
+    o1 = torch.zeros(N, 12)
+    rm.composite_rays_flex(n_alive, n_step, 12, alive.clone(), torch.full((N,), 0.5), sg, f32(rng.random((n_alive * n_step, 12))), dl, torch.zeros(N), o1, 1e-4)
+    out["composite_flex_infer"] = o1.numpy()
+    return out
+
+
+def digests(arrays):
+    """{name: [dtype, shape, sha256 of the bytes]}: the exact results, small enough to commit."""
+    import hashlib
+    return {k: [str(a.dtype), list(a.shape), hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()] for k, a in sorted(arrays.items())}
+
+
+def gen_wrapper_digests():
+    """wrapper_digests.json: digests of wrapper_outputs() through the reference's own gridencoder/grid.py, shencoder/sphere_harmonics.py and the
+    composite Functions of raymarching/raymarching.py (their `_backend` = oracle/native_facade.py).  oracle/facade.py -- the restatement bench.py's
+    cpu_baseline and the host-logic tests use -- must give the very same bytes, here and in tests/test_oracle.py."""
+    import json
+    import warnings
+    import_reference()
+    import raymarching as ref_rm, gridencoder as ref_ge, shencoder as ref_sh  # noqa: E401
+    from gridencoder.grid import grid_encode as ref_grid_encode
+
+    def ref_half(x01, emb, offsets, pls):      # the reference's wrapper hands a half table to the kernel when autocast is on
+        real = torch.is_autocast_enabled
+        torch.is_autocast_enabled = lambda *a_, **k_: True
+        try:
+            y = ref_grid_encode(torch.from_numpy(x01), torch.from_numpy(emb), torch.from_numpy(offsets), pls, 16, False, 0, False)
+        finally:
+            torch.is_autocast_enabled = real
+        assert y.dtype == torch.float16
+        return y.numpy()
+
+    warnings.simplefilter("ignore")
+    ref = digests(wrapper_outputs(ref_rm, ref_ge, ref_sh, ref_half))
+    rm, ge, sh, _ = make_oracle_modules()
+    mine = digests(wrapper_outputs(rm, ge, sh, oracle_half_encode))
+    assert ref == mine, [k for k in ref if ref[k] != mine.get(k)]
+    json.dump(ref, open(os.path.join(HERE, "wrapper_digests.json"), "w"), indent=0, sort_keys=True)
+    print("wrapper digests", len(ref))
+
+
+def oracle_half_encode(x01, emb, offsets, pls):
+    return oracle.grid_encode_forward(x01, emb.astype(np.float16), offsets, pls, 16)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["sh", "frames"]
+    if "wrappers" in which:
+        gen_wrapper_digests()
     if "occupancy" in which:
         gen_occupancy()
     if "grid_autocast" in which:

@@ -123,3 +123,33 @@ def test_child_passes_of_a_rank_never_see_the_launcher(monkeypatch):
     assert l2["algorithmic_bytes_per_sample"] == 2328 and "note" in l2 and l2["closer_ceiling"]["name"].startswith("hbm") and l2["closer_ceiling"]["frac"] == l2["hbm_frac_of_measured_traffic"]
     none = bench.roofline_block("k", 100.0, None, None, 1, 1.0, 10, 1164, 1)
     assert none["traffic"] is None and "hbm_frac_of_measured_traffic" not in none
+
+
+def test_dump_outputs_types_cap_and_repeatable_sample(tmp_path, monkeypatch):
+    """--dump-outputs: tensors only, float64 kept and integer counts widened to float64 (exact), every other dtype as float32; a set that would exceed the
+    64 MB cap is cut to the same fixed share of every array, at positions that depend on the sizes alone (two runs compare element for element)."""
+    import numpy as np
+    import torch
+    small = {"image": torch.rand(1, 1000, 3), "t64": torch.rand(7, dtype=torch.float64), "rendered": torch.tensor([123456789], dtype=torch.int64),
+             "count32": torch.tensor([5, 6], dtype=torch.int32), "half": torch.rand(4).half(), "n_samples": 17}
+    w = bench.dump_outputs(str(tmp_path / "a"), small)
+    assert sorted(os.listdir(tmp_path / "a")) == ["count32.npy", "half.npy", "image.npy", "rendered.npy", "t64.npy"]
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in w}
+    assert got["image"].dtype == np.float32 and got["image"].shape == (1, 1000, 3) and np.array_equal(got["image"], small["image"].numpy())
+    assert got["t64"].dtype == np.float64 and np.array_equal(got["t64"], small["t64"].numpy())
+    assert got["rendered"].dtype == np.float64 and got["rendered"][0] == 123456789 and got["count32"].dtype == np.float64
+    assert got["half"].dtype == np.float32 and np.array_equal(got["half"], small["half"].float().numpy())
+    # the real cap: 80 MB of float32 in, at most 64 MB on disk
+    big = {"rows": torch.rand(16_000_000), "image": torch.rand(1, 1_000_000, 3)}
+    w = bench.dump_outputs(str(tmp_path / "b"), big)
+    on_disk = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert on_disk <= 64_000_000 and on_disk > 0.9 * bench.DUMP_BUDGET_BYTES
+    assert w["rows"][1] == [16_000_000] and w["image"][1] == [1, 1_000_000, 3] and w["rows"][0][0] < 16_000_000
+    # the sample: sorted positions of the full array, the same in every run for the same sizes
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4000)
+    ramp = {"x": torch.arange(2000, dtype=torch.float32), "y": torch.arange(1000, dtype=torch.float32)}
+    bench.dump_outputs(str(tmp_path / "c"), ramp)
+    bench.dump_outputs(str(tmp_path / "d"), {k: v.clone() for k, v in ramp.items()})
+    for k, n in (("x", 2000), ("y", 1000)):
+        a, b = np.load(tmp_path / "c" / f"{k}.npy"), np.load(tmp_path / "d" / f"{k}.npy")
+        assert np.array_equal(a, b) and a.size == n // 3 and np.all(np.diff(a) > 0) and a.max() < n

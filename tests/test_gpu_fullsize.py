@@ -275,7 +275,7 @@ def test_bench_line_with_frames_in_flight_over_rccl(cuda):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PNR_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547")
-    common = [sys.executable, os.path.join(root, "bench.py"), "--res", "200", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-extras"]
+    common = [sys.executable, os.path.join(root, "bench.py"), "--full", "--res", "200", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-extras"]
     lines = []
     for extra in ([], ["--main-frames-in-flight", "2"]):
         out = subprocess.run(common + extra, env=env, cwd=root, capture_output=True, text=True, timeout=600)
@@ -298,7 +298,7 @@ def test_bench_default_line_for_more_than_one_rank_over_rccl(cuda):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PNR_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29549")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--dist-default", "--steps", "4", "--warmup", "2", "--extra-steps", "5", "--res", "200", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--dist-default", "--steps", "4", "--warmup", "2", "--extra-steps", "5", "--res", "200", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

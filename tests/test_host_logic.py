@@ -13,17 +13,22 @@ from oracle.facade import make_oracle_modules
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 
-@pytest.fixture()
-def facade(monkeypatch):
+def install_facade(setattr_=setattr):
+    """The oracle's facades in place of the mirror's kernel layer (`setattr_`: monkeypatch.setattr in a test, plain setattr in a child process)."""
     rm, ge, sh, pu = make_oracle_modules()
     import palettenerf_amd.gridencoder as pge
     import palettenerf_amd.shencoder as psh
-    monkeypatch.setattr(renderer, "raymarching", rm)
-    monkeypatch.setattr(renderer, "rgb_to_hsv", pu.rgb_to_hsv)
-    monkeypatch.setattr(renderer, "hsv_to_rgb", pu.hsv_to_rgb)
-    monkeypatch.setattr(pge, "GridEncoder", ge.GridEncoder)
-    monkeypatch.setattr(psh, "SHEncoder", sh.SHEncoder)
+    setattr_(renderer, "raymarching", rm)
+    setattr_(renderer, "rgb_to_hsv", pu.rgb_to_hsv)
+    setattr_(renderer, "hsv_to_rgb", pu.hsv_to_rgb)
+    setattr_(pge, "GridEncoder", ge.GridEncoder)
+    setattr_(psh, "SHEncoder", sh.SHEncoder)
     return rm
+
+
+@pytest.fixture()
+def facade(monkeypatch):
+    return install_facade(monkeypatch.setattr)
 
 
 def rays(g):
@@ -263,11 +268,8 @@ def test_get_rays_oracle_and_index_selection_against_the_reference():
     np.testing.assert_array_equal(rays._pair_indices(H, W, 64, 3, "cpu").numpy(), g["pair_inds"][0])
 
 
-@pytest.mark.parametrize("case", ["a", "b"])
-def test_uniform_sampling_path_reproduces_the_reference_run(facade, case):
-    """BASELINE configs[0]: NeRFRenderer.run without an occupancy grid (nerf/renderer.py:127-255) -- goldens made by the reference's own
-    run() (tests/golden/gen_golden.py run).  Both the direct call and the staged render() dispatcher (4096-ray batches in the reference,
-    small ones here) must give the frame."""
+def uniform_sampling_frames(case, out):
+    """The frame of run_nerf_<case>.npz through the mirror's run() and its staged render() dispatcher, written to `out` (.npz); needs the facade."""
     g = np.load(os.path.join(GOLDEN, f"run_nerf_{case}.npz"))
     m = network.NeRFNetwork(bound=2, cuda_ray=False, density_scale=float(g["density_scale"]), min_near=0.2)
     scene.seed_field_(m, int(g["seed"]))
@@ -277,6 +279,31 @@ def test_uniform_sampling_path_reproduces_the_reference_run(facade, case):
     with torch.no_grad():
         r = m.run(ro, rd, **kw)
         rs = m.render(ro, rd, staged=True, max_ray_batch=100, **kw)
+    np.savez(out, **{k: r[k].numpy() for k in ("image", "depth", "weights_sum")}, **{"staged_" + k: rs[k].numpy() for k in ("image", "depth", "weights_sum")})
+
+
+@pytest.mark.parametrize("case", ["a", "b"])
+def test_uniform_sampling_path_reproduces_the_reference_run(case, tmp_path):
+    """BASELINE configs[0]: NeRFRenderer.run without an occupancy grid (nerf/renderer.py:127-255) -- goldens made by the reference's own
+    run() (tests/golden/gen_golden.py run).  Both the direct call and the staged render() dispatcher (4096-ray batches in the reference,
+    small ones here) must give the frame.  The frame is rendered in a child process under gen_golden.PINNED_CPU_ENV, the CPU arithmetic the
+    goldens were recorded under: the upsampling's inverse CDF turns the last-bit differences of a host's vector kernels into 5e-5 on a few pixels."""
+    import importlib.util
+    import subprocess
+    import sys
+    spec = importlib.util.spec_from_file_location("gen_golden", os.path.join(GOLDEN, "gen_golden.py"))
+    gg = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gg)
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    out = str(tmp_path / "frames.npz")
+    code = (f"import sys; sys.path.insert(0, {root!r}); from tests import test_host_logic as t; t.install_facade(); "
+            f"t.uniform_sampling_frames({case!r}, {out!r})")
+    p = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, **gg.PINNED_CPU_ENV), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    got = np.load(out)
+    g = np.load(os.path.join(GOLDEN, f"run_nerf_{case}.npz"))
+    r = {k: torch.from_numpy(got[k]) for k in ("image", "depth", "weights_sum")}
+    rs = {k: torch.from_numpy(got["staged_" + k]) for k in ("image", "depth", "weights_sum")}
     for k in ("image", "depth", "weights_sum"):
         np.testing.assert_allclose(r[k].numpy(), g[k], rtol=0, atol=2e-6, err_msg=k)
         np.testing.assert_allclose(rs[k].numpy(), g[k], rtol=0, atol=2e-6, err_msg="staged " + k)
