@@ -24,6 +24,7 @@
 // palette_field.hip (internal): device image of the edit parameters
 uint64_t pnr_internal_edit_device_bytes();
 int pnr_internal_edit_upload(const pnr_palette_edit* edit, void* dst, hipStream_t s);
+int pnr_internal_palette_field_forward(const pnr_palette_field_args* a, pnr_stream_t stream, int waves12);
 
 #ifndef PNR_FRAME_LEVEL_PAIRS
 #define PNR_FRAME_LEVEL_PAIRS 1
@@ -1208,8 +1209,20 @@ uint64_t pnr_palette_frame_workspace_bytes(uint32_t N, uint32_t num_basis, uint3
 // phase: kWhole = the frame call; kSubmit = enqueue the frame's first chunk of iterations, its last launch and the control-block read-back, then return WITHOUT
 // waiting (the caller prepares its next frame while this one runs); kFinish = wait for that read-back, enqueue further chunks while the frame is not done (the
 // iteration count is data), fill stats / kernel_ms.  kFinish must follow kSubmit on the same host thread, device, stream and argument struct, with nothing of the
-// frame's buffers touched in between; kWhole = kSubmit + kFinish.
+// frame's buffers touched in between (the stream, N and the workspace are checked; the option switches are the ones kSubmit read); kWhole = kSubmit + kFinish.
 enum FramePhase { kWhole = 0, kSubmit = 1, kFinish = 2 };
+// The pnr_set_option switches a frame's launches depend on, read ONCE per frame: by kWhole / kSubmit, and kept for kFinish in the submitted frame's record,
+// so that a pnr_set_option between the two halves cannot give the finish call's chunks another configuration than the chunks already in the stream.
+struct FrameOpts {
+    int aux_fusion, composite_fusion, hosted_tail, dynamic_tiles, march_budget, march_budget0, march_blocks, iteration_margin, block_skip, coop_march, palette_waves12;
+};
+static FrameOpts frame_opts_now() {
+    FrameOpts o;
+    o.aux_fusion = g_opt_aux_fusion; o.composite_fusion = g_opt_composite_fusion; o.hosted_tail = g_opt_hosted_tail; o.dynamic_tiles = g_opt_dynamic_tiles;
+    o.march_budget = g_opt_march_budget; o.march_budget0 = g_opt_march_budget0; o.march_blocks = g_opt_march_blocks; o.iteration_margin = g_opt_iteration_margin;
+    o.block_skip = g_opt_block_skip; o.coop_march = g_opt_coop_march; o.palette_waves12 = g_opt_palette_waves12;
+    return o;
+}
 static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_frame_args* pal, pnr_stream_t stream, FramePhase phase);
 
 int pnr_nerf_render_frame(const pnr_nerf_frame_args* a, pnr_stream_t stream) { return render_frame_impl(a, nullptr, stream, kWhole); }
@@ -1257,11 +1270,43 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
         in_o = w.s_o; in_d = w.s_d; in_far = w.s_far;
         out_ws = w.s_ws; out_depth = w.s_depth; out_image = w.s_image; out_aux = pal ? w.s_aux : nullptr;
     }
+    // per host thread AND per device (a process may drive several GPUs): the pinned read-back slot, the timing events and the iteration
+    // prediction of the previous frame rendered there
+    // (released when the host thread ends: a pool that replaces its worker threads does not accumulate pinned blocks and events)
+    struct PerDevice {
+        FrameCtl* host_ctl = nullptr; std::vector<hipEvent_t> ev; uint32_t predicted_iterations = 0; hipEvent_t done_ev = nullptr;
+        // a frame submitted and not yet finished (pnr_*_render_frame_submit): what its finish call continues from, and what it must be continued WITH --
+        // the stream, the frame's size and workspace (checked) and the option snapshot its launches were shaped by (reused)
+        struct Pending {
+            bool on = false; const void* args = nullptr; int iter = 0; uint32_t alive_ub = 0, chunk = 0, looks = 0, prev_partials = 0; size_t ev_used = 0;
+            pnr_stream_t stream = nullptr; uint32_t N = 0; const void* workspace = nullptr; FrameOpts opts = {};
+        } pending;
+        ~PerDevice() {
+            if (host_ctl) (void)hipHostFree(host_ctl);
+            if (done_ev) (void)hipEventDestroy(done_ev);
+            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        }
+    };
+    static thread_local PerDevice per_device[kMaxDevices];
+    PerDevice& dev_state = per_device[current_device()];
+    FrameCtl*& host_ctl = dev_state.host_ctl;  // one in-flight frame per host thread and device
+    if (!host_ctl && hipHostMalloc(reinterpret_cast<void**>(&host_ctl), sizeof(FrameCtl), hipHostMallocPortable) != hipSuccess) return PNR_ERR_LAUNCH;
+
+    auto& pending = dev_state.pending;
+    // _finish continues exactly the frame _submit started.  Every check comes before anything is enqueued: a finish with another stream, frame size or workspace
+    // would launch over another carve of the workspace (or into another stream) -- it is refused and the frame stays pending, so that the right finish call
+    // can still complete it.
+    if (phase == kFinish) {
+        if (!pending.on || pending.args != static_cast<const void*>(pal ? static_cast<const void*>(pal) : static_cast<const void*>(a))) return PNR_ERR_INVALID;   // no frame of THIS struct was submitted on this thread and device
+        if (pending.stream != stream || pending.N != a->N || pending.workspace != a->workspace) return PNR_ERR_INVALID;
+    }
+    const FrameOpts opt = phase == kFinish ? pending.opts : frame_opts_now();
+
     const float* tables[3] = {a->embeddings, pal ? pal->embeddings_palette : nullptr, with_clip ? pal->embeddings_clip : nullptr};
     const uint32_t n_enc = pal ? (with_clip ? 3u : 2u) : 1u;
-    const int aux_fused = (pal && g_opt_aux_fusion && pnr_palette_field_stages_aux(pal->num_basis, pal->clip_dim, pal->pred_clip)) ? 1 : 0;
-    const int composite_fused = (!pal && g_opt_composite_fusion) ? g_opt_composite_fusion : 0;   // NeRF: 1 = one-sample-per-ray iterations are composited inside the field kernel, 2 = all of them (no composite launch)
-    const bool pal_composite_fused = pal && aux_fused && g_opt_composite_fusion == 2;   // PaletteNeRF: the ray state is composited inside the field kernel as well (needs the staged aux rows)
+    const int aux_fused = (pal && opt.aux_fusion && pnr_palette_field_stages_aux(pal->num_basis, pal->clip_dim, pal->pred_clip)) ? 1 : 0;
+    const int composite_fused = (!pal && opt.composite_fusion) ? opt.composite_fusion : 0;   // NeRF: 1 = one-sample-per-ray iterations are composited inside the field kernel, 2 = all of them (no composite launch)
+    const bool pal_composite_fused = pal && aux_fused && opt.composite_fusion == 2;   // PaletteNeRF: the ray state is composited inside the field kernel as well (needs the staged aux rows)
     const bool half_tables = a->table_dtype == PNR_DTYPE_F16;   // fp16 tables: nerf = `embeddings` as halves; palette = embeddings_pair as interleaved halves
     if (half_tables && pal && (with_clip || !pal->embeddings_pair)) return PNR_ERR_UNSUPPORTED;
     if (a->table_dtype != PNR_DTYPE_F32 && a->table_dtype != PNR_DTYPE_F16) return PNR_ERR_UNSUPPORTED;
@@ -1276,7 +1321,7 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
         pf.precision = a->field_precision; pf.xyzs = w.xyzs;
         for (int k = 0; k < 3; k++) pf.enc_scale[k] = a->enc_scale[k];
         pf.overflow_flag = a->watch_overflow ? w.scratch + 1 : nullptr;
-        pf.tile_counter = g_opt_dynamic_tiles ? w.scratch + 2 : nullptr;
+        pf.tile_counter = opt.dynamic_tiles ? w.scratch + 2 : nullptr;
         if (pal->edit && pal->edit->mode != 0) {   // RegionEdit / Stylizer: parameters uploaded once for the whole frame
             if (phase != kFinish) {
                 const int rc = pnr_internal_edit_upload(pal->edit, w.edit, s);
@@ -1286,32 +1331,15 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
         }
     }
 
-    // per host thread AND per device (a process may drive several GPUs): the pinned read-back slot, the timing events and the iteration
-    // prediction of the previous frame rendered there
-    // (released when the host thread ends: a pool that replaces its worker threads does not accumulate pinned blocks and events)
-    struct PerDevice {
-        FrameCtl* host_ctl = nullptr; std::vector<hipEvent_t> ev; uint32_t predicted_iterations = 0; hipEvent_t done_ev = nullptr;
-        // a frame submitted and not yet finished (pnr_*_render_frame_submit): what its finish call continues from
-        struct Pending { bool on = false; const void* args = nullptr; int iter = 0; uint32_t alive_ub = 0, chunk = 0, looks = 0, prev_partials = 0; size_t ev_used = 0; } pending;
-        ~PerDevice() {
-            if (host_ctl) (void)hipHostFree(host_ctl);
-            if (done_ev) (void)hipEventDestroy(done_ev);
-            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        }
-    };
-    static thread_local PerDevice per_device[kMaxDevices];
-    PerDevice& dev_state = per_device[current_device()];
-    FrameCtl*& host_ctl = dev_state.host_ctl;  // one in-flight frame per host thread and device
-    if (!host_ctl && hipHostMalloc(reinterpret_cast<void**>(&host_ctl), sizeof(FrameCtl), hipHostMallocPortable) != hipSuccess) return PNR_ERR_LAUNCH;
-
     const float enc_scale = a->enc_scale[0] > 0.0f ? a->enc_scale[0] : 1.0f;
     const bool use_mip = a->mip && (a->H % 4) == 0 && pnr_occupancy_mip_bytes(a->C, a->H) <= 64 * 1024;
     const bool pow2 = is_pow2f(a->bound) && (a->H & (a->H - 1)) == 0;
-    const MarchParams mp = make_march_params(a->bound, a->dt_gamma, a->max_steps, a->C, a->H, use_mip);
+    MarchParams mp = make_march_params(a->bound, a->dt_gamma, a->max_steps, a->C, a->H, use_mip);
+    mp.block_skip = opt.block_skip ? 1u : 0u; mp.coop = opt.coop_march ? 1u : 0u;   // (the frame's snapshot, not the switches as they are now)
     const uint32_t march_lds = mp.mip_words ? (2 * mp.mip_words + 8) * 4 : 0;
     const LevelParams lp = make_level_params(16, a->S, a->base_resolution);
     const uint32_t* mip = static_cast<const uint32_t*>(a->mip);
-    const bool hosted = g_opt_hosted_tail && use_mip && pow2 && mp.mip_words != 0 && (a->H % 64u) == 0;   // (what MODE 2 and hosted_march_tail are compiled for)
+    const bool hosted = opt.hosted_tail && use_mip && pow2 && mp.mip_words != 0 && (a->H % 64u) == 0;   // (what MODE 2 and hosted_march_tail are compiled for)
 
     const uint32_t cstride = N / kRayBlock + 2;
     auto counts_of = [&](int parity) { return w.scratch + kHdr + (uint32_t)(parity & 1) * cstride; };   // iteration i fills counts_of(i), its march reads counts_of(i + 1)
@@ -1322,10 +1350,7 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
     fb.order = a->ray_order; fb.rays_o = a->rays_o; fb.rays_d = a->rays_d; fb.nears_in = a->nears; fb.fars_in = a->fars;
     fb.aabb = a->aabb; fb.min_near = a->min_near; fb.nears_out = a->nears; fb.fars_out = a->fars;
     fb.so = w.s_o; fb.sd = w.s_d; fb.sf = w.s_far;
-    auto& pending = dev_state.pending;
-    if (phase == kFinish) {
-        if (!pending.on || pending.args != static_cast<const void*>(pal ? static_cast<const void*>(pal) : static_cast<const void*>(a))) return PNR_ERR_INVALID;   // no frame of THIS struct was submitted on this thread and device
-    } else {
+    if (phase != kFinish) {
         // one submitted frame per host thread and device: a second _submit is refused (finish the first one).  A WHOLE-frame call drops a submitted frame that
         // was never finished (the caller gave it up -- an exception between its two halves): its launches are in the stream in front of this frame's, nothing
         // waits for them any more, and this call would otherwise be refused for as long as the thread lives.
@@ -1373,7 +1398,7 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
     // (+1: the launch that finds no ray left is the one that reports it; + g_opt_iteration_margin spare iterations.  Along a camera path the
     // count drifts by one or two from frame to frame; a spare iteration is four early-exit launches (~19 us), a wrong guess one host round
     // trip.  Measured on the moving-camera benchmark the round trip is the cheaper of the two: the margin defaults to 0)
-    const uint32_t want = predicted_iterations + 1u + (uint32_t)g_opt_iteration_margin;
+    const uint32_t want = predicted_iterations + 1u + (uint32_t)opt.iteration_margin;
     uint32_t chunk = predicted_iterations ? (want < 1024u ? want : 1024u) : 8u;
     uint32_t looks = 0;
     uint32_t prev_partials = 0;   // workgroups of the previous march launch (= sample partials to add up)
@@ -1391,7 +1416,7 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
             const uint32_t ray_blocks = cdiv(alive_ub, kRayBlock);
             const uint32_t rows_ub = (uint64_t)alive_ub * 8 < N ? alive_ub * 8 : N;
             // hosted tail (MODE 2): the march gives every ray `budget` sample-less probes and queues the rest for the lookup launch's first workgroups
-            const uint32_t budget = hosted ? (uint32_t)(iter == 0 ? g_opt_march_budget0 : g_opt_march_budget) : 0u;
+            const uint32_t budget = hosted ? (uint32_t)(iter == 0 ? opt.march_budget0 : opt.march_budget) : 0u;
             const int mode = budget ? 2 : 1;
             // MODE 2 runs five workgroups per CU (1 280 resident).  A typical later lego launch has 1 352 chunks: its last 72 workgroups start ~8 us late
             // (launch 16.9 us), and capping the launch at 1 280 is no way out -- a workgroup's second chunk waits at the block barriers for the slowest
@@ -1400,7 +1425,7 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
             const uint32_t kResident = 1280;
             uint32_t march_cap = kMaxMarchBlocks;
             if (mode == 2) {
-                if (g_opt_march_blocks > 0 && g_opt_march_blocks < 65536) march_cap = (uint32_t)g_opt_march_blocks < kMaxMarchBlocks ? (uint32_t)g_opt_march_blocks : kMaxMarchBlocks;
+                if (opt.march_blocks > 0 && opt.march_blocks < 65536) march_cap = (uint32_t)opt.march_blocks < kMaxMarchBlocks ? (uint32_t)opt.march_blocks : kMaxMarchBlocks;
                 else if (ray_blocks >= 2 * kResident) march_cap = kResident;
             }
             const dim3 gm(ray_blocks < march_cap ? ray_blocks : march_cap), bm(kRayBlock);
@@ -1462,7 +1487,7 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
                 if (pal_composite_fused) {   // the field kernel does the whole compositing step: no composite launch
                     pf.rays_t = w.rays_t; pf.weights_sum_rw = out_ws; pf.depth = out_depth; pf.image = out_image; pf.rays_alive_rw = alive_in; pf.counts_cur = counts_of(iter);
                 }
-                const int rc = pnr_palette_field_forward(&pf, stream);
+                const int rc = pnr_internal_palette_field_forward(&pf, stream, opt.palette_waves12);
                 if (rc != PNR_OK) return rc;
             } else if (a->field_precision == PNR_FIELD_FP32)
                 hipLaunchKernelGGL((k_frame_field<0, false>), dim3(gx < 512u ? gx : 512u), dim3(kFieldThreads), 0, s, cur, w.enc, N, w.dirs, w.deltas,
@@ -1502,6 +1527,7 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
         if (phase == kSubmit) {
             pending.on = true; pending.args = pal ? static_cast<const void*>(pal) : static_cast<const void*>(a);
             pending.iter = iter; pending.alive_ub = alive_ub; pending.chunk = chunk; pending.looks = looks; pending.prev_partials = prev_partials; pending.ev_used = ev_used;
+            pending.stream = stream; pending.N = N; pending.workspace = a->workspace; pending.opts = opt;
             return check_launch();
         }
     }

@@ -968,8 +968,6 @@ int pnr_internal_edit_upload(const pnr_palette_edit* edit, void* dst, hipStream_
     return hipMemcpyAsync(dst, &e, sizeof(e), hipMemcpyHostToDevice, s) == hipSuccess ? PNR_OK : PNR_ERR_LAUNCH;   // pageable source: staged before the call returns
 }
 
-extern int g_opt_palette_waves12;
-
 #ifdef PNR_PAL_TIMING
 // diagnostic builds only (not in include/pnr.h): out != NULL: copy the PT_N + 3 accumulators out; reset != 0: zero them
 extern "C" int pnr_debug_pal_timing(unsigned long long* out, int reset) {
@@ -1040,7 +1038,10 @@ int pnr_palette_field_stages_aux(uint32_t num_basis, uint32_t clip_dim, int pred
     return packed_bytes + (kPalThreads / 64) * 32 * (aux_stride + 3) * 4 <= 160 * 1024;
 }
 
-int pnr_palette_field_forward(const pnr_palette_field_args* a, pnr_stream_t stream) {
+}  // extern "C"
+
+// internal (frame.hip): the field launch with the wide-kernel switch given by the caller -- a frame call keeps the value its submit half read
+int pnr_internal_palette_field_forward(const pnr_palette_field_args* a, pnr_stream_t stream, int waves12) {
     if (!a) return PNR_ERR_INVALID;
     if (!shape_ok(a->num_basis, a->clip_dim)) return PNR_ERR_UNSUPPORTED;
     if (a->precision != PNR_FIELD_FP32 && a->precision != PNR_FIELD_F16X3 && a->precision != PNR_FIELD_F16X2) return PNR_ERR_UNSUPPORTED;
@@ -1066,7 +1067,7 @@ int pnr_palette_field_forward(const pnr_palette_field_args* a, pnr_stream_t stre
     const bool x2 = a->precision == PNR_FIELD_F16X2 && nb4 && edit_mode == 0;
     // "wide": the specialised kernels for the shipped shape -- 4 bases, no clip head, rows of 36 floats -- whose tail stages nothing in LDS (see the top of
     // the file): PNR_PAL_WIDE_WAVES waves per workgroup (16: four per SIMD at <= 128 registers) next to 100 KiB of weights + 384 bytes per wave
-    const bool wide = nb4 && g_opt_palette_waves12 && !pp.pred_clip && a->aux_stride == 36u && a->aux_stride == pnr_palette_aux_channels(a->num_basis, a->clip_dim);
+    const bool wide = nb4 && waves12 && !pp.pred_clip && a->aux_stride == 36u && a->aux_stride == pnr_palette_aux_channels(a->num_basis, a->clip_dim);
     const uint32_t waves = wide ? (uint32_t)PNR_PAL_WIDE_WAVES : 8u;
     const uint32_t ntiles = cdiv(rows_ub ? rows_ub : 1, 28);   // wave tiles (a wave tile holds 28 ... 32 rows when it holds whole rays): dealt wave-major, see the kernel
     const uint32_t grid = ntiles < 256u ? ntiles : 256u;
@@ -1140,6 +1141,12 @@ int pnr_palette_field_forward(const pnr_palette_field_args* a, pnr_stream_t stre
 #undef PNR_LAUNCH_PAL_NB
     if (edit_slot >= 0 && hipEventRecord(g_edit_ring[current_device()].used[edit_slot], s) != hipSuccess) return PNR_ERR_LAUNCH;
     return check_launch();
+}
+
+extern "C" {
+
+int pnr_palette_field_forward(const pnr_palette_field_args* a, pnr_stream_t stream) {
+    return pnr_internal_palette_field_forward(a, stream, g_opt_palette_waves12);
 }
 
 }  // extern "C"

@@ -120,6 +120,7 @@ extern int g_opt_march_budget, g_opt_march_budget0;   // that budget in probe ro
 extern int g_opt_march_blocks;   // frame loops: workgroup cap of a budgeted march launch
 extern int g_opt_aux_fusion;   // PaletteNeRF frame loop: aux composite inside the field kernel
 extern int g_opt_composite_fusion;   // NeRF frame loop: 1 = n_step == 1 iterations composited inside the field kernel, 2 = every iteration (no composite launch)
+extern int g_opt_palette_waves12;    // PaletteNeRF field: the wide (PNR_PAL_WIDE_WAVES-wave) kernels for the shipped 4-basis shape (palette_field.hip)
 extern int g_opt_dynamic_tiles;      // frame loops: field kernels hand wave tiles out through a device counter instead of a static schedule
 extern int g_opt_grid_fast;          // stand-alone lookup op: k_grid_fwd_d3c2 for D = 3, C = 2 (gridencoder.hip)
 extern int g_opt_train_coop;  // training march: cooperative counting pass

@@ -42,7 +42,7 @@ def install(patch_palette_utils=True):
     return installed
 
 
-def fuse_field(model, precision="f16x3"):
+def fuse_field(model, precision="f16x3", pair_lookup=False):
     """Opt-in, one step beyond the operator boundary: give a NeRFNetwork or PaletteNetwork -- the REFERENCE's own class (nerf/network.py, built over the drop-in
     encoders after install()) or this package's mirror -- the fused MFMA field kernel as its forward() for inference batches.  The reference's
     renderer (`run_cuda`'s while loop, its boolean-mask compaction, its composite_rays calls) and its network file stay unchanged; what
@@ -50,7 +50,10 @@ def fuse_field(model, precision="f16x3"):
     matrix cores, pnr_nerf_field_forward) instead of encoder permute-copy + 5 GEMMs + 6 elementwise launches.  Same (sigma, rgb) to 2e-6
     (tests/test_gpu_ops.py), images to 1e-4 of the reference-driven goldens (tests/test_gpu_frames.py).  Batches under autograd or autocast, and
     CPU tensors, keep the model's own forward.  The model must have the shipped architecture (hashgrid 16 x 2, 64-wide nets, SH degree 4);
-    NeRFFieldFused raises otherwise.  precision: "f16x3" (split-fp16 products, fp32-class), "fp32" (exact fmaf chains) or "f16x2" (opt-in)."""
+    NeRFFieldFused raises otherwise.  precision: "f16x3" (split-fp16 products, fp32-class), "fp32" (exact fmaf chains) or "f16x2" (opt-in).
+    pair_lookup (PaletteNetwork only): look both hash tables up through one interleaved copy (PaletteFieldFused.stand_alone_pair).  The copy follows torch's
+    version counters only: after writing the tables through `.data` (torch_ema's copy_to / restore around an evaluation) call
+    invalidate_fused_caches(model), or the forward reads the old tables.  Default: the live tables, whatever wrote them."""
     import torch
     from .fused import NeRFFieldFused, PaletteFieldFused
     plain = model.forward
@@ -61,13 +64,14 @@ def fuse_field(model, precision="f16x3"):
         # the device as one launch (below).
         fused = PaletteFieldFused(model)
         fused.precision = {"fp32": 0, "f16x3": 1, "f16x2": 1}[precision]
+        fused.stand_alone_pair = bool(pair_lookup)
 
         def run(x, d):
             out = fused.network_forward(x, d)
             # what follows an inference forward() in run_cuda are the iteration's six / seven composite_rays_flex calls and then composite_rays
             # (palette/renderer.py:508-519): they are collected and issued as ONE pnr_composite_rays_flex_multi launch in front of that composite_rays
-            # (raymarching._FlexQueue: same bits; the deferral ends with that call)
-            _rm.arm_flex_deferral()
+            # (raymarching._FlexQueue: same bits; the deferral ends with that call, and arms only inside a march iteration, for its rays)
+            _rm.arm_flex_deferral_in_iteration()
             return out
     else:
         fused = NeRFFieldFused(model)

@@ -325,6 +325,9 @@ class _PrecisionGuard:
     def _note_overflow(self):
         import warnings
         self._overflowed_key = self._guard_key
+        # frames prepared before this point carry the split-fp16 precision and watch in their argument structs: frame_launch refuses them (StaleFrame) and
+        # render_launch prepares them again, on the exact fp32 path
+        self._gen = self.__dict__.get("_gen", 0) + 1
         warnings.warn("fused field: an activation left fp16's range (> 65504) in the split-fp16 matrix path: the frame is rendered again on the exact "
                       "fp32 path, which these weights keep from now on")
 
@@ -471,6 +474,7 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch):
 
     def invalidate_caches(self):
         self.versions = None
+        self._blobs = {}
         self._emb_half = None
         self._guard_key = None
         self._watch_ref = None       # the next frame rebuilds every blob: its source checksums become the reference
@@ -494,18 +498,29 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch):
         c1 = l1[3] * c0
         return max(enc, h1, geo, c0, c1)
 
+    def _blob_key(self, prec):
+        """What the blob of precision `prec` is derived from: every weight of the field and the precision (the blob's layout depends on it)."""
+        return tuple(_pkey(w) for w in self._w()) + (prec,)
+
     def _pack(self, prec=None):
-        ws = self._w()
+        """The MFMA-ordered weight blob for `prec`: one blob per precision (the stand-alone ops may run fp32 where the frame loops run split-fp16 with the
+        watch, and a frame prepared or in flight at one precision must never see the other's layout), each packed into a NEW tensor when its sources change --
+        never rewritten in place, so the tensor a kept or submitted argument struct points at (frame tokens hold it) stays as it was."""
         prec = self.effective_precision() if prec is None else prec
-        versions = tuple(_pkey(w) for w in ws) + (prec,)
-        if self.packed is None or versions != self.versions or PARANOID:
-            dev = ws[0].device
-            if self.packed is None or self.packed.device != dev:
-                self.packed = torch.empty(int(_lib.load().pnr_nerf_field_packed_bytes()) // 4, dtype=torch.float32, device=dev)
+        versions = self._blob_key(prec)
+        blobs = self.__dict__.get("_blobs")
+        if blobs is None:
+            blobs = self._blobs = {}
+        hit = blobs.get(prec)
+        ws = self._w()
+        dev = ws[0].device
+        if hit is None or hit[0] != versions or hit[1].device != dev or PARANOID:
+            blob = torch.empty(int(_lib.load().pnr_nerf_field_packed_bytes()) // 4, dtype=torch.float32, device=dev)
             ws = [require(w.detach().contiguous(), torch.float32, "weight") for w in ws]
-            call("pnr_nerf_field_pack", *[ptr(w) for w in ws], ptr(self.packed), _int(prec))
-            self.versions = versions
-        return self.packed
+            call("pnr_nerf_field_pack", *[ptr(w) for w in ws], ptr(blob), _int(prec))
+            hit = blobs[prec] = (versions, blob)
+        self.versions, self.packed = hit      # (the blob handed out last and its key)
+        return hit[1]
 
     @torch.no_grad()
     def render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0):
@@ -604,9 +619,10 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch):
             a.ray_order = order.data_ptr() if order is not None else None
             plan = plans[slot] = (plan_key, a, prec, watch, (emb, self._ws, order))     # (the tensors whose addresses the struct holds)
         a, prec, watch = plan[1], plan[2], plan[3]
-        # The packed blob is NOT part of the plan: the stand-alone ops on this object (`self(x, d)` from network.forward) repack it in place for THEIR precision
-        # (effective_precision() is fp32 where frame_precision() keeps split-fp16 with a watch).  _pack is a key compare when nothing changed.
-        a.packed_weights = self._pack(prec).data_ptr()
+        # The packed blob is NOT part of the plan: it is looked up per frame (a key compare when nothing changed) and the token keeps it alive; a repack -- new
+        # weights, or the stand-alone ops (`self(x, d)` from network.forward) asking for THEIR precision -- goes into another tensor (_pack).
+        blob = self._pack(prec)
+        a.packed_weights = blob.data_ptr()
         mip = raymarching.occupancy_mip(m.density_bitfield, m.cascade, m.grid_size, m.bound)
         stats = (ctypes.c_uint64 * 6)()
         a.rays_o, a.rays_d = rays_o.data_ptr(), rays_d.data_ptr()
@@ -623,7 +639,7 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch):
             require(t, torch.float32, name)
         return _FrameToken(gen=self.__dict__.get("_gen", 0), a=a, out=(ws, depth, image), stats=stats, kms=kms, watch_state=watch_state, watch=watch, finished=finished, nears=nears, fars=fars,
                            again=(rays_o, rays_d, None if aabb is not None else nears, None if aabb is not None else fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near),
-                           keep=(mip, bg_color))
+                           keep=(mip, bg_color, blob))
 
     def _frame_post(self, tok):
         valid = tok.valid if tok.valid is not None else _frame_valid(self, tok)
@@ -666,14 +682,8 @@ class DensityFused(NeRFFieldFused):
         enc = tmax[0] * scales[0]
         return max(enc, l1[0] * enc)
 
-    def _pack(self, prec=None):
-        prec = self.effective_precision() if prec is None else prec
-        versions = tuple(_pkey(w) for w in self._guard_weights()) + (prec,)
-        if self.packed is None or versions != self.versions or PARANOID:
-            self.versions = None
-            super()._pack(prec)
-            self.versions = versions
-        return self.packed
+    def _blob_key(self, prec):     # only the sigma_net part of the blob is read here: colour-head updates keep the blob
+        return tuple(_pkey(w) for w in self._guard_weights()) + (prec,)
 
     @torch.no_grad()
     def __call__(self, x, scale=1.0, want_geo=True, enc=None):
@@ -718,6 +728,10 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
         self.precision = 1              # PNR_FIELD_F16X3; 0 = PNR_FIELD_FP32 (exact fmaf chains, pnr_palette_*'s fp32 matrix path); 2 = PNR_FIELD_F16X2 (opt-in)
         self.supports_f16x2 = True      # honoured by the 4-basis kernel without an edit head; the library runs every other shape as F16X3
         self.interleave_tables = True   # native loop: look both hash tables up through one interleaved copy (see _pair_table)
+        # stand-alone calls (__call__ / network_forward: the dropin.fuse_field path) read the live tables by default.  True: they read the native loop's
+        # interleaved copy instead (one 16-byte gather for both lookups) -- a cache keyed on torch's version counters with no checksum on this path, so
+        # after a write through `.data` (torch_ema's copy_to / restore) invalidate_fused_caches(model) is REQUIRED, or the call reads the old tables
+        self.stand_alone_pair = False
         self.table_half = False         # native loop: fp16 tables with the reference's half interpolation (its --fp16 mode; no clip head)
         self.aux_channels = int(_lib.load().pnr_palette_aux_channels(self.nb, self.clip_dim))
 
@@ -1035,8 +1049,8 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
         dev = x.device
         x01 = ((x + m.bound) / (2 * m.bound)).contiguous()
         pair = None
-        if self.interleave_tables and not self.pred_clip and not self.table_half and pairable(m.encoder, m.encoder_palette):
-            pair = self._pair_table()       # the native loop's interleaved copy (rebuilt when either table changes): one 16-byte gather serves both lookups
+        if self.stand_alone_pair and self.interleave_tables and not self.pred_clip and not self.table_half and pairable(m.encoder, m.encoder_palette):
+            pair = self._pair_table()       # opt-in (stand_alone_pair): the native loop's interleaved copy, rebuilt when torch can tell either table changed
         if pair is not None:
             L = m.encoder.num_levels
             enc = torch.empty(L, B, 2, device=dev, dtype=torch.float32)

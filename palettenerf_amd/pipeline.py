@@ -15,7 +15,7 @@ import threading
 
 import torch
 
-_FUSED_SETTINGS = ("precision", "table_half", "interleave_tables", "ray_order", "time_grid_kernel")
+_FUSED_SETTINGS = ("precision", "table_half", "interleave_tables", "stand_alone_pair", "ray_order", "time_grid_kernel")
 
 
 def clone_for_concurrent_frames(model):

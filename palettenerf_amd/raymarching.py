@@ -327,9 +327,11 @@ _march_rays_now = _march_rays.apply
 
 
 def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, density_bitfield, C, H, near, far, align=-1, perturb=False, dt_gamma=0, max_steps=1024):
-    """raymarching/raymarching.py:347-398."""
-    if _flex_queues.q.shared is not None or _flex_queues.q.armed:
-        _flex_queues.q.flush()
+    """raymarching/raymarching.py:347-398.  Opens a march iteration on this thread (its rays: what arm_flex_deferral_in_iteration may defer composites of)."""
+    q = _flex_queues.q
+    if q.shared is not None or q.armed:
+        q.flush()
+    q.iteration = (rays_alive, rays_alive.data_ptr(), int(n_alive))
     return _march_rays_now(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, density_bitfield, C, H, near, far, align, perturb, dt_gamma, max_steps)
 
 
@@ -354,8 +356,10 @@ _composite_rays_now = _composite_rays.apply
 def composite_rays(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image, T_thresh=1e-2):
     """raymarching/raymarching.py:401-423 (in place; returns an empty tuple).  Queued flex composites (defer_flex_composites) are issued first: this call is the
     writer of what they read."""
-    if _flex_queues.q.shared is not None or _flex_queues.q.armed:
-        _flex_queues.q.flush()
+    q = _flex_queues.q
+    if q.shared is not None or q.armed:
+        q.flush()
+    q.iteration = None      # (the march iteration ends with its composite)
     return _composite_rays_now(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image, T_thresh)
 
 
@@ -403,11 +407,18 @@ class _FlexQueue:
     issued at any point before the next writer of what they read -- composite_rays (weights_sum, rays_alive).  With deferral on, a call is queued (the tensors are
     held) and the queue is issued as ONE pnr_composite_rays_flex_multi launch in front of the next composite_rays / march_rays / compact_alive of this module, or
     by flush_flex_composites() -- call that before reading a flex output that no composite_rays follows.  Calls whose shared arguments differ from the queue's
-    flush it first.  Results are bit for bit those of the immediate calls."""
+    flush it first.  Results are bit for bit those of the immediate calls.
+    One-shot forms: arm_flex_deferral() is the caller's own statement that the calls up to the next composite_rays belong to one iteration.  The drop-in's
+    implicit arming (arm_flex_deferral_in_iteration, behind every fused forward) is bound to a march iteration instead: it arms only while one is open (a
+    march_rays of this thread not yet followed by its composite_rays / compact_alive) and defers only calls on that iteration's rays (the same `rays_alive`
+    tensor, storage and n_alive).  Any other call -- a point query, an export script, the non-cuda_ray run() after a fused forward -- flushes the queue and
+    runs at once, so its `output` is written when it returns, as the reference's is."""
 
     def __init__(self):
         self.on = False
-        self.armed = False     # one-shot: on until the next flush (dropin.fuse_field arms it behind every fused PaletteNetwork.forward of an inference iteration)
+        self.armed = False     # one-shot: on until the next flush (dropin.fuse_field arms it behind every fused PaletteNetwork.forward inside a march iteration)
+        self.iteration = None  # (rays_alive, its data_ptr, n_alive) of the open march iteration: march_rays opens it, composite_rays / compact_alive close it
+        self.bound = None      # the iteration an implicit arming defers for (None: armed by the caller, or not armed)
         self.shared = None     # (n_alive, n_step, rays_alive, rays_t, sigmas, deltas, weights_sum, T_thresh)
         self.maps = []
 
@@ -422,6 +433,7 @@ class _FlexQueue:
 
     def flush(self):
         self.armed = False
+        self.bound = None
         if self.shared is None:
             return
         (n_alive, n_step, rays_alive, rays_t, sigmas, deltas, weights_sum, T_thresh), maps = self.shared, self.maps
@@ -457,14 +469,31 @@ def flush_flex_composites():
 
 def arm_flex_deferral():
     """Defer the composite_rays_flex calls from here up to the next composite_rays / march_rays / compact_alive / flush_flex_composites (one march iteration of
-    the reference's loop), then fall back to immediate calls."""
-    _flex_queues.q.armed = True
+    the reference's loop, driven by the caller), then fall back to immediate calls."""
+    q = _flex_queues.q
+    q.armed, q.bound = True, None
+
+
+def arm_flex_deferral_in_iteration():
+    """What dropin.fuse_field runs behind every fused PaletteNetwork.forward under no_grad: arm_flex_deferral for the rays of the march iteration that is open on
+    this thread -- and nothing when none is (a forward outside run_cuda's loop: its flex calls, if any, stay immediate)."""
+    q = _flex_queues.q
+    if q.iteration is not None:
+        q.armed, q.bound = True, q.iteration
+
+
+def _bound_to_other_rays(q, n_alive, rays_alive):
+    it = q.bound
+    return it is not None and not (it[0] is rays_alive and it[1] == rays_alive.data_ptr() and it[2] == int(n_alive))
 
 
 def composite_rays_flex(n_alive, n_step, n_channel, rays_alive, rays_t, sigmas, input, deltas, weights_sum, output, T_thresh=1e-2):
     """raymarching/raymarching.py:425-447 (in place on `output`; returns an empty tuple)."""
-    if (_flex_queues.q.on or _flex_queues.q.armed) and not torch.is_autocast_enabled() and sigmas.dtype == torch.float32 and input.dtype == torch.float32:
-        _flex_queues.q.push(n_alive, n_step, n_channel, rays_alive, rays_t, sigmas, input, deltas, weights_sum, output, T_thresh)
+    q = _flex_queues.q
+    if q.armed and not q.on and _bound_to_other_rays(q, n_alive, rays_alive):
+        q.flush()           # not the armed iteration's rays: what is queued goes out first, the deferral ends, this call runs now
+    if (q.on or q.armed) and not torch.is_autocast_enabled() and sigmas.dtype == torch.float32 and input.dtype == torch.float32:
+        q.push(n_alive, n_step, n_channel, rays_alive, rays_t, sigmas, input, deltas, weights_sum, output, T_thresh)
         return tuple()
     return _composite_rays_flex_now(n_alive, n_step, n_channel, rays_alive, rays_t, sigmas, input, deltas, weights_sum, output, T_thresh)
 
@@ -489,8 +518,10 @@ spread_ray_to_sample = _spread_ray_to_sample.apply
 def compact_alive(rays_alive, n_alive=None, out=None, count=None):
     """Device-side, order-preserving replacement of `rays_alive[rays_alive >= 0]`
     (nerf/renderer.py:376).  Returns (compacted ids buffer, device int32[1] count); no host sync."""
-    if _flex_queues.q.shared is not None or _flex_queues.q.armed:
-        _flex_queues.q.flush()
+    q = _flex_queues.q
+    if q.shared is not None or q.armed:
+        q.flush()
+    q.iteration = None
     n = rays_alive.shape[0] if n_alive is None else n_alive
     if out is None:
         out = torch.empty_like(rays_alive)

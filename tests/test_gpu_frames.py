@@ -1167,3 +1167,207 @@ def test_prepare_launch_finish_frames_equal_frames_rendered_one_by_one(cuda, kin
     assert int(r["rendered"].sum()) == want[1]["rendered"] and torch.equal(torch.nan_to_num(r["image"]), torch.nan_to_num(want[1]["image"]))
     got = render_queue(m, lambda i: rays[i], 3, **kw)
     assert all(torch.equal(torch.nan_to_num(g["image"]), torch.nan_to_num(w["image"])) for g, w in zip(got, want))
+
+
+def _queue_model(kind, cuda, seed=0, density_scale=40.0, overflow=False):
+    """A NeRF / PaletteNeRF mirror on the brick scene for the prepare / launch / finish tests.  overflow: the weight recipe of
+    test_split_fp16_field_when_activations_can_leave_the_fp16_range at row_scale 4e4 (seed 11): one hidden activation of the view-dependent head really
+    leaves fp16's range while every weight stays inside it."""
+    if kind == "nerf":
+        m = network.NeRFNetwork(bound=2, cuda_ray=True, density_scale=density_scale, min_near=0.2)
+    else:
+        m = network.PaletteNetwork(renderer.default_opt(), bound=2, cuda_ray=True, density_scale=density_scale, min_near=0.2)
+    scene.seed_field_(m, seed)
+    if overflow:
+        row_scale = 4.0e4
+        with torch.no_grad():
+            m.sigma_net[1].weight[1:].mul_(64.0)
+            m.color_net[0].weight[:, 16:].mul_(1.0 / 64.0)
+            if kind == "palette":
+                m.diff_net[0].weight.mul_(1.0 / 64.0)
+            m.color_net[0].weight[5, 16:].mul_(64.0)
+            m.color_net[0].weight[5].mul_(row_scale)
+            m.color_net[1].weight[:, 5].mul_(1.0 / row_scale)
+    m = m.to(cuda).eval()
+    m.density_grid.copy_(torch.from_numpy(scene.brick_density_grid()).to(cuda))
+    raymarching.packbits(m.density_grid, 0.5, m.density_bitfield)
+    m.march_mode, m.fused_field, m.count_rendered = "native", True, True
+    return m
+
+
+def _queue_rays(cuda, H, W, n, far_apart, first=None):
+    """n poses around the object; far_apart: poses 2 and 3 look past it (few iterations), so that the frame behind them needs more iterations than its submit
+    call enqueues (the finish call then enqueues the rest: host_looks > 1).  first: another pose for frame 0."""
+    intr = scene.intrinsics_from_fov(H, W)
+    rays = []
+    for i in range(n):
+        if i == 0 and first is not None:
+            pose = first
+        elif far_apart and i in (2, 3):
+            pose = scene.lookat_pose_from((3.0, 1.0, 0.5), target=(6.0, 2.5, 0.5))
+        else:
+            pose = scene.lookat_pose(azimuth_deg=20.0 + 61.0 * i, elevation_deg=25.0)
+        ro, rd = scene.get_rays(torch.from_numpy(pose)[None], intr, H, W)
+        rays.append((ro.to(cuda), rd.to(cuda)))
+    return rays
+
+
+def _queue_kw(kind):
+    kw = dict(perturb=False, dt_gamma=0, max_steps=1024, T_thresh=1e-4)
+    if kind == "palette":
+        kw["gui_mode"] = False
+    return kw
+
+
+def _same_frame(got, want, what):
+    assert int(got["rendered"].sum()) == int(want["rendered"].sum()), what
+    for k in ("image", "depth", "weights_sum"):
+        a, b = got[k].cpu().numpy(), want[k].cpu().numpy()
+        np.testing.assert_array_equal(np.isnan(a), np.isnan(b), err_msg=f"{what} {k}")
+        np.testing.assert_array_equal(np.nan_to_num(a), np.nan_to_num(b), err_msg=f"{what} {k}")
+
+
+def _kept(r):
+    return {k: (r[k].clone() if torch.is_tensor(r[k]) else r[k]) for k in ("image", "depth", "weights_sum", "rendered", "host_looks")}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["nerf", "palette"])
+def test_queue_frame_after_an_fp16_overflow_is_rendered_from_a_valid_blob(cuda, kind):
+    """render_queue when a frame reports an fp16 overflow: render_result renders that frame again on the exact fp32 path (repacking the fp32 blob) while the
+    NEXT frame is already prepared with split-fp16 + watch.  That frame must not run against the fp32 blob: the overflow latch makes frame_launch refuse it
+    (StaleFrame) and render_launch prepares it again on fp32.  Every frame then equals, bit for bit, what a fresh object at precision 0 renders one by one;
+    the overflow is reported once.  (PaletteNeRF packs every blob into a new tensor; the case proves that path stays right too.)"""
+    import warnings
+    from palettenerf_amd.fused import NeRFFieldFused, PaletteFieldFused
+    from palettenerf_amd.pipeline import render_queue
+    cls = NeRFFieldFused if kind == "nerf" else PaletteFieldFused
+    m = _queue_model(kind, cuda, seed=11, density_scale=100.0, overflow=True)
+    rays = _queue_rays(cuda, 48, 48, 5, far_apart=False, first=scene.lookat_pose(elevation_deg=30.0, azimuth_deg=45.0))   # (frame 0: the pose that overflows there)
+    kw = _queue_kw(kind)
+    exact = cls(m)
+    exact.precision = 0
+    m._fused = exact
+    with torch.no_grad(), warnings.catch_warnings():
+        warnings.simplefilter("error")
+        want = [_kept(m.render(ro, rd, **kw)) for ro, rd in rays]
+    assert all(int(w["rendered"].sum()) > 100 for w in want)
+    queued = cls(m)
+    m._fused = queued
+    assert queued.effective_precision() == 0 and queued.frame_precision() == (1, True)
+    launches = []
+    launch = queued.frame_launch
+
+    def counted(tok):
+        launches.append(tok.gen == queued.__dict__.get("_gen", 0))      # False: a frame prepared before the blobs / the precision changed
+        return launch(tok)
+    queued.frame_launch = counted
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        got = render_queue(m, lambda i: rays[i], len(rays), **kw)
+    overflows = [w for w in caught if "fp16's range" in str(w.message)]
+    assert len(overflows) == 1, [str(w.message) for w in caught]
+    assert queued.frame_precision() == (0, False)
+    assert len(launches) == len(rays) + 1 and launches.count(False) == 1 and launches[1] is False   # frame 1 was prepared a second time
+    for i, (g, w) in enumerate(zip(got, want)):
+        _same_frame(g, w, f"frame {i}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["nerf", "palette"])
+def test_stand_alone_call_between_launch_and_finish_leaves_the_frame_intact(cuda, kind):
+    """render_queue's consume() runs between frame i + 1's launch and its finish.  A stand-alone field call there (`m._fused(x, d)`, on the exact fp32 path
+    because the static bound fails) must not touch the blob the frame in flight reads -- its finish call still enqueues chunks (host_looks > 1) -- and a
+    16 MB NaN fill right behind it must not reach anything the frame reads.  Frames equal the frames rendered one by one, the stand-alone results the exact
+    fp32 results."""
+    from palettenerf_amd.fused import NeRFFieldFused, PaletteFieldFused
+    from palettenerf_amd.pipeline import render_queue
+    cls = NeRFFieldFused if kind == "nerf" else PaletteFieldFused
+
+    def pessimistic(obj):
+        obj._guard_bound = lambda tmax, scales: 1.0e9
+        return obj
+
+    m = _queue_model(kind, cuda)
+    m._fused = pessimistic(cls(m))
+    assert m._fused.effective_precision() == 0 and m._fused.frame_precision() == (1, True)
+    rays = _queue_rays(cuda, 96, 128, 6, far_apart=True)
+    kw = _queue_kw(kind)
+    with torch.no_grad():
+        want = [_kept(m.render(ro, rd, **kw)) for ro, rd in rays]
+    g = torch.Generator().manual_seed(4)
+    x = ((torch.rand(4096, 3, generator=g) * 2 - 1) * 1.5).to(cuda)
+    d = torch.nn.functional.normalize(torch.randn(4096, 3, generator=g), dim=-1).to(cuda)
+    exact = cls(m)
+    exact.precision = 0
+    alone_want = [t.clone() for t in exact(x, d)]
+    alone = []
+
+    def consume(i, r):
+        alone.append([t.clone() for t in m._fused(x, d)])
+        torch.empty(1 << 22, device=cuda).fill_(float("nan"))
+        return _kept(r)
+    got = render_queue(m, lambda i: rays[i], len(rays), consume=consume, **kw)
+    assert max(int(r["host_looks"]) for r in got) > 1
+    for i, (r, w) in enumerate(zip(got, want)):
+        _same_frame(r, w, f"frame {i}")
+    assert len(alone) == len(rays)
+    for out in alone:
+        for a, b in zip(out, alone_want):
+            assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["nerf", "palette"])
+def test_finish_keeps_the_submit_stream_and_options(cuda, kind):
+    """pnr_*_render_frame_finish continues exactly the frame _submit started: a finish on another stream is refused (-1) before it enqueues anything and the
+    frame stays submitted -- the finish on its own stream then completes it; a pnr_set_option between the two halves does not reach the frame's remaining
+    chunks: the frame equals the whole frame rendered under the submit-time value."""
+    import ctypes
+    from palettenerf_amd import _lib
+    from palettenerf_amd.fused import NeRFFieldFused, PaletteFieldFused
+    lib = _lib.load()
+    m = _queue_model(kind, cuda)
+    f = m._fused = NeRFFieldFused(m) if kind == "nerf" else PaletteFieldFused(m)
+    rays = _queue_rays(cuda, 96, 128, 3, far_apart=True)
+    (ro_long, rd_long), (ro_short, rd_short) = (rays[0][0][0], rays[0][1][0]), (rays[2][0][0], rays[2][1][0])
+    fin = lib.pnr_nerf_render_frame_finish if kind == "nerf" else lib.pnr_palette_render_frame_finish
+    arg = (lambda t: ctypes.byref(t.a)) if kind == "nerf" else (lambda t: ctypes.byref(t.p))
+    args = lambda ro, rd: (ro, rd, None, None, 0.0, 1024, 1e-4)
+    kw = dict(bg_color=1, aabb=m.aabb_infer, min_near=m.min_near)
+
+    def whole():
+        return [t.clone() if torch.is_tensor(t) else t for t in f.render_frame(*args(ro_long, rd_long), **kw)]
+
+    def split(between=None, other_stream=False):
+        f.render_frame(*args(ro_short, rd_short), **kw)        # this thread's prediction: a few iterations -> the long frame's submit call falls short
+        tok = f.frame_prepare(*args(ro_long, rd_long), **kw)
+        f.frame_launch(tok)
+        if between is not None:
+            between()
+        if other_stream:
+            assert fin(arg(tok), torch.cuda.Stream().cuda_stream) == -1
+        out = f.frame_finish(tok)
+        assert out[-1]["looks"] > 1
+        return out
+
+    def equal(a, b, what):
+        assert a[-1]["rendered"] == b[-1]["rendered"] > 1000, what
+        for x, y in zip(a[:-1], b[:-1]):
+            if torch.is_tensor(x):
+                assert torch.equal(torch.nan_to_num(x, nan=-7.0), torch.nan_to_num(y, nan=-7.0)), what
+
+    with torch.no_grad():
+        equal(split(other_stream=True), whole(), "finish on another stream refused, then on its own")
+        options = [b"hosted_tail", b"composite_fusion"] + ([b"aux_fusion"] if kind == "palette" else [])
+        on_value = {b"hosted_tail": 1, b"composite_fusion": 2, b"aux_fusion": 1}
+        try:
+            for name in options:
+                for submit_value, flipped in ((on_value[name], 0), (0, on_value[name])):
+                    assert lib.pnr_set_option(name, submit_value) == 0
+                    want = whole()
+                    got = split(between=lambda: lib.pnr_set_option(name, flipped))
+                    assert lib.pnr_set_option(name, submit_value) == 0
+                    equal(got, want, (name, submit_value))
+        finally:
+            lib.pnr_set_option(b"hosted_tail", 1); lib.pnr_set_option(b"composite_fusion", 2); lib.pnr_set_option(b"aux_fusion", 1)

@@ -1910,3 +1910,99 @@ def test_fused_mlp_tile_moves_on_odd_widths_and_ragged_ends(cuda, dims, B, sig, 
         y = torch.empty(B, dims[-1], device=cuda)
         rc = lib.pnr_mlp_forward(ctypes.byref(desc), packed.data_ptr(), x_view.data_ptr(), B, y.data_ptr(), None)
         assert rc == -4 and b"16-byte" in lib.pnr_error_string(rc)      # PNR_ERR_ALIGNMENT: the error says what is wrong
+
+
+def test_fuse_field_palette_forward_follows_data_writes_to_the_tables(cuda):
+    """dropin.fuse_field on a PaletteNetwork: torch_ema's copy_to / restore write the hash tables through `.data` (neither the version counter nor the storage
+    moves).  The fused forward must read the tables as they are now -- within the tolerances of test_fused_palette_field_matches_torch_module against the
+    module's own torch forward -- by default, and with the opt-in interleaved pair lookup after invalidate_fused_caches()."""
+    from palettenerf_amd import dropin, network, renderer
+    from palettenerf_amd.fused import invalidate_fused_caches
+    rng = np.random.default_rng(63)
+    m = network.PaletteNetwork(renderer.default_opt(), bound=2, cuda_ray=True, density_scale=3.0)
+    scene.seed_field_(m, 5)
+    m = m.to(cuda).eval()
+    dropin.fuse_field(m)
+    B = 4097
+    x = dev(rng.random((B, 3)).astype(np.float32) * 4 - 2, cuda)
+    d = rng.standard_normal((B, 3)).astype(np.float32)
+    d = dev(d / np.linalg.norm(d, axis=1, keepdims=True), cuda)
+
+    def agree(got, what):
+        with torch.no_grad():
+            want = network.PaletteNetwork.forward(m, x, d)          # the module's own torch forward
+        np.testing.assert_allclose(host(got[0]), host(want[0]), rtol=3e-5, atol=1e-7, err_msg=what)
+        for g_, w_ in zip(got[1:], want[1:]):
+            np.testing.assert_allclose(host(g_), host(w_), rtol=0, atol=5e-6, err_msg=what)
+
+    with torch.no_grad():
+        before = [t.clone() for t in m(x, d)]
+    agree(before, "before the writes")
+    keys = [(t._version, t.data_ptr()) for t in (m.encoder.embeddings, m.encoder_palette.embeddings)]
+    other = (torch.rand(m.encoder.embeddings.shape, generator=torch.Generator().manual_seed(8)) * 2 - 1).to(cuda)
+    m.encoder.embeddings.data.copy_(other)
+    m.encoder_palette.embeddings.data.mul_(-1)
+    assert [(t._version, t.data_ptr()) for t in (m.encoder.embeddings, m.encoder_palette.embeddings)] == keys    # invisible to torch's counters
+    with torch.no_grad():
+        after = m(x, d)
+    assert not torch.equal(after[0], before[0]) and not torch.equal(after[2], before[2])
+    agree(after, "after the .data writes")
+    m._fused.stand_alone_pair = True                                # the opt-in: the interleaved copy, which needs the explicit invalidation
+    invalidate_fused_caches(m)
+    with torch.no_grad():
+        agree(m(x, d), "pair lookup after invalidate_fused_caches")
+    m.encoder_palette.embeddings.data.mul_(-1)
+    invalidate_fused_caches(m)
+    with torch.no_grad():
+        agree(m(x, d), "pair lookup, tables written back")
+
+
+def test_flex_composite_after_a_fused_forward_outside_a_march_loop_is_written_on_return(cuda):
+    """dropin.fuse_field arms the flex deferral behind every fused PaletteNetwork.forward under no_grad.  Outside run_cuda's loop (a point query, an export
+    script) no march iteration is open: a direct composite_rays_flex that follows must have written its `output` when it returns -- as the same call with the
+    deferral off.  The reference-style loop still reaches the device with one multi-map launch per iteration and no single flex launch."""
+    from palettenerf_amd import _torch_glue, dropin, network, renderer
+    rng = np.random.default_rng(92)
+    m = network.PaletteNetwork(renderer.default_opt(), bound=2, cuda_ray=True, density_scale=3.0, min_near=0.2)
+    scene.seed_field_(m, 5)
+    m = m.to(cuda).eval()
+    dropin.fuse_field(m)
+    x = dev(rng.random((512, 3)).astype(np.float32) * 2 - 1, cuda)
+    d = torch.nn.functional.normalize(dev(rng.standard_normal((512, 3)).astype(np.float32), cuda), dim=-1)
+    N, n_alive, n_step = 3000, 1700, 4
+    alive = dev(np.sort(rng.choice(N, n_alive, replace=False)).astype(np.int32), cuda)
+    M = n_alive * n_step
+    sig, inp = dev((rng.random(M) * 60).astype(np.float32), cuda), dev(rng.standard_normal((M, 3)).astype(np.float32), cuda)
+    dl = dev(np.stack([rng.random(M) * 0.02 + 0.003, rng.random(M) * 0.05 + 0.003], 1).astype(np.float32), cuda)
+    t, ws = torch.rand(N, device=cuda), torch.rand(N, device=cuda) * 0.7
+    try:
+        with torch.no_grad():
+            m(x, d)                                                 # a fused forward outside any march loop
+        out = torch.zeros(N, 3, device=cuda)
+        raymarching.composite_rays_flex(n_alive, n_step, 3, alive, t, sig, inp, dl, ws, out, 1e-4)
+        got = out.clone()                                           # what the caller reads right on return
+    finally:
+        raymarching.flush_flex_composites()
+    was = raymarching.defer_flex_composites(False)
+    try:
+        want = torch.zeros(N, 3, device=cuda)
+        raymarching.composite_rays_flex(n_alive, n_step, 3, alive, t, sig, inp, dl, ws, want, 1e-4)
+    finally:
+        raymarching.defer_flex_composites(was)
+    assert float(want.abs().sum()) > 0.0
+    assert torch.equal(got, want)
+    # the reference-style loop (the mirror's per-op loop with its seven flex composites per iteration)
+    m.density_grid.copy_(torch.from_numpy(scene.brick_density_grid()).to(cuda))
+    raymarching.packbits(m.density_grid, 0.5, m.density_bitfield)
+    m.march_mode = "compat"
+    ro, rd = rays_of(32, 32)
+    prof = _torch_glue.profile_kernels(["pnr_composite_rays", "pnr_composite_rays_flex", "pnr_composite_rays_flex_multi"])
+    try:
+        with torch.no_grad():
+            r = m.render(dev(ro, cuda)[None], dev(rd, cuda)[None], dt_gamma=0.0, perturb=False, max_steps=1024, T_thresh=1e-4, gui_mode=False)
+        torch.cuda.synchronize()
+        n_comp, n_flex, n_multi = (len(prof[k]) for k in ("pnr_composite_rays", "pnr_composite_rays_flex", "pnr_composite_rays_flex_multi"))
+    finally:
+        _torch_glue.profile_kernels(None)
+    assert float(r["weights_sum"].sum()) > 0.0
+    assert n_comp > 1 and n_flex == 0 and n_multi == n_comp
