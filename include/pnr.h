@@ -346,7 +346,8 @@ typedef struct pnr_nerf_frame_args {
     float bg_color[3];             /* used when finish != 0 and bg_map == NULL (the reference's default is 1) */
     const float* bg_map;           /* optional per-ray background [N,3] (device) for finish */
     int table_dtype;               /* PNR_DTYPE_F32 (default) or PNR_DTYPE_F16: the reference's --fp16 tables (`embeddings` then points to halves;
-                                      PaletteNeRF: embeddings_pair = both tables as interleaved halves, required, no clip head).  The lookup
+                                      PaletteNeRF: embeddings_pair = both tables as interleaved halves, required without a clip head; with a
+                                      clip head embeddings_triple = the three tables as pnr_interleave_tables3_half rows, required).  The lookup
                                       then reproduces the reference's half interpolation (as pnr_grid_encode_forward with dtype 1) */
     float enc_scale[3];            /* power-of-two prescale of the features of `embeddings` (PaletteNeRF: + embeddings_palette, embeddings_clip) in the
                                       split-fp16 field, see pnr_nerf_field_forward; 0 or 1 = none */
@@ -414,13 +415,19 @@ typedef struct pnr_palette_frame_args {
                                           pnr_interleave_tables; rebuild when either table changes).  Used when pred_clip == 0: one 16-byte
                                           gather serves both tables, results bit-identical to the separate lookups */
     const float* embeddings_triple;    /* optional, pred_clip != 0: all three tables interleaved ([rows][8] floats: encoder, encoder_palette,
-                                          encoder_clip, 2 pad; pnr_interleave_tables3): one 32-byte row per corner, bit-identical results */
+                                          encoder_clip, 2 pad; pnr_interleave_tables3): one 32-byte row per corner, bit-identical results.
+                                          With base.table_dtype == PNR_DTYPE_F16 (required then): [rows][8] HALVES instead, built by
+                                          pnr_interleave_tables3_half -- one 16-byte row per corner */
     const pnr_palette_edit* edit;      /* HOST, optional: RegionEdit / Stylizer applied to every sample (NULL or mode 0: none) */
 } pnr_palette_frame_args;
 /* out[i] = (a[i].x, a[i].y, b[i].x, b[i].y) for two C = 2 fp32 tables of `rows` rows with the same level layout */
 int pnr_interleave_tables(const float* a, const float* b, uint64_t rows, float* out, pnr_stream_t stream);
 /* a, b, c: [rows][2] fp32 -> out [rows][8] = (a.x, a.y, b.x, b.y, c.x, c.y, 0, 0): the --pred_clip model's three lookups from one 32-byte row */
 int pnr_interleave_tables3(const float* a, const float* b, const float* c, uint64_t rows, float* out, pnr_stream_t stream);
+/* (ABI 8) a, b, c: [rows][2] fp32 -> out [rows][8] fp16 = (a.x, a.y, b.x, b.y, c.x, c.y, 0, 0), each value rounded to nearest even (the bits of
+ * tensor.to(torch.float16): beyond fp16's range -> inf): the --pred_clip model's three fp16 lookups from one 16-byte row (embeddings_triple with
+ * table_dtype PNR_DTYPE_F16) */
+int pnr_interleave_tables3_half(const float* a, const float* b, const float* c, uint64_t rows, void* out, pnr_stream_t stream);
 uint64_t pnr_palette_frame_workspace_bytes(uint32_t N, uint32_t num_basis, uint32_t clip_dim, int pred_clip);
 int pnr_palette_render_frame(const pnr_palette_frame_args* args, pnr_stream_t stream);
 int pnr_palette_render_frame_submit(const pnr_palette_frame_args* args, pnr_stream_t stream);   /* as pnr_nerf_render_frame_submit / _finish */

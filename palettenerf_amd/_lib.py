@@ -85,6 +85,7 @@ SIGNATURES = {
     "pnr_palette_field_stages_aux": [_u32, _u32, _int],
     "pnr_interleave_tables": [_ptr, _ptr, _u64, _ptr, _ptr],
     "pnr_interleave_tables3": [_ptr, _ptr, _ptr, _u64, _ptr, _ptr],
+    "pnr_interleave_tables3_half": [_ptr, _ptr, _ptr, _u64, _ptr, _ptr],
     "pnr_palette_train_shade_workspace_bytes": [_u32],
     "pnr_palette_train_shade_forward": [_u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
     "pnr_palette_train_shade_backward": [_u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u64, _ptr],

@@ -525,8 +525,10 @@ __global__ void __launch_bounds__(kRayBlock) __attribute__((amdgpu_waves_per_eu(
 //              row by row, a row = NT x half2.  Interpolation with the reference's half accumulator -- every addend and every partial sum
 //              rounded to fp16 (gridencoder.cu:142,165 with scalar_t = at::Half) -- so the encoder output equals k_grid_fwd<__half>'s bit for
 //              bit; it is handed to the field kernel as fp32 (exact).
+//   GK_HALF3   --pred_clip with fp16 tables: the three tables as halves, one 16-byte row per index (enc.x, enc.y, pal.x, pal.y, clip.x, clip.y, 0, 0;
+//              pnr_interleave_tables3_half): one gather per corner, the register budget of GK_PAIR, GK_HALF1/2's half accumulator per channel
 // ------------------------------------------------------------------------------------------
-enum GridKind { GK_SINGLE = 0, GK_PAIR = 1, GK_TRIPLE = 2, GK_HALF1 = 3, GK_HALF2 = 4 };
+enum GridKind { GK_SINGLE = 0, GK_PAIR = 1, GK_TRIPLE = 2, GK_HALF1 = 3, GK_HALF2 = 4, GK_HALF3 = 5 };
 struct GridArgs {
     const float* xyzs; const float* deltas;
     const void* table[3]; float* enc[3];
@@ -659,8 +661,9 @@ __device__ __forceinline__ void grid_row(const GridArgs& g, const LevelCtx& lc, 
         *reinterpret_cast<float2*>(g.enc[1] + o) = make_float2(out.z, out.w);
         *reinterpret_cast<float2*>(g.enc[2] + o) = outc;
     } else {
-        constexpr int NT = KIND == GK_HALF2 ? 2 : 1;
-        typedef uint32_t RowT __attribute__((ext_vector_type(NT)));   // NT x half2
+        constexpr int NT = KIND == GK_HALF3 ? 3 : (KIND == GK_HALF2 ? 2 : 1);
+        constexpr int NW = NT == 3 ? 4 : NT;   // (GK_HALF3: 3 x half2 + one pad word = 16 bytes)
+        typedef uint32_t RowT __attribute__((ext_vector_type(NW)));   // NT x half2
         __half acc[2 * NT];
 #pragma unroll
         for (int ch = 0; ch < 2 * NT; ch++) acc[ch] = __float2half(0.0f);
@@ -671,14 +674,15 @@ __device__ __forceinline__ void grid_row(const GridArgs& g, const LevelCtx& lc, 
 #pragma unroll
             for (uint32_t idx = 0; idx < 8; idx++) {
                 __half hv[2 * NT];
-                __builtin_memcpy(hv, &v[idx], sizeof(RowT));
+                __builtin_memcpy(hv, &v[idx], sizeof(hv));
 #pragma unroll
                 for (int ch = 0; ch < 2 * NT; ch++)   // the reference's half accumulator: addend and sum rounded to fp16 (corner_accumulate<__half>)
                     acc[ch] = __float2half(__half2float(acc[ch]) + __half2float(__float2half(ws[idx] * __half2float(hv[ch]))));
             }
         }
         *reinterpret_cast<float2*>(enc0 + o) = make_float2(__half2float(acc[0]), __half2float(acc[1]));
-        if constexpr (NT == 2) *reinterpret_cast<float2*>(g.enc[1] + o) = make_float2(__half2float(acc[2]), __half2float(acc[3]));
+        if constexpr (NT >= 2) *reinterpret_cast<float2*>(g.enc[1] + o) = make_float2(__half2float(acc[2]), __half2float(acc[3]));
+        if constexpr (NT == 3) *reinterpret_cast<float2*>(g.enc[2] + o) = make_float2(__half2float(acc[4]), __half2float(acc[5]));
     }
 }
 
@@ -739,7 +743,7 @@ __device__ __forceinline__ void hosted_march_tail(const FrameCtl* ctl, const Gri
     }
     __syncthreads();
     const uint32_t n_step = (uint32_t)ctl->n_step;
-    const uint32_t n_tab = KIND == GK_SINGLE ? ha.n_tab : 1u;
+    const uint32_t n_tab = KIND == GK_SINGLE ? ha.n_tab : 1u;   // (the interleaved kinds -- pair, triple, h2, h3 -- write every table's output from one row)
     uint32_t emitted = 0;
     for (uint32_t task = blockIdx.x * kWavesPerBlock + (uint32_t)wave; task < ntasks; task += h.blocks * kWavesPerBlock) {
         const uint32_t qi = (task << glog) + (uint32_t)lane;
@@ -879,6 +883,7 @@ PNR_GRID_KERNEL(k_frame_grid_pair, GK_PAIR, PNR_GRID_WAVES)
 PNR_GRID_KERNEL(k_frame_grid_triple, GK_TRIPLE, PNR_GRID_WAVES)
 PNR_GRID_KERNEL(k_frame_grid_h1, GK_HALF1, PNR_GRID_WAVES)
 PNR_GRID_KERNEL(k_frame_grid_h2, GK_HALF2, PNR_GRID_WAVES)
+PNR_GRID_KERNEL(k_frame_grid_h3, GK_HALF3, PNR_GRID_WAVES)
 #undef PNR_GRID_KERNEL
 
 __global__ void __launch_bounds__(256) k_interleave_tables(const float2* __restrict__ a, const float2* __restrict__ b, uint64_t rows,
@@ -893,6 +898,19 @@ __global__ void __launch_bounds__(256) k_interleave_tables3(const float2* __rest
         const float2 u = a[i], v = b[i], t = c[i];
         out[2 * i] = make_float4(u.x, u.y, v.x, v.y);
         out[2 * i + 1] = make_float4(t.x, t.y, 0.0f, 0.0f);
+    }
+}
+// pnr_interleave_tables3_half: the three tables as halves (__float2half: round to nearest even, what tensor.to(torch.float16) does), 16 bytes per row
+__global__ void __launch_bounds__(256) k_interleave_tables3_half(const float2* __restrict__ a, const float2* __restrict__ b, const float2* __restrict__ c,
+                                                                 uint64_t rows, uint4* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < rows) {
+        const float2 u = a[i], v = b[i], t = c[i];
+        const __half h[8] = {__float2half(u.x), __float2half(u.y), __float2half(v.x), __float2half(v.y), __float2half(t.x), __float2half(t.y),
+                             __float2half(0.0f), __float2half(0.0f)};
+        uint4 row;
+        __builtin_memcpy(&row, h, sizeof(row));
+        out[i] = row;
     }
 }
 
@@ -1201,6 +1219,14 @@ int pnr_interleave_tables3(const float* a, const float* b, const float* c, uint6
     return check_launch();
 }
 
+int pnr_interleave_tables3_half(const float* a, const float* b, const float* c, uint64_t rows, void* out, pnr_stream_t stream) {
+    if (rows == 0) return PNR_OK;
+    if (!a || !b || !c || !out) return PNR_ERR_INVALID;
+    hipLaunchKernelGGL(k_interleave_tables3_half, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, as_stream(stream), reinterpret_cast<const float2*>(a),
+                       reinterpret_cast<const float2*>(b), reinterpret_cast<const float2*>(c), rows, static_cast<uint4*>(out));
+    return check_launch();
+}
+
 uint64_t pnr_nerf_frame_workspace_bytes(uint32_t N) { return carve(nullptr, N).bytes; }
 uint64_t pnr_palette_frame_workspace_bytes(uint32_t N, uint32_t num_basis, uint32_t clip_dim, int pred_clip) {
     return carve(nullptr, N, pnr_palette_aux_channels(num_basis, clip_dim), pred_clip != 0).bytes;
@@ -1307,8 +1333,9 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
     const int aux_fused = (pal && opt.aux_fusion && pnr_palette_field_stages_aux(pal->num_basis, pal->clip_dim, pal->pred_clip)) ? 1 : 0;
     const int composite_fused = (!pal && opt.composite_fusion) ? opt.composite_fusion : 0;   // NeRF: 1 = one-sample-per-ray iterations are composited inside the field kernel, 2 = all of them (no composite launch)
     const bool pal_composite_fused = pal && aux_fused && opt.composite_fusion == 2;   // PaletteNeRF: the ray state is composited inside the field kernel as well (needs the staged aux rows)
-    const bool half_tables = a->table_dtype == PNR_DTYPE_F16;   // fp16 tables: nerf = `embeddings` as halves; palette = embeddings_pair as interleaved halves
-    if (half_tables && pal && (with_clip || !pal->embeddings_pair)) return PNR_ERR_UNSUPPORTED;
+    const bool half_tables = a->table_dtype == PNR_DTYPE_F16;   // fp16 tables: nerf = `embeddings` as halves; palette = embeddings_pair (no clip head) or
+                                                                // embeddings_triple (clip head) as interleaved halves
+    if (half_tables && pal && (with_clip ? !pal->embeddings_triple : !pal->embeddings_pair)) return PNR_ERR_UNSUPPORTED;
     if (a->table_dtype != PNR_DTYPE_F32 && a->table_dtype != PNR_DTYPE_F16) return PNR_ERR_UNSUPPORTED;
     const float4* pair_table = (pal && !half_tables && !with_clip && pal->embeddings_pair) ? reinterpret_cast<const float4*>(pal->embeddings_pair) : nullptr;
     const float4* triple_table = (pal && !half_tables && with_clip && pal->embeddings_triple) ? reinterpret_cast<const float4*>(pal->embeddings_triple) : nullptr;
@@ -1464,7 +1491,10 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
             // kernel took 71.0
             hipEvent_t e0 = timing ? next_event() : nullptr, e1 = timing ? next_event() : nullptr;
 #define PNR_LAUNCH_GRID(KERNEL, GRID) hipExtLaunchKernelGGL(KERNEL, (ha.blocks ? dim3(ha.blocks + (GRID).x * (GRID).y * (GRID).z) : (GRID)), dim3(256), grid_lds, s, e0, e1, 0, cur, ga, ha)
-            if (half_tables && pal) {
+            if (half_tables && pal && with_clip) {
+                ga.table[0] = pal->embeddings_triple;
+                PNR_LAUNCH_GRID(k_frame_grid_h3, dim3(gxc, 16));
+            } else if (half_tables && pal) {
                 ga.table[0] = pal->embeddings_pair;
                 PNR_LAUNCH_GRID(k_frame_grid_h2, dim3(gxc, 16));
             } else if (half_tables) {
@@ -1548,7 +1578,7 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
             if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) total += ms;
         }
         a->kernel_ms[0] = total;
-        a->kernel_ms[1] = (float)counted * ((pair_table || triple_table || half_tables) ? 1.0f : (float)n_enc);  // a k_frame_grid launch covers n_enc tables (count table-launches); the pair kernel is one launch for both
+        a->kernel_ms[1] = (float)counted * ((pair_table || triple_table || half_tables) ? 1.0f : (float)n_enc);  // a k_frame_grid launch covers n_enc tables (count table-launches); the interleaved kinds (pair, triple, h2, h3) are one launch for all
     }
     if (a->stats) {
         a->stats[0] = (uint64_t)host_ctl->iterations;

@@ -732,7 +732,7 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
         # interleaved copy instead (one 16-byte gather for both lookups) -- a cache keyed on torch's version counters with no checksum on this path, so
         # after a write through `.data` (torch_ema's copy_to / restore) invalidate_fused_caches(model) is REQUIRED, or the call reads the old tables
         self.stand_alone_pair = False
-        self.table_half = False         # native loop: fp16 tables with the reference's half interpolation (its --fp16 mode; no clip head)
+        self.table_half = False         # native loop: fp16 tables with the reference's half interpolation (its --fp16 mode; the clip head reads the half triple)
         self.aux_channels = int(_lib.load().pnr_palette_aux_channels(self.nb, self.clip_dim))
 
     def _weights(self):
@@ -750,7 +750,7 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
 
     def invalidate_caches(self):
         self.versions = None
-        self._pair_key = self._triple_key = self._guard_key = None
+        self._pair_key = self._triple_key = self._triple_half_key = self._guard_key = None
         self._watch_ref = None       # the next frame rebuilds every blob: its source checksums become the reference
         self._guard_held = self._weights_held = None   # (a held call that retries asks again)
         self._frame_plan = None      # the frame call's kept argument struct points into the blobs
@@ -873,17 +873,21 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
     @torch.no_grad()
     def _triple_table(self):
         """--pred_clip: the three tables interleaved row by row ([rows, 8] fp32 = encoder, encoder_palette, encoder_clip, 2 pad): one 32-byte
-        row per corner serves all three lookups.  Rebuilt when any table changes."""
+        row per corner serves all three lookups.  table_half: [rows, 8] fp16 instead (pnr_interleave_tables3_half, one 16-byte row).  Rebuilt
+        when any table changes; the fp32 and half copies are cached apart (a new tensor per rebuild: a frame in flight keeps the one it was given)."""
         m = self.model
-        key = tuple(_pkey(e.embeddings) for e in (m.encoder, m.encoder_palette, m.encoder_clip))
+        half = bool(self.table_half)
+        key = tuple(_pkey(e.embeddings) for e in (m.encoder, m.encoder_palette, m.encoder_clip)) + (half,)
         ts = [e.embeddings.detach() for e in (m.encoder, m.encoder_palette, m.encoder_clip)]
         if any(t.dtype != torch.float32 or t.shape != ts[0].shape or t.shape[1] != 2 for t in ts):
             return None
-        if getattr(self, "_triple_key", None) != key or PARANOID:
-            out = torch.empty(ts[0].shape[0], 8, dtype=torch.float32, device=ts[0].device)
-            call("pnr_interleave_tables3", *[ptr(t.contiguous()) for t in ts], ctypes.c_uint64(ts[0].shape[0]), ptr(out))
-            self._triple, self._triple_key = out, key
-        return self._triple
+        name = "_triple_half" if half else "_triple"
+        if getattr(self, name + "_key", None) != key or PARANOID:
+            out = torch.empty(ts[0].shape[0], 8, dtype=torch.float16 if half else torch.float32, device=ts[0].device)
+            call("pnr_interleave_tables3_half" if half else "pnr_interleave_tables3", *[ptr(t.contiguous()) for t in ts], ctypes.c_uint64(ts[0].shape[0]), ptr(out))
+            setattr(self, name, out)
+            setattr(self, name + "_key", key)
+        return getattr(self, name)
 
     def render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0):
         """One PaletteNeRF inference frame through the device-driven loop (pnr_palette_render_frame).
@@ -976,11 +980,9 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
             p.embeddings_clip = require(m.encoder_clip.embeddings.detach(), torch.float32, "embeddings").data_ptr() if self.pred_clip else None
             p.num_basis, p.clip_dim, p.pred_clip = self.nb, self.clip_dim, int(self.pred_clip)
             p.offsets_weight, p.view_dep_weight = float(m.offsets_weight), float(m.view_dep_weight)
-            if self.table_half and self.pred_clip:
-                raise RuntimeError("fp16 tables in the native PaletteNeRF loop need the interleaved pair table (no clip head)")
             pair = self._pair_table() if ((self.interleave_tables or self.table_half) and not self.pred_clip) else None
             p.embeddings_pair = pair.data_ptr() if pair is not None else None
-            triple = self._triple_table() if (self.interleave_tables and self.pred_clip and not self.table_half) else None
+            triple = self._triple_table() if ((self.interleave_tables or self.table_half) and self.pred_clip) else None
             p.embeddings_triple = triple.data_ptr() if triple is not None else None
             a.table_dtype = 1 if self.table_half else 0
             plan = plans[slot] = (plan_key, p, prec, watch, (self._ws, order, pair, triple))     # (the tensors whose addresses the struct holds)

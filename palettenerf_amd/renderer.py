@@ -731,8 +731,8 @@ class PaletteRenderer(_RendererBase):
         device = rays_o.device
         nb, clip_dim = self.num_basis, self.opt.clip_dim
         aabb = self.aabb_train if self.training else self.aabb_infer
-        # under fp16 autocast only the native loop takes the fused path (fp16 tables, fp32-accurate field); it has no clip-head variant there
-        autocast_ok = not torch.is_autocast_enabled() or (self.march_mode == "native" and not perturb and not self.opt.pred_clip)
+        # under fp16 autocast only the native loop takes the fused path (fp16 tables, fp32-accurate field; with the clip head: the half triple)
+        autocast_ok = not torch.is_autocast_enabled() or (self.march_mode == "native" and not perturb)
         # RegionEdit and the Stylizer run inside the fused field kernel's epilogue (pnr_palette_edit): editing costs no extra launch
         use_fused = not self.training and bool(getattr(self, "fused_field", False)) and autocast_ok
         native = use_fused and self.march_mode == "native" and not perturb
