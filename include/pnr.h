@@ -303,7 +303,8 @@ int pnr_nerf_density_forward(const float* enc, const float* packed, uint32_t B, 
  * same per-ray arithmetic, order-preserving compaction) with n_alive / n_step / step kept in a device control
  * block, so the host does not synchronise per iteration.  Outputs are the raw accumulations (weights_sum [N],
  * depth [N], image [N,3]) BEFORE the background mix / depth normalisation of nerf/renderer.py:382-383.
- * perturb is False (inference).  workspace: pnr_nerf_frame_workspace_bytes(N) bytes of device memory. */
+ * perturb (ABI 9): `noises` NULL is the unjittered frame; with `noises` the first sample of every ray is jittered as the reference's march
+ * does with perturb set (raymarching.cu:927,945), in the frame's first iteration only (the loops pass `perturb if step == 0 else False`).  workspace: pnr_nerf_frame_workspace_bytes(N) bytes of device memory. */
 typedef struct pnr_nerf_frame_args {
     uint32_t N;
     const float* rays_o;           /* [N,3] */
@@ -359,6 +360,11 @@ typedef struct pnr_nerf_frame_args {
     float min_near;                /* used with `aabb` */
     float* depth_raw;              /* optional [N] out: the un-normalised depth by ray id when finish bit 1 rewrites `depth`
                                       (PaletteNeRF's depth_origin, palette/renderer.py:522) */
+    const float* noises;           /* (ABI 9) optional [N] (device), indexed by RAY ID whatever `ray_order` says: the uniform [0, 1) draw per ray of
+                                      march_rays(perturb=True) (raymarching/raymarching.py:388-392).  The frame's first march starts ray r at
+                                      t = fmaf(clamp(near * dt_gamma, dt_min, dt_max), noises[r], near); later iterations are not jittered.  NULL: no jitter
+                                      (the frame as it was before ABI 9, bit for bit; an all-zero array gives the same bits).  Read between _submit
+                                      and _finish like every other input */
 } pnr_nerf_frame_args;
 uint64_t pnr_nerf_frame_workspace_bytes(uint32_t N);
 int pnr_nerf_render_frame(const pnr_nerf_frame_args* args, pnr_stream_t stream);
@@ -371,7 +377,8 @@ int pnr_nerf_render_frame(const pnr_nerf_frame_args* args, pnr_stream_t stream);
  * per host thread and device (a second _submit is PNR_ERR_INVALID; a whole-frame call drops a submitted frame that was never finished); nothing the frame
  * reads or writes may be touched in between.  The frame keeps the pnr_set_option switches _submit saw (aux_fusion, composite_fusion, hosted_tail,
  * march_budget, march_budget0, march_blocks, iteration_margin, dynamic_tiles, block_skip, coop_march, palette_waves12): a pnr_set_option between the two
- * calls applies from the next frame on.  pnr_nerf_render_frame == _submit + _finish. */
+ * calls applies from the next frame on.  pnr_nerf_render_frame == _submit + _finish.  (`noises` is read by the frame's first iteration, which _submit
+ * enqueues: it is one more input the caller leaves alone until _finish.) */
 int pnr_nerf_render_frame_submit(const pnr_nerf_frame_args* args, pnr_stream_t stream);
 int pnr_nerf_render_frame_finish(const pnr_nerf_frame_args* args, pnr_stream_t stream);
 
@@ -624,6 +631,36 @@ int pnr_get_rays(const float* poses, uint32_t B, float fx, float fy, float cx, f
  * a frame leaves the GPU as 3 bytes per pixel.  u8 = (uint8)(v * 255) (truncation, as numpy's astype for in-range values);
  * linear_to_srgb != 0: v = v < 0.0031308 ? 12.92 v : 1.055 v^0.41666 - 0.055 first. */
 int pnr_image_to_uint8(const float* src, uint64_t n, int linear_to_srgb, uint8_t* dst, pnr_stream_t stream);
+
+/* (ABI 9) The viewer's step behind a frame -- test_gui (palette/utils.py:1106-1119, nerf/utils.py likewise) and the still camera's running mean
+ * (palette/gui.py:225-231) -- in one launch: the maps rendered at src_h x src_w -> the display maps at dst_h x dst_w, fp32, on the device.
+ *   out_image [dst,3]  = nearest(clamp(image, 0, 1)), then linear->sRGB when linear_to_srgb (pnr_image_to_uint8's arithmetic)
+ *   out_depth [dst]    = nearest(depth)
+ *   out_xyz   [dst,3]  = nearest(rays_o + rays_d * depth_origin)   optional (NULL: none; else rays_o, rays_d, depth_origin are required)
+ *   out_clip  [dst,clip_dim] = nearest(clip_feat)                  optional (NULL: none); clip_feat rows are clip_stride floats apart (a view
+ *                        into the frame's aux map is fine), moved 16 bytes at a time when row start, stride and clip_dim allow, 8 or 4 otherwise
+ *   accum     [dst,3]  optional, caller-owned: spp == 0: accum = out_image; else accum = (accum * spp + out_image) / (spp + 1)
+ * nearest: source index min((int)floorf(dst * ((float)in / out)), in - 1) per axis, as F.interpolate(size=..., mode='nearest'); equal sizes: identity.
+ * Same fp32 operations in the same order as the torch expressions: the maps are bit-identical to them (the sRGB branch to an ulp of powf).
+ * Returns PNR_OK for an empty destination (nothing is read), PNR_ERR_INVALID for a missing map or a zero source size. */
+typedef struct pnr_present_args {
+    uint32_t src_h, src_w, dst_h, dst_w;
+    const float* image;            /* [src,3] */
+    const float* depth;            /* [src]   normalised depth */
+    const float* rays_o;           /* [src,3] with out_xyz */
+    const float* rays_d;           /* [src,3] with out_xyz */
+    const float* depth_origin;     /* [src]   with out_xyz: the un-normalised depth (pnr_nerf_frame_args::depth_raw) */
+    const float* clip_feat;        /* [src] rows of clip_dim floats, clip_stride floats apart, with out_clip */
+    uint32_t clip_dim, clip_stride;
+    int linear_to_srgb;
+    float* out_image;
+    float* out_depth;
+    float* out_xyz;
+    float* out_clip;
+    float* accum;
+    uint32_t spp;                  /* frames already in `accum` */
+} pnr_present_args;
+int pnr_present_frame(const pnr_present_args* args, pnr_stream_t stream);
 
 /* ---------------------------------------------------------------- palette ------------------ */
 

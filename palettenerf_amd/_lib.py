@@ -92,6 +92,7 @@ SIGNATURES = {
     "pnr_palette_heads_forward": [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr],
     "pnr_palette_heads_backward": [_ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr],
     "pnr_image_to_uint8": [_ptr, _u64, _int, _ptr, _ptr],
+    "pnr_present_frame": [_ptr, _ptr],
     "pnr_adam_max_tensors": [],
     "pnr_adam_step": [_ptr, _u32, _ptr, _ptr],
     "pnr_get_rays": [_ptr, _u32, _f32, _f32, _f32, _f32, _u32, _u32, _ptr, _u32, _ptr, _ptr, _ptr],
@@ -150,7 +151,7 @@ class NerfFrameArgs(ctypes.Structure):
                 ("num_levels", _u32), ("S", _f32), ("base_resolution", _u32), ("gridtype", _u32), ("packed_weights", _ptr), ("field_precision", _int), ("density_scale", _f32),
                 ("weights_sum", _ptr), ("depth", _ptr), ("image", _ptr), ("workspace", _ptr), ("workspace_bytes", _u64), ("stats", _ptr), ("kernel_ms", _ptr), ("ray_order", _ptr),
                 ("finish", _int), ("bg_color", _f32 * 3), ("bg_map", _ptr), ("table_dtype", _int), ("enc_scale", _f32 * 3), ("watch_overflow", _int),
-                ("aabb", _ptr), ("min_near", _f32), ("depth_raw", _ptr)]
+                ("aabb", _ptr), ("min_near", _f32), ("depth_raw", _ptr), ("noises", _ptr)]
 
 
 MAX_BASIS, MAX_CLIP = 10, 32   # PNR_MAX_BASIS, PNR_MAX_CLIP
@@ -168,6 +169,14 @@ class PaletteFrameArgs(ctypes.Structure):
     _fields_ = [("base", NerfFrameArgs), ("embeddings_palette", _ptr), ("embeddings_clip", _ptr),
                 ("num_basis", _u32), ("clip_dim", _u32), ("pred_clip", _int), ("offsets_weight", _f32), ("view_dep_weight", _f32), ("aux_map", _ptr), ("embeddings_pair", _ptr), ("embeddings_triple", _ptr),
                 ("edit", _ptr)]
+
+
+class PresentArgs(ctypes.Structure):
+    """Mirror of `pnr_present_args` (include/pnr.h)."""
+    _fields_ = ([(n, _u32) for n in ("src_h", "src_w", "dst_h", "dst_w")]
+                + [(n, _ptr) for n in ("image", "depth", "rays_o", "rays_d", "depth_origin", "clip_feat")]
+                + [("clip_dim", _u32), ("clip_stride", _u32), ("linear_to_srgb", _int)]
+                + [(n, _ptr) for n in ("out_image", "out_depth", "out_xyz", "out_clip", "accum")] + [("spp", _u32)])
 
 
 class PaletteWeights(ctypes.Structure):

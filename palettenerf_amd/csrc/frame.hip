@@ -91,7 +91,7 @@ __device__ __forceinline__ int schedule_n_step(int N, int n_alive) {  // nerf/re
 
 // A frame's first launch.  Per ray (thread i = processing slot i): the optional gather into processing order (pnr_nerf_frame_args::ray_order -- the frame
 // runs on copies of the per-ray inputs in that order and on outputs kept in that order, scattered back to ray ids at the end; per-ray results do not
-// depend on the slot a ray occupies (no perturbation on this path), and listing rays tile by tile (8x8 pixels per wave) keeps the 64 rays of a wave
+// depend on the slot a ray occupies (the first-sample jitter, pnr_nerf_frame_args::noises, is indexed by ray id and gathered here with the other inputs), and listing rays tile by tile (8x8 pixels per wave) keeps the 64 rays of a wave
 // spatially compact, which the hash-grid gathers and the march like), the optional near / far against the box (pnr_nerf_frame_args::aabb:
 // pnr_near_far_from_aabb's arithmetic, written by ray id as that op writes them), and the state "in front of iteration 0" as k_frame_march expects it
 // from a previous iteration: a full alive list whose chunks all survive (identity compaction), nothing marched yet.  (Three launches until round 5:
@@ -103,6 +103,7 @@ struct FrameBegin {
     const float* aabb; float min_near;          // else: computed here ...
     float *nears_out, *fars_out;                // ... and written by ray id
     float *so, *sd, *sf;                        // order != NULL: the inputs in processing order (the near only seeds rays_t)
+    const float* noises; float* snoise;         // order != NULL and noises != NULL: the per-ray jitter in processing order
     float* aux_zero; uint32_t aux_stride;       // PaletteNeRF: the frame's aux map (processing order), zeroed here; stride a multiple of 4 floats
 };
 __global__ void __launch_bounds__(kRayBlock) k_frame_begin(uint32_t N, FrameBegin fb, int32_t* __restrict__ alive,
@@ -128,6 +129,7 @@ __global__ void __launch_bounds__(kRayBlock) k_frame_begin(uint32_t N, FrameBegi
 #pragma unroll
                 for (int k = 0; k < 3; k++) { fb.so[i * 3 + k] = o[k]; fb.sd[i * 3 + k] = d[k]; }
                 fb.sf[i] = far;
+                if (fb.noises) fb.snoise[i] = fb.noises[r];
             }
         } else {
             near = fb.nears_in[r];
@@ -271,7 +273,8 @@ __global__ void __launch_bounds__(kRayBlock) __attribute__((amdgpu_waves_per_eu(
                                                            float* __restrict__ deltas, const uint32_t* __restrict__ mip,
                                                            int32_t* __restrict__ emitted_partials /* [gridDim.x] */, uint32_t budget,
                                                            int32_t* __restrict__ qctr_all /* [2][kQueueCtrs] */, StragglerRec* __restrict__ qrecs,
-                                                           uint8_t* __restrict__ rowflag /* [rows]: 1 = the row belongs to a queued ray */) {
+                                                           uint8_t* __restrict__ rowflag /* [rows]: 1 = the row belongs to a queued ray */,
+                                                           const float* __restrict__ noises /* optional, by processing slot: the first iteration's jitter */) {
     __shared__ int csum[kRayBlock / PNR_WAVE];
     __shared__ unsigned long long red[kRayBlock / PNR_WAVE];
     __shared__ CoopShared coop[MODE == 1 ? kRayBlock / PNR_WAVE : 1];
@@ -392,7 +395,10 @@ __global__ void __launch_bounds__(kRayBlock) __attribute__((amdgpu_waves_per_eu(
             t = rays_t[index];
             const BoxHit bh = clip_to_box(c, fars[index]);
             far = bh.far;
-            t = fmaf(clampf(t * c.dt_gamma, c.dt_min, c.dt_max), 0.0f, t);  // perturb == False on the inference path
+            // raymarching.cu:927,945: the first sample's jitter, in the frame's first iteration only (the loops pass `perturb if step == 0 else False`,
+            // nerf/renderer.py:366); every later iteration -- and every frame without noises -- keeps the zero term
+            const float noise = (noises && prev->iterations == -1) ? noises[index] : 0.0f;
+            t = fmaf(clampf(t * c.dt_gamma, c.dt_min, c.dt_max), noise, t);
             last_t = t;
             t = skip_to_box<MIP && POW2>(c, bh, t);
         }
@@ -1148,7 +1154,7 @@ struct FrameWorkspace {
     float *rays_t, *xyzs, *dirs, *deltas, *enc, *sigmas, *rgbs;
     float *enc_pal, *enc_clip, *aux;  // palette model only
     void* edit;                       // palette model only: device image of the edit parameters
-    float *s_o, *s_d, *s_near, *s_far, *s_ws, *s_depth, *s_image, *s_aux;  // ray_order: inputs / outputs in processing order
+    float *s_o, *s_d, *s_noise, *s_far, *s_ws, *s_depth, *s_image, *s_aux;  // ray_order: inputs (s_noise: the jitter, when the frame has one) / outputs in processing order
     int32_t* scratch;
     int32_t* partials[2];   // the march's per-workgroup sample counts (+ the hosted tail's): written by iteration i, summed by iteration i + 1
     HostedConst* hosted;    // hosted march tail: frame constants (written by k_frame_begin)
@@ -1184,7 +1190,7 @@ static FrameWorkspace carve(void* base, uint32_t N, uint32_t aux_stride = 0, boo
         w.aux = reinterpret_cast<float*>(take(n * aux_stride * 4));
     }
     w.s_o = reinterpret_cast<float*>(take(n * 12)); w.s_d = reinterpret_cast<float*>(take(n * 12));
-    w.s_near = reinterpret_cast<float*>(take(n * 4)); w.s_far = reinterpret_cast<float*>(take(n * 4));
+    w.s_noise = reinterpret_cast<float*>(take(n * 4)); w.s_far = reinterpret_cast<float*>(take(n * 4));
     w.s_ws = reinterpret_cast<float*>(take(n * 4)); w.s_depth = reinterpret_cast<float*>(take(n * 4));
     w.s_image = reinterpret_cast<float*>(take(n * 12));
     w.s_aux = aux_stride ? reinterpret_cast<float*>(take(n * aux_stride * 4)) : nullptr;
@@ -1376,7 +1382,8 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
     FrameBegin fb = {};
     fb.order = a->ray_order; fb.rays_o = a->rays_o; fb.rays_d = a->rays_d; fb.nears_in = a->nears; fb.fars_in = a->fars;
     fb.aabb = a->aabb; fb.min_near = a->min_near; fb.nears_out = a->nears; fb.fars_out = a->fars;
-    fb.so = w.s_o; fb.sd = w.s_d; fb.sf = w.s_far;
+    fb.so = w.s_o; fb.sd = w.s_d; fb.sf = w.s_far; fb.noises = a->noises; fb.snoise = w.s_noise;
+    const float* noise_p = a->noises ? (sorted ? w.s_noise : a->noises) : nullptr;   // by processing slot, as the march indexes it
     if (phase != kFinish) {
         // one submitted frame per host thread and device: a second _submit is refused (finish the first one).  A WHOLE-frame call drops a submitted frame that
         // was never finished (the caller gave it up -- an exception between its two halves): its launches are in the stream in front of this frame's, nothing
@@ -1459,7 +1466,7 @@ static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_fra
 #define PNR_LAUNCH_MARCH(MIPV, P2V, MODEV)                                                                                                                \
             hipLaunchKernelGGL((k_frame_march<MIPV, P2V, MODEV>), gm, bm, march_lds, s, prev, cur, alive_prev, alive_in, counts_of(iter + 1), counts_of(iter), w.scratch, N, a->max_steps,    \
                                w.partials[(iter + 1) & 1], prev_partials, w.rays_t, in_o, in_d, mp, a->bitfield, in_far, w.xyzs, w.dirs, w.deltas, mip,           \
-                               w.partials[iter & 1], budget, w.qctr, w.qrecs, w.rowflag)
+                               w.partials[iter & 1], budget, w.qctr, w.qrecs, w.rowflag, noise_p)
             if (mode == 2) PNR_LAUNCH_MARCH(true, true, 2);   // (hosted implies the mip and power-of-two configuration)
             else if (use_mip && pow2) PNR_LAUNCH_MARCH(true, true, 1);
             else if (use_mip) PNR_LAUNCH_MARCH(true, false, 1);

@@ -573,7 +573,7 @@ using namespace pnr;
 
 extern "C" {
 
-int pnr_abi_version(void) { return 8; }
+int pnr_abi_version(void) { return 9; }
 
 int pnr_set_option(const char* name, int value) {
     if (!name) return PNR_ERR_INVALID;

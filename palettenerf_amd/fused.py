@@ -430,13 +430,22 @@ def _set_finish(a, bg_color, N, mask):
     return True
 
 
+def _noises_ptr(noises, N, dev):
+    """The `noises` field of a frame-args struct: None, or the address of N contiguous fp32 values on the frame's device (the token keeps the tensor)."""
+    if noises is None:
+        return None
+    if not (torch.is_tensor(noises) and noises.dtype == torch.float32 and noises.device == dev and noises.is_contiguous() and noises.numel() == N):
+        raise RuntimeError("noises must be N contiguous fp32 values on the rays' device (one uniform draw per ray, indexed by ray id)")
+    return noises.data_ptr()
+
+
 class StaleFrame(RuntimeError):
     """frame_launch of a frame that was prepared before the object's blobs were rebuilt (invalidate_caches): prepare it again."""
 
 
 class _FrameToken:
     """A frame between frame_prepare and frame_finish: its argument struct, outputs, host-side stats arrays and what a re-render needs."""
-    __slots__ = ("a", "p", "out", "stats", "kms", "watch_state", "watch", "finished", "nears", "fars", "again", "keep", "stream", "depth_raw", "edit", "valid", "gen")
+    __slots__ = ("a", "p", "out", "stats", "kms", "watch_state", "watch", "finished", "nears", "fars", "again", "keep", "stream", "depth_raw", "edit", "valid", "gen", "noises")
 
     def __init__(self, **kw):
         self.valid = None
@@ -523,14 +532,15 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch):
         return hit[1]
 
     @torch.no_grad()
-    def render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0):
+    def render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0, noises=None):
         """One inference frame through the device-driven loop (pnr_nerf_render_frame).  Returns
         (weights_sum [N], depth [N], image [N,3], stats dict).  bg_color None: raw accumulations (bg mix and depth normalisation are
         the caller's); a number, 3 numbers or an [N,3] tensor: the call also applies run_cuda's epilogue (image + (1 - ws) bg,
         normalised depth) -- stats['finished'] says so.  aabb (device tensor of 6 floats) with nears = fars = None: the call computes
-        near / far in its first launch (near_far_from_aabb's arithmetic); stats['nears'], stats['fars'] hold them."""
+        near / far in its first launch (near_far_from_aabb's arithmetic); stats['nears'], stats['fars'] hold them.  noises ([N] fp32 on the device, by ray
+        id): the first-sample jitter of march_rays(perturb=True), applied in the frame's first iteration (pnr_nerf_frame_args::noises); None: no jitter."""
         with self._held():
-            return self._render_frame(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near)
+            return self._render_frame(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
 
     # The same frame in three steps (round 6; pnr_nerf_render_frame_submit / _finish): frame_prepare does everything in front of the library call (outputs, argument
     # struct, source checksums) and may run while the PREVIOUS frame is still on the device; frame_launch enqueues the frame and returns at once; frame_finish waits
@@ -538,9 +548,9 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch):
     #     tok = prepare(0); launch(tok);  for i in 1..: nxt = prepare(i); out = finish(tok); launch(nxt); tok = nxt; consume(out)
     # so that the host's work for frame i + 1 lies under frame i's kernels.  Two argument structs alternate (a frame's struct must stay as it was until its finish).
     @torch.no_grad()
-    def frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0):
+    def frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0, noises=None):
         with self._held():
-            return self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near)
+            return self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
 
     def frame_launch(self, tok):
         if tok.gen != self.__dict__.get("_gen", 0):
@@ -566,13 +576,13 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch):
         self.frame_wait(tok)
         return self.frame_result(tok)
 
-    def _render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near):
-        tok = self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near)
+    def _render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises=None):
+        tok = self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
         rc = _lib.load().pnr_nerf_render_frame(ctypes.byref(tok.a), stream_ptr())
         _lib.check(rc, "pnr_nerf_render_frame")
         return self._frame_post(tok)
 
-    def _frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near):
+    def _frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises=None):
         from . import raymarching
         m = self.model
         N = rays_o.shape[0]
@@ -635,11 +645,12 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch):
         kms = (ctypes.c_float * 2)()
         a.kernel_ms = ctypes.cast(kms, ctypes.c_void_p) if self.time_grid_kernel else None
         finished = _set_finish(a, bg_color, N, 3)
+        a.noises = _noises_ptr(noises, N, dev)
         for t, name in ((rays_o, "rays_o"), (rays_d, "rays_d"), (nears, "nears"), (fars, "fars")):
             require(t, torch.float32, name)
         return _FrameToken(gen=self.__dict__.get("_gen", 0), a=a, out=(ws, depth, image), stats=stats, kms=kms, watch_state=watch_state, watch=watch, finished=finished, nears=nears, fars=fars,
-                           again=(rays_o, rays_d, None if aabb is not None else nears, None if aabb is not None else fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near),
-                           keep=(mip, bg_color, blob))
+                           again=(rays_o, rays_d, None if aabb is not None else nears, None if aabb is not None else fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises),
+                           keep=(mip, bg_color, blob), noises=noises)
 
     def _frame_post(self, tok):
         valid = tok.valid if tok.valid is not None else _frame_valid(self, tok)
@@ -889,19 +900,19 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
             setattr(self, name + "_key", key)
         return getattr(self, name)
 
-    def render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0):
+    def render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0, noises=None):
         """One PaletteNeRF inference frame through the device-driven loop (pnr_palette_render_frame).
         Returns (weights_sum [N], depth [N], image [N,3], aux_map [N, aux_channels], stats).  bg_color None: raw accumulations; a number, 3 numbers
         or an [N,3] tensor: the call's last launch also applies run_cuda's epilogue (palette/renderer.py:520-540: image and aux_map[:, 0:3] = direct_rgb
         blended with the background, depth normalised, the raw depth kept in stats['depth_raw']) -- stats['finished'] says so.  aabb with
-        nears = fars = None: near / far computed by the call's first launch (stats['nears'], stats['fars'])."""
+        nears = fars = None: near / far computed by the call's first launch (stats['nears'], stats['fars']).  noises: NeRFFieldFused.render_frame explains."""
         with torch.no_grad(), self._held():
-            return self._render_frame(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near)
+            return self._render_frame(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
 
     # prepare / launch / finish: NeRFFieldFused explains (pnr_palette_render_frame_submit / _finish)
-    def frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0):
+    def frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0, noises=None):
         with torch.no_grad(), self._held():
-            return self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near)
+            return self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
 
     def frame_launch(self, tok):
         if tok.gen != self.__dict__.get("_gen", 0):
@@ -923,13 +934,13 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
         self.frame_wait(tok)
         return self.frame_result(tok)
 
-    def _render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near):
-        tok = self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near)
+    def _render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises=None):
+        tok = self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
         rc = _lib.load().pnr_palette_render_frame(ctypes.byref(tok.p), stream_ptr())
         _lib.check(rc, "pnr_palette_render_frame")
         return self._frame_post(tok)
 
-    def _frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near):
+    def _frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises=None):
         from . import raymarching
         m = self.model
         N = rays_o.shape[0]
@@ -1001,6 +1012,7 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
         a.stats = ctypes.cast(stats, ctypes.c_void_p)
         a.kernel_ms = ctypes.cast(kms, ctypes.c_void_p) if getattr(self, "time_grid_kernel", False) else None
         finished = _set_finish(a, bg_color, N, 7)
+        a.noises = _noises_ptr(noises, N, dev)
         depth_raw = torch.empty(N, dtype=torch.float32, device=dev) if finished else None
         a.depth_raw = depth_raw.data_ptr() if finished else None
         p.aux_map = aux_map.data_ptr()
@@ -1010,8 +1022,8 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
             require(t, torch.float32, name)
         return _FrameToken(gen=self.__dict__.get("_gen", 0), a=a, p=p, out=(ws, depth, image, aux_map), stats=stats, kms=kms, watch_state=watch_state, watch=watch, finished=finished, nears=nears, fars=fars,
                            depth_raw=depth_raw, edit=edit,
-                           again=(rays_o, rays_d, None if aabb is not None else nears, None if aabb is not None else fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near),
-                           keep=(mip, bg_color, self.packed))
+                           again=(rays_o, rays_d, None if aabb is not None else nears, None if aabb is not None else fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises),
+                           keep=(mip, bg_color, self.packed), noises=noises)
 
     def _frame_post(self, tok):
         valid = tok.valid if tok.valid is not None else _frame_valid(self, tok)

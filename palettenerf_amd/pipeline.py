@@ -207,3 +207,110 @@ def render_path(model, poses, intrinsics, H, W, frames_in_flight=2, linear_to_sr
         import numpy as np
         return np.stack([f[0].numpy() for f in frames]), np.stack([f[1].numpy() for f in frames])
     return torch.stack([f[0] for f in frames]), torch.stack([f[1] for f in frames])
+
+
+def present_frame(image, depth, rH, rW, H, W, rays_o=None, rays_d=None, depth_origin=None, clip_feat=None, linear_to_srgb=False, accum=None, accum_count=0):
+    """pnr_present_frame: the maps of a frame rendered at rH x rW -> the viewer's maps at H x W (nearest upsampling as F.interpolate's, clamp, optional
+    linear->sRGB, the xyz pick map rays_o + rays_d * depth_origin, the clip_feat map, and optionally the running mean into `accum`), one launch, fp32 on
+    the device.  clip_feat may be a strided view ([N, clip_dim] columns of the frame's aux map).  accum: [H, W, 3] fp32, caller-owned;
+    accum_count = frames already in it (0: the buffer is overwritten).  Returns {image, depth[, xyz][, clip_feat]}."""
+    import ctypes
+    from . import _lib
+    from ._torch_glue import require, stream_ptr
+    dev = image.device
+    a = _lib.PresentArgs()
+    a.src_h, a.src_w, a.dst_h, a.dst_w = int(rH), int(rW), int(H), int(W)
+    n_src = int(rH) * int(rW)
+    keep = []
+
+    def src(t, cols, name):
+        t = require((t.reshape(n_src, cols) if cols else t.reshape(n_src)).contiguous(), torch.float32, name)
+        keep.append(t)
+        return t.data_ptr()
+
+    a.image, a.depth = src(image, 3, "image"), src(depth, 0, "depth")
+    out = {"image": torch.empty(H, W, 3, dtype=torch.float32, device=dev), "depth": torch.empty(H, W, dtype=torch.float32, device=dev)}
+    if depth_origin is not None:
+        a.rays_o, a.rays_d, a.depth_origin = src(rays_o, 3, "rays_o"), src(rays_d, 3, "rays_d"), src(depth_origin, 0, "depth_origin")
+        out["xyz"] = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+        a.out_xyz = out["xyz"].data_ptr()
+    if clip_feat is not None:
+        cf = clip_feat.reshape(n_src, clip_feat.shape[-1])
+        if cf.dtype != torch.float32 or not cf.is_cuda:
+            raise RuntimeError("clip_feat must be a float32 CUDA tensor")
+        if cf.shape[1] == 0 or cf.stride(1) != 1 or cf.stride(0) < cf.shape[1]:     # (rows of a wider map are fine: the launch takes their stride)
+            cf = cf.contiguous()
+        keep.append(cf)
+        a.clip_feat, a.clip_dim, a.clip_stride = cf.data_ptr(), cf.shape[1], cf.stride(0) if n_src > 1 else cf.shape[1]
+        out["clip_feat"] = torch.empty(H, W, cf.shape[1], dtype=torch.float32, device=dev)
+        a.out_clip = out["clip_feat"].data_ptr() if cf.shape[1] else None
+    a.linear_to_srgb = int(bool(linear_to_srgb))
+    a.out_image, a.out_depth = out["image"].data_ptr(), out["depth"].data_ptr()
+    if accum is not None:
+        if not (accum.dtype == torch.float32 and accum.device == dev and accum.is_contiguous() and accum.numel() == H * W * 3):
+            raise RuntimeError("accum must be a contiguous [H, W, 3] fp32 buffer on the frame's device")
+        a.accum, a.spp = accum.data_ptr(), int(accum_count)
+    _lib.check(_lib.load().pnr_present_frame(ctypes.byref(a), stream_ptr()), "pnr_present_frame")
+    return out
+
+
+def viewer_frame(model, pose, intrinsics, W, H, bg_color=None, spp=1, downscale=1, gui_mode=True, linear_to_srgb=False, accum=None, accum_count=0,
+                 **render_kwargs):
+    """One frame of the reference's viewer, `Trainer.test_gui` (palette/utils.py:1083-1133, nerf/utils.py likewise) without the trainer around it:
+    render at rH x rW = int(H * downscale) x int(W * downscale) with the intrinsics scaled, rays generated on the device, `perturb = False if spp == 1
+    else spp` (the frames of a still camera are jittered and averaged; the native frame loop takes the jitter), then ONE launch (present_frame) for
+    the clamp, the nearest upsampling to H x W, linear->sRGB for linear-colour scenes, PaletteNeRF's xyz / clip_feat pick maps and -- with `accum` --
+    the running mean of gui.py:225-231.  Returns device tensors: image [H,W,3], depth [H,W], for a PaletteNeRF model also xyz [H,W,3] and clip_feat
+    [H,W,clip_dim], and `frame`, the model's own result dict; `.cpu()` is the caller's.  Wrap the call in torch.autocast for the reference's -O mode."""
+    from . import rays as prays
+    rH, rW = int(H * downscale), int(W * downscale)
+    if rH < 1 or rW < 1:
+        raise ValueError(f"viewer_frame: downscale {downscale} leaves no pixel of {H} x {W} to render")
+    device = next(model.parameters()).device
+    pose = torch.as_tensor(pose, dtype=torch.float32).reshape(1, 4, 4).to(device)
+    ro, rd = prays.rays_from_indices(pose, [float(v) * downscale for v in intrinsics], rH, rW, None)
+    palette = hasattr(model, "num_basis")
+    kw = dict(render_kwargs, bg_color=bg_color, perturb=False if spp == 1 else spp)
+    if palette:
+        kw["gui_mode"] = gui_mode
+    with torch.no_grad():
+        r = model.render(ro, rd, **kw)
+        out = present_frame(r["image"], r["depth"], rH, rW, H, W, rays_o=ro if palette else None, rays_d=rd if palette else None,
+                            depth_origin=r["depth_origin"] if palette else None, clip_feat=r["clip_feat"] if palette else None,
+                            linear_to_srgb=linear_to_srgb, accum=accum, accum_count=accum_count)
+    out["frame"] = r
+    return out
+
+
+class ViewerAccumulator:
+    """The display buffer of the reference's viewer (palette/gui.py:196-231) around viewer_frame: it owns the [H, W, 3] buffer and `spp`.  After
+    `need_update` (a moved camera, an edited palette: set it, or call reset()) the next frame replaces the buffer and spp becomes 1; every later frame
+    of the still scene is rendered with perturb = spp and averaged in, buffer = (buffer * spp + frame) / (spp + 1), until spp reaches max_spp.  The mean
+    is formed inside viewer_frame's one launch.  The dynamic-resolution controller of gui.py:207-213 is the caller's: pass `downscale` per step (a change
+    of downscale does not change the buffer's size).
+    Two things are gui.py's and kept on purpose: the frame after a reset is rendered with the spp the buffer HAD (gui.py:201 passes self.spp before
+    :227 resets it -- that frame is jittered unless spp was 1), and the first frame averaged in (spp == 1) is not jittered (perturb = False if spp == 1)."""
+
+    def __init__(self, model, W, H, max_spp=64, linear_to_srgb=False):
+        self.model, self.W, self.H, self.max_spp, self.linear_to_srgb = model, int(W), int(H), int(max_spp), bool(linear_to_srgb)
+        self.spp, self.need_update, self.buffer = 1, True, None
+
+    def reset(self):
+        self.need_update = True
+
+    def step(self, pose, intrinsics, bg_color=None, downscale=1, gui_mode=True, **render_kwargs):
+        """One viewer frame; returns viewer_frame's dict plus `accum` (the display buffer, owned by this object: copy it to keep it) and `spp`,
+        or None when the buffer has converged (spp == max_spp and nothing changed) -- gui.py:197."""
+        if not (self.need_update or self.spp < self.max_spp):
+            return None
+        if self.buffer is None:
+            self.buffer = torch.empty(self.H, self.W, 3, dtype=torch.float32, device=next(self.model.parameters()).device)
+            self.need_update = True
+        out = viewer_frame(self.model, pose, intrinsics, self.W, self.H, bg_color=bg_color, spp=self.spp, downscale=downscale, gui_mode=gui_mode,
+                           linear_to_srgb=self.linear_to_srgb, accum=self.buffer, accum_count=0 if self.need_update else self.spp, **render_kwargs)
+        if self.need_update:
+            self.spp, self.need_update = 1, False
+        else:
+            self.spp += 1
+        out["accum"], out["spp"] = self.buffer, self.spp
+        return out

@@ -330,7 +330,9 @@ class _RendererBase(nn.Module):
             raise RuntimeError("render_prepare / render_launch / render_finish exist for march_mode = 'native' inference frames")
         with torch.no_grad():
             pending = self.run_cuda(rays_o, rays_d, _phase="prepare", **kwargs)
-        pending.redo = lambda: self.render_prepare(rays_o, rays_d, **kwargs)
+        # (a frame prepared again keeps the jitter it drew: a second torch.rand would give the queued frame another noise than render() under the same seed)
+        again = dict(kwargs, noises=pending.tok.noises)
+        pending.redo = lambda: self.render_prepare(rays_o, rays_d, **again)
         return pending
 
     def render_launch(self, pending):
@@ -387,6 +389,17 @@ class PendingFrame:
 
     def __init__(self, fused, tok, complete):
         self.fused, self.tok, self.complete, self.redo = fused, tok, complete, None
+
+
+def _frame_noises(perturb, noises, N, rays_o):
+    """The native frame's first-sample jitter: an explicit `noises` ([N] fp32 on the device, by ray id) as given; else, with a truthy `perturb`, the draw
+    the per-op loop's first march_rays makes (raymarching.py: torch.rand(n_alive) with n_alive = N, the frame's only draw) -- nothing touches torch's
+    generator between run_cuda's entry and that call, so under one torch.manual_seed both loops see the same noise; else None (no jitter)."""
+    if noises is not None:
+        return noises
+    if perturb:
+        return torch.rand(N, dtype=rays_o.dtype, device=rays_o.device)
+    return None
 
 
 def _zero_map(owner, name, shape, like):
@@ -504,6 +517,8 @@ class NeRFRenderer(_OccupancyMaintenance, _RendererBase):
         elif bg_color is None:
             bg_color = 1
         results = {}
+        if self.training and kwargs.get("noises") is not None:
+            raise RuntimeError("noises= belongs to the native inference frame; the training march draws its own with perturb")
         if self.training:
             counter = self.step_counter[self.local_step % 16]
             counter.zero_()
@@ -534,14 +549,13 @@ class NeRFRenderer(_OccupancyMaintenance, _RendererBase):
             if getattr(self, "_fused", None) is None:
                 from .fused import NeRFFieldFused
                 self._fused = NeRFFieldFused(self)
-            if perturb:
-                raise RuntimeError("march_mode='native' covers inference without perturbation")
+            noises = _frame_noises(perturb, kwargs.get("noises"), N, rays_o)
             # under fp16 autocast (the reference's -O mode) the loop looks the hash table up as fp16 with the reference's half interpolation
             # (gridencoder/grid.py:36-39), the field stays on its fp32-accurate matrix path; outputs are fp32 as the reference's are
             was_half = self._fused.table_half
             self._fused.table_half = was_half or torch.is_autocast_enabled()
             frame_args = (rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh)
-            frame_kw = dict(bg_color=bg_color, aabb=aabb if native_frame else None, min_near=self.min_near)
+            frame_kw = dict(bg_color=bg_color, aabb=aabb if native_frame else None, min_near=self.min_near, noises=noises)
             try:
                 if kwargs.get("_phase") == "prepare":   # render_prepare(): everything in front of the library call, now; the frame itself in render_launch / render_finish
                     tok = self._fused.frame_prepare(*frame_args, **frame_kw)
@@ -580,6 +594,8 @@ class NeRFRenderer(_OccupancyMaintenance, _RendererBase):
                 raymarching.composite_rays(n_alive, n_step, st.rays_alive, st.rays_t, sigmas, rgbs, deltas, st.weights_sum, st.depth,
                                            st.image, T_thresh)
 
+            if kwargs.get("noises") is not None:
+                raise RuntimeError("noises= belongs to the native frame (march_mode = 'native'); the per-op loops draw their own with perturb")
             st = self._infer_loop(rays_o, rays_d, nears, fars, perturb, dt_gamma, max_steps, shade)
             weights_sum = st.weights_sum
             image = st.image + (1 - weights_sum).unsqueeze(-1) * bg_color
@@ -732,10 +748,10 @@ class PaletteRenderer(_RendererBase):
         nb, clip_dim = self.num_basis, self.opt.clip_dim
         aabb = self.aabb_train if self.training else self.aabb_infer
         # under fp16 autocast only the native loop takes the fused path (fp16 tables, fp32-accurate field; with the clip head: the half triple)
-        autocast_ok = not torch.is_autocast_enabled() or (self.march_mode == "native" and not perturb)
+        autocast_ok = not torch.is_autocast_enabled() or self.march_mode == "native"
         # RegionEdit and the Stylizer run inside the fused field kernel's epilogue (pnr_palette_edit): editing costs no extra launch
         use_fused = not self.training and bool(getattr(self, "fused_field", False)) and autocast_ok
-        native = use_fused and self.march_mode == "native" and not perturb
+        native = use_fused and self.march_mode == "native"
         # the device-driven frame computes near / far inside its own first launch (same arithmetic, one launch and one operator call less per frame)
         native_near_far = native and rays_o.is_cuda and aabb.is_cuda
         nears, fars = (None, None) if native_near_far else raymarching.near_far_from_aabb(rays_o, rays_d, aabb, self.min_near)
@@ -746,6 +762,8 @@ class PaletteRenderer(_RendererBase):
             bg_color = 1
         results = {}
 
+        if self.training and kwargs.get("noises") is not None:
+            raise RuntimeError("noises= belongs to the native inference frame; the training march draws its own with perturb")
         if self.training:
             counter = self.step_counter[self.local_step % 16]
             counter.zero_()
@@ -919,7 +937,8 @@ class PaletteRenderer(_RendererBase):
             was_half = self._fused.table_half
             self._fused.table_half = was_half or torch.is_autocast_enabled()     # -O mode: fp16 tables with the reference's half interpolation
             frame_args = (rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh)
-            frame_kw = dict(bg_color=bg_color, aabb=aabb if native_near_far else None, min_near=self.min_near)
+            frame_kw = dict(bg_color=bg_color, aabb=aabb if native_near_far else None, min_near=self.min_near,
+                            noises=_frame_noises(perturb, kwargs.get("noises"), N, rays_o))
             try:
                 if kwargs.get("_phase") == "prepare":   # render_prepare(): the frame itself goes out in render_launch / render_finish
                     tok = self._fused.frame_prepare(*frame_args, **frame_kw)
@@ -941,5 +960,7 @@ class PaletteRenderer(_RendererBase):
             if kwargs.get("_phase") == "prepare":
                 return PendingFrame(self._fused, tok, lambda ret: complete(ret))
             return complete(ret)
+        if kwargs.get("noises") is not None:
+            raise RuntimeError("noises= belongs to the native frame (march_mode = 'native', fused_field); the per-op loops draw their own with perturb")
         st = self._infer_loop(rays_o, rays_d, nears, fars, perturb, dt_gamma, max_steps, shade_fused if use_fused else shade)
         return tail(st, aux_map if use_fused else None, False, None, nears, fars)
