@@ -761,6 +761,42 @@ int pnr_hsv_to_rgb(uint32_t n, const float* input, float* output, pnr_stream_t s
 int pnr_rgb_histogram(const float* colors_rgb, const float* weights, uint32_t n, int bits_per_channel, double* bin_weights,
                       float* bin_centers, pnr_stream_t stream);
 
+/* ---------------------------------------------------------------- background model (ABI 10) - */
+
+/* The background of an unbounded capture (bg_radius > 0: nerf/network.py:145-160, palette/network.py:205-220, fed by sph_from_ray in
+ * nerf/renderer.py:270-273) for all N rays of a frame in ONE launch, one ray per lane:
+ *   (u, v)  = pnr_sph_from_ray's coordinates of the ray (same arithmetic, same bits; with coords_in: read instead of computed)
+ *   enc     = encoder_bg((u, v)): the D = 2, C = 2 lookup of pnr_grid_encode_forward on ((u, v) + 1) / 2 -- fp32 table: fmaf chains; fp16 table:
+ *             the half accumulator of the reference's autocast lookup, upcast once
+ *   rgb     = sigmoid(W1 . relu(W0 . [SH_4(d) ; enc]))       fp32 fmaf chains in input order, weights staged in LDS
+ * Supported: num_levels = 4, level_dim = 2, sh_degree = 4, num_layers = 2, hidden_dim = 64 (the reference's only background architecture);
+ * anything else is PNR_ERR_UNSUPPORTED, before anything is launched.  A null struct or a missing pointer is PNR_ERR_INVALID; N = 0 is PNR_OK.
+ *   pnr_background_pack: bg_net.0.weight [64, 24] and bg_net.1.weight [3, 64] (row-major [out][in], device fp32) -> `packed`
+ *                        (pnr_background_packed_bytes() bytes, 16-byte aligned); call again when either weight changes. */
+typedef struct pnr_background_args {
+    uint32_t N;
+    const float* rays_o;           /* [N,3]; not read with coords_in */
+    const float* rays_d;           /* [N,3] unit directions */
+    float radius;                  /* bg_radius; not used with coords_in */
+    const float* coords_in;        /* optional [N,2]: sphere coordinates already at hand (NeRFNetwork.background(x, d)); NULL: computed from the rays */
+    const void* embeddings;        /* encoder_bg table [table_rows, 2], fp32 or fp16 (table_dtype) */
+    int table_dtype;               /* PNR_DTYPE_F32 / PNR_DTYPE_F16 */
+    const int32_t* offsets;        /* device int32[num_levels + 1], read by the kernel; a level that does not fit table_rows gives zeros */
+    uint32_t table_rows;
+    uint32_t num_levels, level_dim;
+    float S;                       /* log2(per_level_scale) */
+    uint32_t H;                    /* base_resolution */
+    uint32_t gridtype;             /* 0 hash, 1 tiled */
+    int align_corners;
+    uint32_t sh_degree, num_layers, hidden_dim;
+    const float* packed;           /* pnr_background_pack output */
+    float* out;                    /* [N,3] fp32 */
+    float* coords_out;             /* optional [N,2]: the sphere coordinates the lookup used */
+} pnr_background_args;
+uint64_t pnr_background_packed_bytes(void);
+int pnr_background_pack(const float* w0, const float* w1, float* packed, pnr_stream_t stream);
+int pnr_background_forward(const pnr_background_args* args, pnr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
 // the same scan, and all launches take an explicit stream.
 #include "pnr_common.hpp"
 #include "march_core.hpp"
+#include "sph_core.hpp"
 
 namespace pnr {
 
@@ -42,16 +43,12 @@ __global__ void __launch_bounds__(kBlock) k_sph_from_ray(const float* __restrict
                                                          float radius, uint32_t N, float* __restrict__ coords) {
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     if (n >= N) return;
-    const float RPI = 0.3183098861837907f;
     const float ox = rays_o[n * 3], oy = rays_o[n * 3 + 1], oz = rays_o[n * 3 + 2];
     const float dx = rays_d[n * 3], dy = rays_d[n * 3 + 1], dz = rays_d[n * 3 + 2];
-    const float A = dx * dx + dy * dy + dz * dz;
-    const float B = ox * dx + oy * dy + oz * dz;
-    const float Cq = ox * ox + oy * oy + oz * oz - radius * radius;
-    const float t = (-B + sqrtf(B * B - A * Cq)) / A;
-    const float x = ox + t * dx, y = oy + t * dy, z = oz + t * dz;
-    coords[n * 2] = 2 * atan2f(sqrtf(x * x + z * z), y) * RPI - 1;
-    coords[n * 2 + 1] = atan2f(z, x) * RPI;
+    float u, v;
+    sph_coords_of(ox, oy, oz, dx, dy, dz, radius, u, v);   // sph_core.hpp, shared with the fused background launch (background.hip)
+    coords[n * 2] = u;
+    coords[n * 2 + 1] = v;
 }
 
 // reference raymarching.cu:217-257
@@ -573,7 +570,7 @@ using namespace pnr;
 
 extern "C" {
 
-int pnr_abi_version(void) { return 9; }
+int pnr_abi_version(void) { return 10; }
 
 int pnr_set_option(const char* name, int value) {
     if (!name) return PNR_ERR_INVALID;

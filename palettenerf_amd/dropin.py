@@ -53,7 +53,10 @@ def fuse_field(model, precision="f16x3", pair_lookup=False):
     NeRFFieldFused raises otherwise.  precision: "f16x3" (split-fp16 products, fp32-class), "fp32" (exact fmaf chains) or "f16x2" (opt-in).
     pair_lookup (PaletteNetwork only): look both hash tables up through one interleaved copy (PaletteFieldFused.stand_alone_pair).  The copy follows torch's
     version counters only: after writing the tables through `.data` (torch_ema's copy_to / restore around an evaluation) call
-    invalidate_fused_caches(model), or the forward reads the old tables.  Default: the live tables, whatever wrote them."""
+    invalidate_fused_caches(model), or the forward reads the old tables.  Default: the live tables, whatever wrote them.
+    A model with a background (bg_radius > 0) also gets `background(x, d)` bound the same way: encoder_bg, SH, bg_net and the sigmoid as one launch
+    (pnr_background_forward over the coordinates the caller's sph_from_ray produced) for the same inference batches, the model's own method otherwise;
+    a background that is not the reference's architecture (4 x 2 levels, SH degree 4, 24 -> 64 -> 3) keeps the model's own method."""
     import torch
     from .fused import NeRFFieldFused, PaletteFieldFused
     plain = model.forward
@@ -85,4 +88,25 @@ def fuse_field(model, precision="f16x3", pair_lookup=False):
 
     model._fused = fused
     model.forward = forward      # instance attribute: nn.Module.__call__ resolves self.forward here
+    bind_background(model)
     return model
+
+
+def bind_background(model):
+    """fuse_field's background half: `model.background` as an instance attribute over the model's own BackgroundFused (pipeline.clone_for_concurrent_frames
+    binds a twin's again, over the twin's).  Nothing is bound without a background or for an architecture the launch does not support: the per-op
+    formulation stays."""
+    import torch
+    from .fused import background_fused
+    model.__dict__.pop("background", None)
+    bg_fused = background_fused(model) if getattr(model, "bg_radius", 0) > 0 and getattr(model, "bg_net", None) is not None else None
+    if bg_fused is None:
+        return
+    plain_bg = model.background
+
+    def background(x, d):
+        if torch.is_grad_enabled() or torch.is_autocast_enabled() or not x.is_cuda:
+            return plain_bg(x, d)
+        return bg_fused.from_coords(x, d)
+
+    model.background = background

@@ -185,7 +185,7 @@ def invalidate_fused_caches(model):
     Called by load_state_dict and initialize_palette; call it yourself after writing parameters through `.data` (EMA swap-in / restore:
     nerf/utils.py:829-839, 959-961).  Whole-tensor `.data` rewrites are also caught by the per-frame checksum (_SourceWatch); a write to only
     PART of a hash table is not (tables are checksummed on every 1 021st word): after such a write this call is required."""
-    for attr in ("_fused", "_density_fused"):
+    for attr in ("_fused", "_density_fused", "_bg_fused"):
         f = getattr(model, attr, None)
         if f is not None:
             f.invalidate_caches()
@@ -458,6 +458,115 @@ def _frame_valid(fused, tok):
     if not fused._watch_end(tok.watch_state):
         return 1
     return 2 if (tok.watch and tok.stats[5]) else 0
+
+
+class BackgroundFused:
+    """The background model of a bg_radius > 0 network as ONE launch per frame (pnr_background_forward: sphere coordinates, the 2-D lookup of
+    `encoder_bg`, SH, bg_net, sigmoid), for inference batches.  Conventions of the field classes: the weight blob and, for the reference's -O mode,
+    the half copy of the table are cached and rebuilt when torch's version counters move (_pkey) or invalidate_fused_caches(model) says so; a
+    repack goes into a NEW tensor, so a launch already enqueued keeps reading what it was given; `state()` changes whenever a cached blob was
+    or has to be rebuilt, which is how a frame prepared before a weight change is recognised (renderer.render_launch)."""
+
+    def __init__(self, model):
+        if not self.supported(model):
+            raise RuntimeError("the fused background launch is specialised for the reference's background model (hashgrid 4 x 2 over 2-D, SH degree 4, bg_net 24 -> 64 -> 3)")
+        self.model = model
+        self._blob = None
+        self._emb_half = None
+        self._gen = 0
+
+    @staticmethod
+    def supported(m):
+        from .gridencoder import GridEncoder
+        e, net = getattr(m, "encoder_bg", None), getattr(m, "bg_net", None)
+        try:
+            return (isinstance(e, GridEncoder) and e.input_dim == 2 and e.num_levels == 4 and e.level_dim == 2 and getattr(m.encoder_dir, "degree", 0) == 4
+                    and net is not None and len(net) == 2 and m.num_layers_bg == 2 and m.hidden_dim_bg == 64
+                    and tuple(net[0].weight.shape) == (64, 24) and tuple(net[1].weight.shape) == (3, 64) and net[0].bias is None and net[1].bias is None
+                    and net[0].weight.dtype == torch.float32 and net[1].weight.dtype == torch.float32 and e.embeddings.dtype == torch.float32)
+        except AttributeError:
+            return False
+
+    def _weights(self):
+        return [_weight_of(self.model, "bg_net", 0), _weight_of(self.model, "bg_net", 1)]
+
+    def invalidate_caches(self):
+        self._blob = None
+        self._emb_half = None
+        self._gen += 1
+
+    def state(self):
+        """Identity of everything a launch reads, as far as torch can tell, and the number of invalidations so far."""
+        return (self._gen,) + tuple(_pkey(w) for w in self._weights()) + (_pkey(self.model.encoder_bg.embeddings),)
+
+    def _pack(self):
+        ws = self._weights()
+        key = tuple(_pkey(w) for w in ws)
+        hit = self._blob
+        if hit is None or hit[0] != key or hit[1].device != ws[0].device or PARANOID:
+            blob = torch.empty(int(_lib.load().pnr_background_packed_bytes()) // 4, dtype=torch.float32, device=ws[0].device)
+            call("pnr_background_pack", *[ptr(require(w.detach().contiguous(), torch.float32, "bg_net weight")) for w in ws], ptr(blob))
+            hit = self._blob = (key, blob)
+        return hit[1]
+
+    def _table(self, half):
+        emb = self.model.encoder_bg.embeddings
+        if half:      # the reference's --fp16 table (`embeddings.to(torch.half)` per forward, gridencoder/grid.py:38): converted once per update here
+            return _half_copy(self, "_emb_half", emb), 1
+        return require(emb.detach(), torch.float32, "encoder_bg.embeddings"), 0
+
+    @torch.no_grad()
+    def _launch(self, rays_o, rays_d, coords, want_coords, half):
+        m, enc = self.model, self.model.encoder_bg
+        rays_d = require(rays_d.reshape(-1, 3).contiguous(), torch.float32, "rays_d")
+        N, dev = rays_d.shape[0], rays_d.device
+        half = torch.is_autocast_enabled() if half is None else bool(half)
+        table, dtype = self._table(half)
+        blob = self._pack()
+        out = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        coords_out = torch.empty(N, 2, dtype=torch.float32, device=dev) if want_coords else None
+        a = _lib.BackgroundArgs()
+        a.N = N
+        a.rays_d = rays_d.data_ptr()
+        if coords is not None:
+            coords = require(coords.reshape(-1, 2).contiguous(), torch.float32, "coords")
+            if coords.shape[0] != N:
+                raise RuntimeError("background: one coordinate pair per direction")
+            a.coords_in = coords.data_ptr()
+        else:
+            rays_o = require(rays_o.reshape(-1, 3).contiguous(), torch.float32, "rays_o")
+            if rays_o.shape[0] != N:
+                raise RuntimeError("background: one origin per direction")
+            a.rays_o, a.radius = rays_o.data_ptr(), float(m.bg_radius)
+        a.embeddings, a.table_dtype, a.offsets, a.table_rows = table.data_ptr(), dtype, require(enc.offsets, torch.int32, "offsets").data_ptr(), int(table.shape[0])
+        a.num_levels, a.level_dim, a.S, a.H = enc.num_levels, enc.level_dim, float(np.log2(enc.per_level_scale)), enc.base_resolution
+        a.gridtype, a.align_corners = enc.gridtype_id, int(enc.align_corners)
+        a.sh_degree, a.num_layers, a.hidden_dim = int(m.encoder_dir.degree), int(m.num_layers_bg), int(m.hidden_dim_bg)
+        a.packed, a.out = blob.data_ptr(), out.data_ptr()
+        a.coords_out = coords_out.data_ptr() if coords_out is not None else None
+        # (the launch is enqueued on torch's current stream before this returns: the caching allocator keeps `table`, `blob` and the inputs alive for it)
+        call("pnr_background_forward", ctypes.byref(a), units=N)
+        return (out, coords_out) if want_coords else out
+
+    def from_rays(self, rays_o, rays_d, want_coords=False, half=None):
+        """rays [N,3] -> background colour [N,3] (with want_coords: and the sphere coordinates [N,2], bit for bit raymarching.sph_from_ray's).
+        half None: the half table under autocast, the fp32 table otherwise."""
+        return self._launch(rays_o, rays_d, None, want_coords, half)
+
+    def from_coords(self, x, d, half=None):
+        """NeRFNetwork.background(x, d): x [N,2] the coordinates of sph_from_ray, d [N,3]."""
+        return self._launch(None, d, x, False, half).view(*d.shape[:-1], 3)
+
+
+def background_fused(model):
+    """The model's BackgroundFused (made on first use), or None when its background model is not the architecture the launch supports -- the host
+    then keeps the per-op formulation."""
+    f = model.__dict__.get("_bg_fused")
+    if f is None:
+        if not BackgroundFused.supported(model):
+            return None
+        f = model.__dict__["_bg_fused"] = BackgroundFused(model)
+    return f
 
 
 class NeRFFieldFused(_PrecisionGuard, _SourceWatch):

@@ -2,7 +2,7 @@
 `PaletteNetwork` (palette/network.py:10-280).  Same module/parameter names as the reference so a
 reference checkpoint's state_dict loads (encoder.embeddings, sigma_net.N.weight, color_net.N.weight,
 diff_net, basis_net, offsets_radiance_net, omega_net.0, encoder_palette, encoder_clip, clip_net,
-basis_color, density_grid, density_bitfield, aabb_*, step_counter).
+basis_color, density_grid, density_bitfield, aabb_*, step_counter; with bg_radius > 0 also encoder_bg.embeddings and bg_net.N.weight).
 """
 import torch
 import torch.nn as nn
@@ -71,19 +71,54 @@ def _fused_heads_ok(m, h):
             and (h.requires_grad or m.offsets_radiance_net.weight.requires_grad or m.omega_net[0].weight.requires_grad))
 
 
+def _build_background(m, encoding_bg, num_layers_bg, hidden_dim_bg):
+    """The background model of an unbounded capture (nerf/network.py:70-92, palette/network.py:131-153): a small 2-D hash grid over the sphere
+    coordinates of sph_from_ray and a bias-free MLP over [encoder_dir(d), encoder_bg(x)].  bg_radius <= 0: nothing is built, bg_net is None."""
+    m._bg_fused = None
+    if m.bg_radius > 0:
+        m.num_layers_bg, m.hidden_dim_bg = num_layers_bg, hidden_dim_bg
+        m.encoder_bg, m.in_dim_bg = get_encoder(encoding_bg, input_dim=2, num_levels=4, log2_hashmap_size=19, desired_resolution=2048)
+        m.bg_net = _mlp([m.in_dim_bg + m.in_dim_dir] + [hidden_dim_bg] * (num_layers_bg - 1) + [3])
+    else:
+        m.bg_net = None
+
+
+def _background_fused_ok(m, x, d):
+    """Inference batches on a HIP device (no gradient; fp32, or autocast -- then the launch reads the half table as the frame loop does) of a model
+    that asked for fused kernels take the one-launch background (fused.BackgroundFused); everything else the per-op formulation."""
+    if torch.is_grad_enabled() or not (x.is_cuda and d.is_cuda) or not (bool(m.fused_field) or m.march_mode == "native"):
+        return False
+    if x.dtype != torch.float32 or d.dtype != torch.float32 or x.shape[-1] != 2 or d.shape[-1] != 3:
+        return False
+    from .fused import background_fused
+    return background_fused(m) is not None
+
+
+def _background(m, x, d):
+    """nerf/network.py:145-160 = palette/network.py:205-220.  x [N,2] in [-1,1] (sph_from_ray), d [N,3] unit -> rgb [N,3]."""
+    if _background_fused_ok(m, x, d):
+        from .fused import background_fused
+        return background_fused(m).from_coords(x, d)
+    h = m.encoder_bg(x)                                    # default bound = 1
+    h = torch.cat([m.encoder_dir(d), h], dim=-1)           # the direction features come first
+    for l in range(m.num_layers_bg):
+        h = m.bg_net[l](h)
+        if l != m.num_layers_bg - 1:
+            h = F.relu(h, inplace=True)
+    return torch.sigmoid(h)
+
+
 class NeRFNetwork(NeRFRenderer):
     def __init__(self, encoding="hashgrid", encoding_dir="sphere_harmonics", num_layers=2, hidden_dim=64, geo_feat_dim=15,
-                 num_layers_color=3, hidden_dim_color=64, bound=1, **kwargs):
+                 num_layers_color=3, hidden_dim_color=64, bound=1, encoding_bg="hashgrid", num_layers_bg=2, hidden_dim_bg=64, **kwargs):
         super().__init__(bound, **kwargs)
-        if self.bg_radius > 0:
-            raise NotImplementedError("background model (bg_radius > 0) is out of scope: every shipped scene config sets bg_radius=0")
         self.num_layers, self.hidden_dim, self.geo_feat_dim = num_layers, hidden_dim, geo_feat_dim
         self.num_layers_color, self.hidden_dim_color = num_layers_color, hidden_dim_color
         self.encoder, self.in_dim = get_encoder(encoding, desired_resolution=2048 * bound)
         self.sigma_net = _mlp([self.in_dim] + [hidden_dim] * (num_layers - 1) + [1 + geo_feat_dim])
         self.encoder_dir, self.in_dim_dir = get_encoder(encoding_dir)
         self.color_net = _mlp([self.in_dim_dir + geo_feat_dim] + [hidden_dim_color] * (num_layers_color - 1) + [3])
-        self.bg_net = None
+        _build_background(self, encoding_bg, num_layers_bg, hidden_dim_bg)
         self.fused_field = False  # True: inference batches go through the fused MFMA field kernel (fp32, no autograd)
         self._fused = None
 
@@ -121,18 +156,23 @@ class NeRFNetwork(NeRFRenderer):
         rgbs[mask] = h.to(rgbs.dtype)
         return rgbs
 
+    def background(self, x, d):
+        return _background(self, x, d)
+
     def get_params(self, lr):
         """nerf/network.py:186-206"""
-        return [{"params": self.encoder.parameters(), "lr": lr}, {"params": self.sigma_net.parameters(), "lr": lr},
-                {"params": self.encoder_dir.parameters(), "lr": lr}, {"params": self.color_net.parameters(), "lr": lr}]
+        params = [{"params": self.encoder.parameters(), "lr": lr}, {"params": self.sigma_net.parameters(), "lr": lr},
+                  {"params": self.encoder_dir.parameters(), "lr": lr}, {"params": self.color_net.parameters(), "lr": lr}]
+        if self.bg_radius > 0:
+            params.append({"params": self.encoder_bg.parameters(), "lr": lr})
+            params.append({"params": self.bg_net.parameters(), "lr": lr})
+        return params
 
 
 class PaletteNetwork(PaletteRenderer):
     def __init__(self, opt, encoding="hashgrid", encoding_dir="sphere_harmonics", num_layers=2, hidden_dim=64, geo_feat_dim=15,
-                 num_layers_color=3, hidden_dim_color=64, bound=1, **kwargs):
+                 num_layers_color=3, hidden_dim_color=64, bound=1, encoding_bg="hashgrid", num_layers_bg=2, hidden_dim_bg=64, **kwargs):
         super().__init__(opt, bound, **kwargs)
-        if self.bg_radius > 0:
-            raise NotImplementedError("background model (bg_radius > 0) is out of scope: every shipped scene config sets bg_radius=0")
         self.num_layers, self.hidden_dim, self.geo_feat_dim = num_layers, hidden_dim, geo_feat_dim
         self.num_layers_color, self.hidden_dim_color = num_layers_color, hidden_dim_color
         self.encoder, self.in_dim = get_encoder(encoding, desired_resolution=2048 * bound)
@@ -149,7 +189,7 @@ class PaletteNetwork(PaletteRenderer):
         self.omega_net = nn.Sequential(Linear(geo_feat_dim, self.num_basis, bias=False), nn.Softplus())
         if opt.pred_clip:
             self.clip_net = _mlp([self.in_dim_clip] + [hidden_dim] * (num_layers - 1) + [opt.clip_dim])
-        self.bg_net = None
+        _build_background(self, encoding_bg, num_layers_bg, hidden_dim_bg)
         self.fused_field = False  # True: inference goes through the fused palette field + packed-aux composite (no edit / stylizer)
         self._fused = None
 
@@ -209,6 +249,9 @@ class PaletteNetwork(PaletteRenderer):
             omega = omega / omega.sum(dim=-1, keepdim=True)
         return omega, offsets_radiance, view_dep, diffuse
 
+    def background(self, x, d):
+        return _background(self, x, d)
+
     def get_params(self, lr):
         """palette/network.py:283-308 -- basis_net (and clip_net unless pred_clip) are deliberately absent (quirk 8)."""
         params = [{"params": m.parameters(), "lr": lr} for m in
@@ -217,6 +260,9 @@ class PaletteNetwork(PaletteRenderer):
         params.append({"params": self.basis_color, "lr": lr})
         if self.opt.use_initialization_from_rgbxy and hasattr(self, "hist_weights"):
             params.append({"params": self.hist_weights, "lr": lr})
+        if self.bg_radius > 0:
+            params.append({"params": self.encoder_bg.parameters(), "lr": lr})
+            params.append({"params": self.bg_net.parameters(), "lr": lr})
         if self.opt.pred_clip:
             params.append({"params": self.clip_net.parameters(), "lr": lr})
         return params

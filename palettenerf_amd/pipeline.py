@@ -20,7 +20,7 @@ _FUSED_SETTINGS = ("precision", "table_half", "interleave_tables", "stand_alone_
 
 def clone_for_concurrent_frames(model):
     """A second handle on `model`'s weights for another host thread: parameters, buffers and sub-modules are shared (nothing is
-    copied), the fused-field object -- workspace, packed-weight blob, interleaved tables -- is its own.  Plain attributes (edit,
+    copied), the fused-field object -- workspace, packed-weight blob, interleaved tables -- and the background's (fused.BackgroundFused) are its own.  Plain attributes (edit,
     stylizer, offsets_weight, density_scale, ...) are snapshots of the moment: FramesInFlight.render re-syncs them from the model
     before every run (sync_twin), and the model keeps a weak list of its twins so that invalidate_fused_caches reaches their blobs."""
     import weakref
@@ -30,6 +30,10 @@ def clone_for_concurrent_frames(model):
     twin = copy.copy(model)                 # shallow: the same Parameter / buffer tensors
     twin.__dict__.pop("_fused_twins", None)
     twin._fused = type(fused)(twin)
+    twin.__dict__.pop("_bg_fused", None)    # the background's blob and half table are per handle too (each handle enqueues on its own stream); made on first use
+    if "background" in twin.__dict__:       # dropin.fuse_field bound the model's background over the MODEL's BackgroundFused: the twin's goes over its own
+        from .dropin import bind_background
+        bind_background(twin)
     for name in _FUSED_SETTINGS:
         if hasattr(fused, name):
             setattr(twin._fused, name, getattr(fused, name))
@@ -40,9 +44,9 @@ def clone_for_concurrent_frames(model):
 def sync_twin(model, twin):
     """Bring a twin's plain attributes up to date with the model's (everything but its own fused-field object and its private caches):
     `model.edit = RegionEdit(...)`, a changed offsets_weight or density_scale after the clone would otherwise be shadowed by the snapshot."""
-    keep = {k: twin.__dict__[k] for k in ("_fused", "_density_fused", "_occ_ws", "_occ_blob") if k in twin.__dict__}
+    keep = {k: twin.__dict__[k] for k in ("_fused", "_density_fused", "_bg_fused", "background", "_occ_ws", "_occ_blob") if k in twin.__dict__}
     for k, v in model.__dict__.items():
-        if k not in ("_fused", "_density_fused", "_occ_ws", "_occ_blob", "_fused_twins"):
+        if k not in ("_fused", "_density_fused", "_bg_fused", "background", "_occ_ws", "_occ_blob", "_fused_twins"):
             twin.__dict__[k] = v
     for k in list(twin.__dict__):
         if k not in model.__dict__ and k not in keep:

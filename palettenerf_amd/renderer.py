@@ -272,6 +272,18 @@ class _RendererBase(nn.Module):
         self.invalidate_fused_caches()
         return out
 
+    def _background_of_rays(self, rays_o, rays_d):
+        """bg_radius > 0: the per-ray background colour [N,3] (nerf/renderer.py:270-273).  Inference frames on the fused paths take one launch for
+        sph_from_ray + background() (fused.BackgroundFused.from_rays: the same coordinates, bit for bit); everything else the two calls."""
+        bg = self.__dict__.get("background")       # an instance attribute (dropin.fuse_field) decides for itself
+        if bg is None and not torch.is_grad_enabled() and rays_o.is_cuda and rays_o.dtype == torch.float32 and rays_d.dtype == torch.float32 \
+                and (bool(getattr(self, "fused_field", False)) or self.march_mode == "native"):
+            from .fused import background_fused
+            fused = background_fused(self)
+            if fused is not None:
+                return fused.from_rays(rays_o, rays_d)
+        return self.background(raymarching.sph_from_ray(rays_o, rays_d, self.bg_radius), rays_d)
+
     def reset_extra_state(self):
         if not self.cuda_ray:
             return
@@ -333,12 +345,20 @@ class _RendererBase(nn.Module):
         # (a frame prepared again keeps the jitter it drew: a second torch.rand would give the queued frame another noise than render() under the same seed)
         again = dict(kwargs, noises=pending.tok.noises)
         pending.redo = lambda: self.render_prepare(rays_o, rays_d, **again)
+        # bg_radius > 0: the frame's per-ray background was computed (enqueued) above, on the stream that is current NOW, from the background weights as they
+        # are now.  render_launch enqueues the frame on the stream current THEN and nothing orders two streams: with a background, prepare and launch must
+        # share a stream (the frame queue, pipeline.render_queue and FramesInFlight do).  The token keeps the [N,3] tensor (keep=); the weight blob and the
+        # half table are only read by a launch that is already enqueued, so the stream-ordered allocator keeps them for it.
+        bg = self.__dict__.get("_bg_fused") if self.bg_radius > 0 else None
+        pending.bg = None if bg is None else (bg, bg.state())
         return pending
 
     def render_launch(self, pending):
         """Enqueue a prepared frame; returns the pending frame to finish (a NEW one when the model's blobs were rebuilt since render_prepare -- a frame in
         front of it found its sources rewritten -- and the frame had to be prepared again)."""
         from .fused import StaleFrame
+        if pending.bg is not None and pending.bg[0].state() != pending.bg[1]:   # the background weights changed since render_prepare: its bg_map is stale
+            pending = pending.redo()
         try:
             pending.fused.frame_launch(pending.tok)
         except StaleFrame:
@@ -385,10 +405,10 @@ class _RendererBase(nn.Module):
 
 class PendingFrame:
     """A native-loop frame between render_prepare and render_finish (fused.py: frame_prepare / frame_launch / frame_finish)."""
-    __slots__ = ("fused", "tok", "complete", "redo")
+    __slots__ = ("fused", "tok", "complete", "redo", "bg")
 
     def __init__(self, fused, tok, complete):
-        self.fused, self.tok, self.complete, self.redo = fused, tok, complete, None
+        self.fused, self.tok, self.complete, self.redo, self.bg = fused, tok, complete, None, None
 
 
 def _frame_noises(perturb, noises, N, rays_o):
@@ -512,8 +532,7 @@ class NeRFRenderer(_OccupancyMaintenance, _RendererBase):
         native_frame = not self.training and self.march_mode == "native" and rays_o.is_cuda and aabb.is_cuda
         nears, fars = (None, None) if native_frame else raymarching.near_far_from_aabb(rays_o, rays_d, aabb, self.min_near)
         if self.bg_radius > 0:
-            sph = raymarching.sph_from_ray(rays_o, rays_d, self.bg_radius)
-            bg_color = self.background(sph, rays_d)
+            bg_color = self._background_of_rays(rays_o, rays_d)
         elif bg_color is None:
             bg_color = 1
         results = {}
@@ -756,8 +775,7 @@ class PaletteRenderer(_RendererBase):
         native_near_far = native and rays_o.is_cuda and aabb.is_cuda
         nears, fars = (None, None) if native_near_far else raymarching.near_far_from_aabb(rays_o, rays_d, aabb, self.min_near)
         if self.bg_radius > 0:
-            sph = raymarching.sph_from_ray(rays_o, rays_d, self.bg_radius)
-            bg_color = self.background(sph, rays_d)
+            bg_color = self._background_of_rays(rays_o, rays_d)
         elif bg_color is None:
             bg_color = 1
         results = {}

@@ -1,0 +1,521 @@
+"""The background model (bg_radius > 0) on the GPU: the one-launch kernel (pnr_background_forward), native frames of both models against the
+reference's own frames (tests/golden/gen_golden_background.py), the -O mode, the cache life cycle, fuse_field, checkpoints and training gradients.
+
+Tolerances.
+  * COLOUR_TOL = DEPTH_TOL = 1e-4: the project's contract (tests/test_gpu_frames.py), on every stored map.  The fixtures' background tables are scaled
+    by 2^-2 so that the device's sphere coordinates (within 2e-6 of the host's, tests/test_gpu_ops.py) move a colour by at most a quarter of it.
+  * KERNEL_TOL = max(1e-5, 4 x E) with E the error of the per-op background() formulation (GridEncoder, SHEncoder, hipBLASLt GEMMs, fp32) against the
+    same float64 evaluation at the same device coordinates: E measured 6.4e-8 on the MI355X (the kernel itself: 6.4e-8; fused against per-op on 800x800 rays: 6.0e-8), so KERNEL_TOL = 1e-5.
+  * FP16_TOL = max(1e-4, 4 x the fp32 native frame's error against its golden): that error measured 4.3e-6 (image; the -O frame against its own golden: 5.7e-6),
+    so FP16_TOL = 1e-4.  The fp32 frames of both models are within 1.0e-6 of their goldens on `image`.
+  * GRAD_TOL = 4e-5 of the largest entry: the worst figure profiles/r05_grad_tolerance.txt reports for the same operators (table gradient, dense layers)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import oracle
+from oracle.torch_encoders import TorchSHEncoder
+from palettenerf_amd import _lib, checkpoint, dropin, network, pipeline, raymarching, renderer, scene
+from palettenerf_amd.fused import BackgroundFused, background_fused, tile_ray_order
+
+pytestmark = pytest.mark.gpu
+
+COLOUR_TOL = 1e-4
+DEPTH_TOL = 1e-4
+KERNEL_TOL = 1e-5
+FP16_TOL = 1e-4
+GRAD_TOL = 4e-5
+NERF_KEYS = ["image", "depth", "weights_sum"]
+FULL_KEYS = ["image", "depth", "depth_origin", "weights_sum", "clip_feat", "direct_rgb", "view_dep_rgb", "basis_rgb", "unscaled_basis_rgb", "basis_acc"]
+KW = dict(max_steps=1024, T_thresh=1e-4)
+
+
+def make_model(kind, cuda, seed, density_scale, pred_clip=False, bg_scale=0.25, main_scale=1.0, bg_radius=4):
+    if kind == "nerf":
+        m = network.NeRFNetwork(bound=2, cuda_ray=True, density_scale=density_scale, min_near=0.2, bg_radius=bg_radius)
+    else:
+        m = network.PaletteNetwork(renderer.default_opt(pred_clip=pred_clip), bound=2, cuda_ray=True, density_scale=density_scale, min_near=0.2, bg_radius=bg_radius)
+    scene.seed_field_(m, seed)
+    with torch.no_grad():
+        m.encoder_bg.embeddings.mul_(bg_scale)
+        if main_scale != 1.0:
+            for e in (m.encoder, m.encoder_palette, m.encoder_clip):
+                e.embeddings.mul_(main_scale)
+    m = m.to(cuda).eval()
+    m.density_grid.copy_(torch.from_numpy(scene.brick_density_grid()).to(cuda))
+    raymarching.packbits(m.density_grid, 0.5, m.density_bitfield)
+    m.march_mode, m.fused_field, m.count_rendered = "native", True, True
+    return m
+
+
+def golden(golden_dir, name):
+    return np.load(os.path.join(golden_dir, name + ".npz"))
+
+
+def golden_model(kind, cuda, g, **kw):
+    assert int(g["bound"]) == 2 and int(g["bg_radius"]) == 4
+    return make_model(kind, cuda, int(g["seed"]), float(g["density_scale"]), bool(g["pred_clip"]) if kind == "palette" else False, float(g["bg_scale"]), **kw)
+
+
+def frame_rays(cuda, H, W, azimuth=45.0):
+    pose = torch.from_numpy(scene.lookat_pose(azimuth_deg=azimuth))[None]
+    ro, rd = scene.get_rays(pose, scene.intrinsics_from_fov(H, W), H, W)
+    return ro.to(cuda), rd.to(cuda)
+
+
+def gui(kind, on=False):
+    return {"gui_mode": on} if kind == "palette" else {}
+
+
+def err_of(got, want):
+    got = torch.as_tensor(got).detach().float().cpu().numpy().reshape(np.shape(want))
+    fin = np.isfinite(want)
+    assert np.array_equal(np.isfinite(got), fin)
+    return float(np.abs(got[fin] - want[fin]).max()) if fin.any() else 0.0
+
+
+def close(got, want, tol, what):
+    err = err_of(got, want)
+    print(f"{what}: max abs err {err:.3g}")
+    assert err <= tol, f"{what}: max abs err {err}"
+    return err
+
+
+def same(a, b, what="", min_maps=3):
+    n = 0
+    for k, v in a.items():
+        if torch.is_tensor(v) and v.dtype.is_floating_point and v.numel() > 1:
+            assert torch.equal(torch.nan_to_num(v, nan=-7.0), torch.nan_to_num(b[k], nan=-7.0)), (what, k)
+            n += 1
+    assert n >= min_maps, what
+
+
+def tol_of(k):
+    return DEPTH_TOL if k.startswith("depth") else COLOUR_TOL
+
+
+def rays_outside_in(cuda, n, seed=0):
+    """Origins inside the background sphere (radius 4), unit directions all over it."""
+    g = torch.Generator().manual_seed(seed)
+    o = (torch.rand(n, 3, generator=g) * 2 - 1) * 1.5
+    d = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1)
+    return o.to(cuda), d.to(cuda)
+
+
+def background_f64(m, coords, d):
+    """oracle.grid_encode_forward + oracle.sh_encode_forward (their own fp32 arithmetic) + float64 dense layers, at the given coordinates."""
+    e = m.encoder_bg
+    x01 = ((coords + np.float32(1)) / np.float32(2)).astype(np.float32)
+    enc = oracle.grid_encode_forward(x01, e.embeddings.detach().cpu().numpy(), e.offsets.cpu().numpy(), float(e.per_level_scale), e.base_resolution)
+    sh = oracle.sh_encode_forward(d, 4)
+    h = np.concatenate([sh, enc], axis=-1).astype(np.float64)
+    h = np.maximum(h @ m.bg_net[0].weight.detach().cpu().numpy().astype(np.float64).T, 0)
+    h = h @ m.bg_net[1].weight.detach().cpu().numpy().astype(np.float64).T
+    return 1.0 / (1.0 + np.exp(-h))
+
+
+# ---------------------------------------------------------------- 1. the kernel
+def test_coords_out_is_sph_from_ray_bit_for_bit(cuda):
+    m = make_model("nerf", cuda, 3, 1.0)
+    o, d = rays_outside_in(cuda, 40_003)
+    rgb, coords = background_fused(m).from_rays(o, d, want_coords=True)
+    want = raymarching.sph_from_ray(o, d, m.bg_radius)
+    assert torch.equal(coords, want) and torch.isfinite(coords).all()
+    assert float(coords.min()) < -0.9 and float(coords.max()) > 0.9            # the whole sphere
+    again = background_fused(m).from_coords(want, d)                            # background(x, d)'s form of the launch: the same colours
+    assert torch.equal(rgb, again)
+
+
+@pytest.mark.parametrize("bg_scale", [1.0, 0.25])
+def test_kernel_arithmetic_against_the_oracle_and_float64_layers(cuda, bg_scale):
+    m = make_model("nerf", cuda, 4, 1.0, bg_scale=bg_scale)
+    o, d = rays_outside_in(cuda, 30_011, seed=1)
+    rgb, coords = background_fused(m).from_rays(o, d, want_coords=True)
+    want = background_f64(m, coords.cpu().numpy(), d.cpu().numpy())
+    m.fused_field, m.march_mode = False, "compat"
+    with torch.no_grad():
+        per_op = m.background(coords, d)
+    e_fused, e_per_op = err_of(rgb, want), err_of(per_op, want)
+    print(f"bg_scale {bg_scale}: fused vs float64 {e_fused:.3g}, per-op vs float64 {e_per_op:.3g}")
+    assert float(np.ptp(want)) > 0.05                                           # the colours vary: not a constant compared with a constant
+    assert e_fused <= KERNEL_TOL and KERNEL_TOL >= 4 * e_per_op
+
+
+def test_fused_equals_per_op_background_on_a_full_frame(cuda):
+    m = make_model("palette", cuda, 6, 1.0, bg_scale=1.0)
+    ro, rd = frame_rays(cuda, 800, 800)
+    ro, rd = ro.view(-1, 3), rd.view(-1, 3)
+    with torch.no_grad():
+        sph = raymarching.sph_from_ray(ro, rd, m.bg_radius)
+        fused = m.background(sph, rd)
+        one = m._background_of_rays(ro, rd)
+        m.fused_field, m.march_mode = False, "compat"
+        per_op = m.background(sph, rd)
+    assert torch.equal(fused, one)
+    err = float((fused - per_op).abs().max())
+    print(f"800x800: fused vs per-op {err:.3g}")
+    assert err <= KERNEL_TOL and float(per_op.std()) > 0.01
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):          # -O: the half table, the reference's half interpolation
+        m.march_mode = "native"
+        half = m._background_of_rays(ro, rd)
+    enc = m.encoder_bg
+    x01 = ((sph + 1) / 2).contiguous()
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+        feat = enc(sph).float()
+    h = torch.cat([m.encoder_dir(rd), feat], dim=-1)
+    want = torch.sigmoid(torch.relu(h @ m.bg_net[0].weight.T) @ m.bg_net[1].weight.T)
+    assert half.dtype == torch.float32 and float((half - want).abs().max()) <= KERNEL_TOL
+    assert float((half - fused).abs().max()) > 1e-5 and x01.shape[0] == 640000   # the half table was really read
+
+
+# ---------------------------------------------------------------- 2. native frames against the reference's
+@pytest.mark.parametrize("case", ["a", "b"])
+@pytest.mark.parametrize("kind", ["nerf", "palette"])
+def test_native_frame_with_background_matches_the_reference(cuda, golden_dir, kind, case):
+    g = golden(golden_dir, f"frame_bg_{kind}_{case}")
+    m = golden_model(kind, cuda, g)
+    ro, rd = frame_rays(cuda, int(g["H"]), int(g["W"]))
+    keys = NERF_KEYS if kind == "nerf" else FULL_KEYS
+    kw = dict(dt_gamma=float(g["dt_gamma"]), perturb=False, **gui(kind), **KW)
+    with torch.no_grad():
+        r = m.render(ro, rd, **kw)
+    assert "iterations" in r and m.__dict__.get("_bg_fused") is not None          # the native loop, the fused background
+    for k in keys:
+        close(r[k], g[k], tol_of(k), f"{kind} {case} {k}")
+    # not a frame without the model's background, nor one that ignored its table
+    m.bg_radius = 0
+    with torch.no_grad():
+        white = m.render(ro, rd, bg_color=1, **kw)
+    m.bg_radius = 4
+    assert err_of(white["image"], g["image"]) > 10 * COLOUR_TOL
+    # the per-op loop computes the same frame
+    m.march_mode, m.fused_field = "compat", False
+    with torch.no_grad():
+        c = m.render(ro, rd, **kw)
+    assert "iterations" not in c
+    for k in keys:
+        close(r[k], c[k].cpu().numpy(), tol_of(k), f"{kind} {case} native vs per-op {k}")
+    # staged rendering is a no-op for cuda_ray models, with or without a background
+    m.march_mode, m.fused_field = "native", True
+    with torch.no_grad():
+        same(m.render(ro, rd, staged=True, **kw), r, "staged")
+
+
+@pytest.mark.parametrize("kind", ["nerf", "palette"])
+def test_ray_sorted_queue_and_jittered_frames(cuda, kind):
+    from palettenerf_amd.fused import NeRFFieldFused, PaletteFieldFused
+    m = make_model(kind, cuda, 5, 30.0)
+    m._fused = (NeRFFieldFused if kind == "nerf" else PaletteFieldFused)(m)
+    H, W = 40, 56
+    kw = dict(dt_gamma=1.0 / 128, **gui(kind), **KW)
+    frames = [frame_rays(cuda, H, W, azimuth=20.0 + 50.0 * i) for i in range(4)]
+    noises = torch.rand(H * W, generator=torch.Generator().manual_seed(4)).to(cuda)
+    with torch.no_grad():
+        want = [m.render(ro, rd, perturb=False, **kw) for ro, rd in frames]
+        jit = m.render(*frames[0], perturb=False, noises=noises, **kw)
+        m._fused.ray_order = tile_ray_order(torch.arange(H * W), W, 8).to(cuda)
+        same(m.render(*frames[0], perturb=False, **kw), want[0], "tile order")
+        same(m.render(*frames[0], perturb=False, noises=noises, **kw), jit, "tile order, jittered")
+        m._fused.ray_order = None
+    assert float((jit["image"] - want[0]["image"]).abs().max()) > 2 * COLOUR_TOL
+    m.bg_radius = 0
+    with torch.no_grad():
+        assert float((m.render(*frames[0], perturb=False, noises=noises, bg_color=1, **kw)["image"] - jit["image"]).abs().max()) > 10 * COLOUR_TOL
+    m.bg_radius = 4
+    got = pipeline.render_queue(m, lambda i: frames[i], len(frames), perturb=False, **kw)
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert "iterations" in a
+        same(a, b, f"queue frame {i}")
+
+
+# ---------------------------------------------------------------- 3. -O
+def test_fp16_autocast_frame_matches_the_reference_half_frame(cuda, golden_dir):
+    g = golden(golden_dir, "frame_bg_palette_fp16_a")
+    m = golden_model("palette", cuda, g, main_scale=float(g["main_scale"]))
+    ro, rd = frame_rays(cuda, int(g["H"]), int(g["W"]))
+    kw = dict(dt_gamma=float(g["dt_gamma"]), perturb=False, gui_mode=False, **KW)
+    with torch.no_grad():
+        full = m.render(ro, rd, **kw)
+    e32 = max(close(full[k], g[f"fp32_{k}"], tol_of(k), f"fp32 {k}") for k in FULL_KEYS)
+    print(f"fp32 native frame against its golden: {e32:.3g}")
+    assert FP16_TOL >= 4 * e32
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+        r = m.render(ro, rd, **kw)
+    assert "iterations" in r and r["image"].dtype == torch.float32
+    for k in FULL_KEYS:
+        close(r[k], g[f"half_{k}"], FP16_TOL, f"-O {k}")
+    assert err_of(r["image"], g["fp32_image"]) > 10 * FP16_TOL                  # the half tables were really used
+    assert background_fused(m)._emb_half is not None
+
+
+# ---------------------------------------------------------------- 4. cache life cycle
+def test_cache_life_cycle(cuda):
+    m = make_model("nerf", cuda, 8, 1.0)
+    ro, rd = frame_rays(cuda, 32, 32)
+    kw = dict(dt_gamma=0.0, perturb=False, **KW)
+    bgf = background_fused(m)
+
+    def frame():
+        with torch.no_grad():
+            return m.render(ro, rd, **kw)["image"].clone()
+
+    def expected():
+        m.march_mode, m.fused_field = "compat", False
+        try:
+            with torch.no_grad():
+                return m.render(ro, rd, **kw)["image"].clone()
+        finally:
+            m.march_mode, m.fused_field = "native", True
+
+    first = frame()
+    blob0 = bgf._blob[1]
+    # a write through .data moves no version counter: invalidate_fused_caches() is the rule
+    m.bg_net[1].weight.data.mul_(-1.5)
+    m.invalidate_fused_caches()
+    second = frame()
+    assert bgf._blob[1] is not blob0                                            # a repack goes into a new tensor
+    assert float((second - first).abs().max()) > 10 * COLOUR_TOL and float((second - expected()).abs().max()) <= COLOUR_TOL
+    # an optimiser step moves the version counters
+    opt = torch.optim.SGD(list(m.bg_net.parameters()) + [m.encoder_bg.embeddings], lr=0.5)
+    for p in opt.param_groups[0]["params"]:
+        p.grad = torch.randn_like(p) * 0.5
+    opt.step()
+    third = frame()
+    assert float((third - second).abs().max()) > 10 * COLOUR_TOL and float((third - expected()).abs().max()) <= COLOUR_TOL
+    # the -O copy of the table follows the table
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+        h1 = bgf.from_rays(ro.view(-1, 3), rd.view(-1, 3))
+        half0 = bgf._emb_half[1]
+        m.encoder_bg.embeddings.mul_(0.5)
+        h2 = bgf.from_rays(ro.view(-1, 3), rd.view(-1, 3))
+    assert bgf._emb_half[1] is not half0 and float((h1 - h2).abs().max()) > 1e-3
+    # a frame prepared before the weights changed is refused and prepared again
+    pend = m.render_prepare(ro, rd, **kw)
+    with torch.no_grad():
+        m.bg_net[0].weight.mul_(0.25)
+    fresh = m.render_launch(pend)
+    assert fresh is not pend
+    out = m.render_finish(fresh)["image"]
+    assert float((out - third).abs().max()) > 10 * COLOUR_TOL and float((out - expected()).abs().max()) <= COLOUR_TOL
+    pend = m.render_prepare(ro, rd, **kw)
+    assert m.render_launch(pend) is pend                                        # nothing changed: the prepared frame goes out
+    assert torch.equal(m.render_finish(pend)["image"], out)
+
+
+# ---------------------------------------------------------------- 5. fuse_field, checkpoints
+@pytest.mark.parametrize("kind", ["nerf", "palette"])
+def test_fuse_field_binds_the_background(cuda, kind):
+    m = make_model(kind, cuda, 9, 1.0)
+    m.march_mode, m.fused_field = "compat", False
+    o, d = rays_outside_in(cuda, 5000, seed=2)
+    sph = raymarching.sph_from_ray(o, d, m.bg_radius)
+    with torch.no_grad():
+        plain = m.background(sph, d)
+    dropin.fuse_field(m)
+    assert "background" in m.__dict__ and isinstance(m._bg_fused, BackgroundFused)
+    with torch.no_grad():
+        m.background(sph, d)                                                     # (the first call packs the weights)
+    calls = []
+    real = _lib.call
+    _lib.call = lambda name, *a: (calls.append(name), real(name, *a))[1]
+    try:
+        with torch.no_grad():
+            got = m.background(sph, d)
+    finally:
+        _lib.call = real
+    assert calls == ["pnr_background_forward"] and float((got - plain).abs().max()) <= KERNEL_TOL
+    g = m.background(sph, d)                                                     # under autograd: the model's own formulation
+    assert g.requires_grad and float((g - plain).abs().max()) <= KERNEL_TOL
+    no_bg = make_model(kind, cuda, 9, 1.0)
+    no_bg.bg_radius = 0
+    assert "background" not in dropin.fuse_field(no_bg).__dict__
+
+
+def test_checkpoint_round_trip_and_reference_named_state_dict(cuda, tmp_path):
+    src = make_model("palette", cuda, 11, 1.0)
+    ro, rd = frame_rays(cuda, 24, 24)
+    kw = dict(dt_gamma=0.0, perturb=False, gui_mode=False, **KW)
+    with torch.no_grad():
+        want = src.render(ro, rd, **kw)
+    path = checkpoint.save_model(src, str(tmp_path / "bg.pth"), epoch=3)
+    dst = make_model("palette", cuda, 12, 1.0, bg_scale=1.0)
+    with torch.no_grad():
+        assert float((dst.render(ro, rd, **kw)["image"] - want["image"]).abs().max()) > 10 * COLOUR_TOL      # (its blobs exist before the load)
+    info = checkpoint.load_model(dst, path, map_location=cuda)
+    assert not info["missing"] and not info["unexpected"]
+    with torch.no_grad():
+        same(dst.render(ro, rd, **kw), want, "after load")
+        with torch.autocast("cuda", dtype=torch.float16):
+            assert "iterations" in dst.render(ro, rd, **kw)
+    assert {"encoder_bg.embeddings", "encoder_bg.offsets", "bg_net.0.weight", "bg_net.1.weight"} <= set(torch.load(path, weights_only=False)["model"])
+
+
+# ---------------------------------------------------------------- 6. training
+class _Torch2DGrid(torch.nn.Module):
+    """encoder_bg with torch ops only, float64: the D = 2 form of oracle/torch_encoders.py's TorchGridEncoder (which is written for D = 3)."""
+
+    def __init__(self, enc):
+        super().__init__()
+        self.offs = enc.offsets.tolist()
+        scale, res = oracle.orc.grid_level_params(enc.num_levels, float(enc.per_level_scale), enc.base_resolution)
+        self.scale, self.res = [float(s) for s in scale], [int(r) for r in res]
+        self.embeddings = torch.nn.Parameter(enc.embeddings.detach().double().cpu())
+
+    def forward(self, x):
+        x = (x + 1) / 2
+        outs = []
+        for lv in range(len(self.res)):
+            size, side = self.offs[lv + 1] - self.offs[lv], self.res[lv] + 1
+            pos = x * self.scale[lv] + 0.5
+            pg = torch.floor(pos)
+            fr, pg = pos - pg, pg.to(torch.int64)
+            table = self.embeddings[self.offs[lv]:self.offs[lv + 1]]
+            acc = 0
+            for c in range(4):
+                bx, by = c & 1, c >> 1
+                w = (fr[:, 0] if bx else 1 - fr[:, 0]) * (fr[:, 1] if by else 1 - fr[:, 1])
+                ix, iy = pg[:, 0] + bx, pg[:, 1] + by
+                index = ix + iy * side if side * side <= size else (ix ^ ((iy * 2654435761) & 0xFFFFFFFF))
+                acc = acc + w[:, None] * table[index % size]
+            outs.append(acc)
+        return torch.cat(outs, -1)
+
+
+def test_training_gradients_of_the_background_against_torch_autograd(cuda):
+    m = make_model("nerf", cuda, 13, 1.0, bg_scale=1.0).train()
+    o, d = rays_outside_in(cuda, 8192, seed=3)
+    sph = raymarching.sph_from_ray(o, d, m.bg_radius)
+    weight = torch.rand(8192, 3, generator=torch.Generator().manual_seed(5)).to(cuda)
+    rgb = m.background(sph, d)
+    assert rgb.requires_grad
+    (rgb * weight).sum().backward()
+    grid, sh = _Torch2DGrid(m.encoder_bg), TorchSHEncoder(degree=4)
+    w0 = m.bg_net[0].weight.detach().double().cpu().requires_grad_(True)
+    w1 = m.bg_net[1].weight.detach().double().cpu().requires_grad_(True)
+    h = torch.cat([sh(d.cpu()).double(), grid(sph.double().cpu())], dim=-1)
+    ref = torch.sigmoid(torch.relu(h @ w0.T) @ w1.T)
+    (ref * weight.double().cpu()).sum().backward()
+    assert float((rgb.detach().double().cpu() - ref.detach()).abs().max()) <= KERNEL_TOL
+    for name, got, want in (("encoder_bg.embeddings", m.encoder_bg.embeddings.grad, grid.embeddings.grad), ("bg_net.0.weight", m.bg_net[0].weight.grad, w0.grad),
+                            ("bg_net.1.weight", m.bg_net[1].weight.grad, w1.grad)):
+        scale = float(want.abs().max())
+        rel = float((got.double().cpu() - want).abs().max()) / scale
+        print(f"{name}: rel err {rel:.3g} (max |g| {scale:.3g})")
+        assert scale > 0 and rel <= GRAD_TOL, name
+    # one training step of the whole model reaches the background's parameters through the image (train_loss's torch formulation)
+    m.zero_grad()
+    m.density_grid.copy_(torch.from_numpy(scene.brick_density_grid()).to(cuda))
+    ro, rd = frame_rays(cuda, 32, 32)
+    r = m.run_cuda(ro, rd, perturb=False, force_all_rays=True)
+    (r["image"] ** 2).mean().backward()
+    for p in (m.encoder_bg.embeddings, m.bg_net[0].weight, m.bg_net[1].weight):
+        assert p.grad is not None and float(p.grad.abs().sum()) > 0
+
+
+# ---------------------------------------------------------------- 7. the uniform-sampling path, both mirrors' checkpoints, shards, frames in flight
+@pytest.mark.parametrize("fused", [False, True])
+def test_uniform_sampling_path_with_background_matches_the_reference_run(cuda, golden_dir, fused):
+    """NeRFRenderer.run (cuda_ray=False) of a bg_radius > 0 model against the reference's own run() frame: fused=False is the per-op background()
+    (GridEncoder D = 2, SHEncoder, Linear -- HIP operators: there is no CPU form of them, so this is where the per-op formulation meets the reference),
+    fused=True the one-launch form behind background(x, d)."""
+    g = golden(golden_dir, "frame_bg_run_nerf_a")
+    m = network.NeRFNetwork(bound=2, cuda_ray=False, density_scale=float(g["density_scale"]), min_near=0.2, bg_radius=int(g["bg_radius"]))
+    scene.seed_field_(m, int(g["seed"]))
+    with torch.no_grad():
+        m.encoder_bg.embeddings.mul_(float(g["bg_scale"]))
+    m = m.to(cuda).eval()
+    m.fused_field = fused
+    ro, rd = frame_rays(cuda, int(g["H"]), int(g["W"]))
+    kw = dict(num_steps=int(g["num_steps"]), upsample_steps=int(g["upsample_steps"]), perturb=False)
+    calls = []
+    real = _lib.call
+    _lib.call = lambda name, *a: (calls.append(name), real(name, *a))[1]
+    try:
+        with torch.no_grad():
+            r = m.render(ro, rd, staged=True, max_ray_batch=4096, **kw)
+    finally:
+        _lib.call = real
+    assert ("pnr_background_forward" in calls) == fused
+    for k in NERF_KEYS:
+        close(r[k], g[k], tol_of(k), f"run fused={fused} {k}")
+    m.bg_radius = 0
+    with torch.no_grad():
+        white = m.render(ro, rd, staged=True, max_ray_batch=4096, bg_color=1, **kw)
+    assert err_of(white["image"], g["image"]) > 10 * COLOUR_TOL
+
+
+def test_nerf_checkpoint_round_trip_and_bare_reference_named_state_dict(cuda, tmp_path):
+    src = make_model("nerf", cuda, 14, 1.0)
+    ro, rd = frame_rays(cuda, 24, 24)
+    kw = dict(dt_gamma=0.0, perturb=False, **KW)
+    with torch.no_grad():
+        want = src.render(ro, rd, **kw)
+    path = checkpoint.save_model(src, str(tmp_path / "bg_nerf.pth"), epoch=1)
+    bare = str(tmp_path / "bare.pth")
+    torch.save({k: v.cpu() for k, v in src.state_dict().items()}, bare)          # a bare state_dict under the reference's names
+    for file in (path, bare):
+        dst = make_model("nerf", cuda, 15, 1.0, bg_scale=1.0)
+        with torch.no_grad():
+            assert float((dst.render(ro, rd, **kw)["image"] - want["image"]).abs().max()) > 10 * COLOUR_TOL
+        info = checkpoint.load_model(dst, file, map_location=cuda)
+        assert not info["missing"] and not info["unexpected"]
+        with torch.no_grad():
+            same(dst.render(ro, rd, **kw), want, file)
+            with torch.autocast("cuda", dtype=torch.float16):
+                assert "iterations" in dst.render(ro, rd, **kw)
+
+
+@pytest.mark.parametrize("kind", ["nerf", "palette"])
+def test_tile_shards_of_a_frame_with_background_equal_the_frame(cuda, kind):
+    from palettenerf_amd import dist as pdist
+    m = make_model(kind, cuda, 16, 1.0)
+    H, W, world = 48, 64, 3
+    ro, rd = frame_rays(cuda, H, W)
+    kw = dict(dt_gamma=0.0, perturb=False, **gui(kind), **KW)
+    with torch.no_grad():
+        full = m.render(ro, rd, **kw)
+    image = torch.full((H * W, 3), float("nan"), device=cuda)
+    for rank in range(world):
+        idx, _ = pdist.shard_indices(H, W, rank, world)
+        idx = idx.to(cuda)
+        with torch.no_grad():
+            part = m.render(ro[:, idx].contiguous(), rd[:, idx].contiguous(), **kw)
+        assert "iterations" in part
+        image[idx] = part["image"].view(-1, 3)
+    assert torch.equal(torch.nan_to_num(image, nan=-7.0), torch.nan_to_num(full["image"].view(-1, 3), nan=-7.0))
+
+
+@pytest.mark.parametrize("kind", ["nerf", "palette"])
+def test_frames_in_flight_with_background(cuda, kind):
+    """Three handles on three threads and streams: each has its own BackgroundFused (blob, half table), and a weight change between two passes
+    reaches all of them."""
+    from palettenerf_amd.fused import NeRFFieldFused, PaletteFieldFused
+    from palettenerf_amd.pipeline import FramesInFlight
+    m = make_model(kind, cuda, 17, 1.0)
+    m._fused = (NeRFFieldFused if kind == "nerf" else PaletteFieldFused)(m)
+    H = W = 96
+    rays = [frame_rays(cuda, H, W, azimuth=20.0 + 23.0 * i) for i in range(6)]
+    kw = dict(dt_gamma=0.0, perturb=False, **gui(kind), **KW)
+    fif = FramesInFlight(m, 3)
+    try:
+        for step in range(3):
+            with torch.no_grad():
+                want = [m.render(ro, rd, **kw) for ro, rd in rays]
+            got = fif.render(lambda i: rays[i], len(rays), **kw)
+            for i, (a, b) in enumerate(zip(got, want)):
+                same(a, b, f"pass {step} frame {i}")
+            owners = [h.__dict__.get("_bg_fused") for h in fif.models]
+            assert all(isinstance(o, BackgroundFused) for o in owners) and len({id(o) for o in owners}) == 3
+            assert len({o._blob[1].data_ptr() for o in owners}) == 3
+            before = want[0]["image"].clone()
+            with torch.no_grad():
+                if step == 0:
+                    m.bg_net[1].weight.mul_(-1.25)                 # the version counter moves
+                else:
+                    m.bg_net[0].weight.data.mul_(0.5)              # it does not: invalidate_fused_caches reaches every handle
+                    m.invalidate_fused_caches()
+                assert float((m.render(*rays[0], **kw)["image"] - before).abs().max()) > 10 * COLOUR_TOL
+    finally:
+        fif.close()
