@@ -683,6 +683,32 @@ int pnr_palette_train_shade_backward(uint32_t M, uint32_t num_basis, uint32_t cl
                                      float* grad_clip_feat, float* grad_smooth_norm, float* grad_basis_color, void* workspace,
                                      uint64_t workspace_bytes, pnr_stream_t stream);
 
+/* The smooth-loss block of a training step (palette/renderer.py:360-378; every step from smooth_loss_start_epoch on) as one launch for the
+ * perturbed points, one for the bilateral weight and the norm, one for the gradient (replaces ~25-30 torch launches each way; additive
+ * entries, the ABI version does not change).  All arrays fp32, row-major.
+ *   pnr_palette_smooth_points: xyzs [M,3], noise [M,3] (torch.rand_like) -> xyzs_diff [M,3] = clamp(xyzs + noise * bound * 0.03, -bound, bound),
+ *     evaluated in torch's order (noise * bound, * 0.03f, the add, the clamp; no contraction): the same bits as the torch expression (:362).
+ *   pnr_palette_smooth_forward: xyzs / xyzs_diff [M,3], diffuse / diffuse_diff [M,3], omega / omega_diff [M,nb], clip_feat / clip_feat_diff
+ *     [M,clip_dim] or both NULL (no clip head: opt.pred_clip off) -> smooth_weight [M] (kept for the backward), smooth_norm [M]:
+ *       xw = |xyzs - xyzs_diff|^2 / bound^2 / sigma_xyz          rw = |diffuse - diffuse_diff|^2 / sigma_color               (:368-369)
+ *       cw = |clip_feat - clip_feat_diff| / sigma_clip with a clip head and sigma_clip > 0, else 0 -- the norm, NOT its square (:370-373)
+ *       smooth_weight = exp(-xw - rw - cw)                                                                                    (:375, detached)
+ *       smooth_norm   = smooth_weight (sum_b (omega_diff_b - omega_b)^2 + sum_c (clip_feat_diff_c - clip_feat_c)^2)           (:376-378)
+ *     the clip sum is added whenever a clip head is given, whether or not sigma_clip > 0 (:377).
+ *   pnr_palette_smooth_backward: grad_smooth_norm [M], smooth_weight, the omega and clip pairs ->
+ *       grad_omega_diff = 2 g w (omega_diff - omega), grad_omega = -grad_omega_diff, and the same pair for the clip feature (grad_clip_feat /
+ *       grad_clip_feat_diff may each be NULL: not wanted).  The weight is detached: nothing reaches xyzs, diffuse or diffuse_diff.
+ * 1 <= nb <= 16 and clip_dim <= 128, else PNR_ERR_UNSUPPORTED; a missing pointer, or one clip pointer of a pair without the other, is
+ * PNR_ERR_INVALID; M = 0 is PNR_OK.  Every check comes before the launch. */
+int pnr_palette_smooth_points(const float* xyzs, const float* noise, float bound, uint32_t M, float* xyzs_diff, pnr_stream_t stream);
+int pnr_palette_smooth_forward(uint32_t M, uint32_t num_basis, uint32_t clip_dim, const float* xyzs, const float* xyzs_diff, const float* diffuse,
+                               const float* diffuse_diff, const float* omega, const float* omega_diff, const float* clip_feat,
+                               const float* clip_feat_diff, float bound, float sigma_xyz, float sigma_color, float sigma_clip, float* smooth_weight,
+                               float* smooth_norm, pnr_stream_t stream);
+int pnr_palette_smooth_backward(uint32_t M, uint32_t num_basis, uint32_t clip_dim, const float* grad_smooth_norm, const float* smooth_weight,
+                                const float* omega, const float* omega_diff, const float* clip_feat, const float* clip_feat_diff, float* grad_omega,
+                                float* grad_omega_diff, float* grad_clip_feat, float* grad_clip_feat_diff, pnr_stream_t stream);
+
 /* The two heads of PaletteNetwork.color under autograd as one launch each way (replaces, per training step, the two library GEMMs + bias add +
  * softplus + add + row sum + divide of palette/network.py:262-268 and their backward -- about twenty launches):
  *   h [M, in_dim] (basis_net's output, in_dim <= 16), w_offsets_radiance [3nb+1, in_dim], b_offsets_radiance [3nb+1], w_omega [nb, in_dim]

@@ -197,6 +197,13 @@ class PaletteNetwork(PaletteRenderer):
         """palette/network.py:156-185.  Returns sigma, clip_feat, omega, offsets_radiance, view_dep, diffuse.
         frozen_density: the caller detaches sigma (PaletteNeRF training, palette/renderer.py:333-334; geo_feat is detached here anyway), so
         encoder + sigma_net may run as the fused no-gradient density kernel."""
+        sigma, geo_feat, enc_pal = self._density_branch(x, frozen_density)
+        clip_feat = self._clip_branch(x, sigma)
+        omega, offsets_radiance, view_dep, diffuse = self.color(x, d, geo_feat=geo_feat, enc_palette=enc_pal)
+        return sigma, clip_feat, omega, offsets_radiance, view_dep, diffuse
+
+    def _density_branch(self, x, frozen_density):
+        """(sigma, geo_feat, encoder_palette's raw output at x or None): the first stage of forward()."""
         enc_pal = None
         if frozen_density and x.is_cuda and _fused_arch_ok(self):   # also under autocast: fp32 tables and MFMA chains, no gradient needed
             enc_density = None
@@ -210,6 +217,10 @@ class PaletteNetwork(PaletteRenderer):
             h = encode_mlp(self.encoder, x, self.bound, None, self.sigma_net)
             sigma = trunc_exp(h[..., 0])
             geo_feat = h[..., 1:].detach()
+        return sigma, geo_feat, enc_pal
+
+    def _clip_branch(self, x, sigma):
+        """clip_feat at x (palette/network.py:176-179); without a clip head the zeros the reference returns."""
         if self.opt.pred_clip:
             clip_feat = encode_mlp(self.encoder_clip, x, self.bound, None, self.clip_net)
         else:
@@ -220,8 +231,18 @@ class PaletteNetwork(PaletteRenderer):
                 clip_feat = z.expand(*sigma.shape, self.opt.clip_dim)
             else:
                 clip_feat = sigma.new_zeros(*sigma.shape, self.opt.clip_dim)   # palette/network.py:179 (zeros_like of a repeat there)
-        omega, offsets_radiance, view_dep, diffuse = self.color(x, d, geo_feat=geo_feat, enc_palette=enc_pal)
-        return sigma, clip_feat, omega, offsets_radiance, view_dep, diffuse
+        return clip_feat
+
+    def smooth_branch(self, x, frozen_density=True):
+        """(clip_feat, omega, diffuse) at x: what the smooth loss reads of its second field evaluation (palette/renderer.py:364).  The launches
+        forward() spends on these three outputs, same bits -- the fused density for geo_feat, diff_net, the palette lookup + basis_net + the heads
+        (whose offsets output is dropped), clip_net with a clip head -- and none for view_dep: no SH encode, no color_net."""
+        sigma, geo_feat, enc_pal = self._density_branch(x, frozen_density)
+        clip_feat = self._clip_branch(x, sigma)
+        g = geo_feat.detach()
+        diffuse = _run(self.diff_net, g, out=torch.sigmoid)
+        omega, _ = self._palette_branch(x, diffuse, enc_pal)
+        return clip_feat, omega, diffuse
 
     def density(self, x):
         if _fused_density_ok(self, x):
@@ -240,6 +261,11 @@ class PaletteNetwork(PaletteRenderer):
         g = geo_feat.detach()
         diffuse = _run(self.diff_net, g, out=torch.sigmoid)
         view_dep = _run(self.color_net, sh_encode_cat(self.encoder_dir, d, g), out=torch.sigmoid)
+        omega, offsets_radiance = self._palette_branch(x, diffuse, enc_palette)
+        return omega, offsets_radiance, view_dep, diffuse
+
+    def _palette_branch(self, x, diffuse, enc_palette=None):
+        """(omega, offsets_radiance) from the palette table at x and the diffuse colour (palette/network.py:257-268)."""
         h = encode_mlp(self.encoder_palette, x, self.bound, diffuse.detach(), self.basis_net, act=F.elu, enc=enc_palette)   # cat([encoder_palette(x), diffuse]) -> basis_net
         if _fused_heads_ok(self, h):
             offsets_radiance, omega = palette_heads(h, self.offsets_radiance_net, self.omega_net[0])
@@ -247,7 +273,7 @@ class PaletteNetwork(PaletteRenderer):
             offsets_radiance = self.offsets_radiance_net(h)
             omega = self.omega_net(h) + 0.05
             omega = omega / omega.sum(dim=-1, keepdim=True)
-        return omega, offsets_radiance, view_dep, diffuse
+        return omega, offsets_radiance
 
     def background(self, x, d):
         return _background(self, x, d)

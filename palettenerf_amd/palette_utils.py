@@ -125,6 +125,73 @@ class _palette_train_shade(Function):
 palette_train_shade = _palette_train_shade.apply
 
 
+def smooth_points(xyzs, noise, bound):
+    """The perturbed sample points of the smooth loss (palette/renderer.py:362) in one HIP launch:
+    clamp(xyzs + noise * bound * 0.03, -bound, bound) with noise = torch.rand_like(xyzs); the torch expression's bits.  [M,3] fp32, no gradient."""
+    f32 = torch.float32
+    xyzs, noise = require(xyzs.detach().contiguous(), f32, "xyzs"), require(noise.contiguous(), f32, "noise")
+    if xyzs.ndim != 2 or xyzs.shape[1] != 3 or noise.shape != xyzs.shape:
+        raise RuntimeError("smooth_points: xyzs and noise must be [M, 3]")
+    out = torch.empty_like(xyzs)
+    call("pnr_palette_smooth_points", ptr(xyzs), ptr(noise), float(bound), _u32(xyzs.shape[0]), ptr(out))
+    return out
+
+
+class _palette_smooth(Function):
+    """The bilateral weight and the norm of the smooth loss (palette/renderer.py:368-378) as one HIP launch each way: see
+    `pnr_palette_smooth_forward` in include/pnr.h.  Returns smooth_norm [M,1]; the weight is detached as in the reference, so only omega,
+    omega_diff, clip_feat and clip_feat_diff receive a gradient.  clip_feat / clip_feat_diff None: no clip head."""
+
+    @staticmethod
+    @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, xyzs, xyzs_diff, diffuse, diffuse_diff, omega, omega_diff, clip_feat, clip_feat_diff, bound, sigma_xyz, sigma_color, sigma_clip=0.0):
+        M, nb = omega.shape
+        if (clip_feat is None) != (clip_feat_diff is None):
+            raise RuntimeError("palette_smooth: clip_feat and clip_feat_diff come as a pair")
+        f32 = torch.float32
+        pairs = []
+        for name, a, b, width in (("xyzs", xyzs, xyzs_diff, 3), ("diffuse", diffuse, diffuse_diff, 3), ("omega", omega, omega_diff, nb),
+                                  ("clip_feat", clip_feat, clip_feat_diff, None)):
+            if a is None:
+                pairs += [None, None]
+                continue
+            width = a.shape[-1] if width is None else width
+            if a.shape != (M, width) or b.shape != (M, width):
+                raise RuntimeError(f"palette_smooth: {name} and {name}_diff must be [M, {width}]")
+            pairs += [require(a.contiguous(), f32, name), require(b.contiguous(), f32, name + "_diff")]
+        xyzs, xyzs_diff, diffuse, diffuse_diff, omega, omega_diff, clip_feat, clip_feat_diff = pairs
+        clip_dim = 0 if clip_feat is None else clip_feat.shape[1]
+        weight = torch.empty(M, device=omega.device, dtype=f32)
+        norm = torch.empty(M, 1, device=omega.device, dtype=f32)
+        call("pnr_palette_smooth_forward", _u32(M), _u32(nb), _u32(clip_dim), ptr(xyzs), ptr(xyzs_diff), ptr(diffuse), ptr(diffuse_diff), ptr(omega),
+             ptr(omega_diff), ptr(clip_feat), ptr(clip_feat_diff), float(bound), float(sigma_xyz), float(sigma_color), float(sigma_clip), ptr(weight),
+             ptr(norm))
+        ctx.save_for_backward(weight, omega, omega_diff, clip_feat, clip_feat_diff)
+        ctx.dims = (M, nb, clip_dim)
+        return norm
+
+    @staticmethod
+    @custom_bwd(device_type="cuda")
+    def backward(ctx, g_norm):
+        weight, omega, omega_diff, clip_feat, clip_feat_diff = ctx.saved_tensors
+        M, nb, clip_dim = ctx.dims
+        g_norm = require(g_norm.contiguous().float().view(-1), torch.float32, "grad_smooth_norm")
+        g_omega, g_omega_diff = torch.empty_like(omega), torch.empty_like(omega_diff)
+        g_clip = torch.empty_like(clip_feat) if clip_feat is not None and ctx.needs_input_grad[6] else None
+        g_clip_diff = torch.empty_like(clip_feat_diff) if clip_feat is not None and ctx.needs_input_grad[7] else None
+        call("pnr_palette_smooth_backward", _u32(M), _u32(nb), _u32(clip_dim), ptr(g_norm), ptr(weight), ptr(omega), ptr(omega_diff), ptr(clip_feat),
+             ptr(clip_feat_diff), ptr(g_omega), ptr(g_omega_diff), ptr(g_clip), ptr(g_clip_diff))
+        return None, None, None, None, g_omega, g_omega_diff, g_clip, g_clip_diff, None, None, None, None
+
+
+def palette_smooth(xyzs, xyzs_diff, diffuse, diffuse_diff, omega, omega_diff, clip_feat, clip_feat_diff, bound, sigma_xyz, sigma_color, sigma_clip=0.0):
+    """smooth_norm [M,1] of the smooth loss through `_palette_smooth`.  The points and the diffuse colours only enter the detached weight
+    (palette/renderer.py:375): they go in detached, so that autograd does not walk the graphs behind them with zero gradients (for diffuse_diff that
+    is a whole diff_net backward launch per step nobody reads)."""
+    return _palette_smooth.apply(xyzs.detach(), xyzs_diff.detach(), diffuse.detach(), diffuse_diff.detach(), omega, omega_diff, clip_feat, clip_feat_diff,
+                                 bound, sigma_xyz, sigma_color, sigma_clip)
+
+
 class _palette_heads(Function):
     """offsets_radiance_net + omega_net + normalisation of PaletteNetwork.color (palette/network.py:262-268) as one HIP launch each way:
     see `pnr_palette_heads_forward` in include/pnr.h.  h [M, in] -> (offsets_radiance [M, 3 nb + 1], omega [M, nb])."""

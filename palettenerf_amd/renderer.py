@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from . import _lib, raymarching
 from ._torch_glue import call, ptr, require
-from .palette_utils import hsv_to_rgb, palette_train_shade, rgb_to_hsv
+from .palette_utils import hsv_to_rgb, palette_smooth, palette_train_shade, rgb_to_hsv, smooth_points
 from .train_loss import RawTrain, TrainResults
 
 
@@ -812,7 +812,20 @@ class PaletteRenderer(_RendererBase):
                 omega_sparsity = omega[..., 0].sum(dim=-1, keepdim=True) / ((omega[..., 0] ** 2).sum(dim=-1, keepdim=True) + 1e-6) - 1
                 offsets_norm = (offsets ** 2).sum(dim=-1).sum(dim=-1, keepdim=True)
                 view_dep_norm = (view_dep ** 2).sum(dim=-1, keepdim=True)
-            if self.require_smooth_loss:
+            fused_smooth = (self.require_smooth_loss and bool(getattr(self, "fused_train_smooth", True)) and xyzs.is_cuda and nb <= 16
+                            and (not self.opt.pred_clip or clip_dim <= 128))   # the entries' range; anything else keeps the torch block
+            if fused_smooth:   # palette/renderer.py:360-378 on pnr_palette_smooth_*: the points, the weight + norm and their gradient are one launch each
+                frozen = bool(getattr(self, "fused_train_density", True))
+                xyzs_diff = smooth_points(xyzs, torch.rand_like(xyzs), self.bound)   # the one draw the torch block makes: a seed perturbs both alike
+                if hasattr(self, "smooth_branch"):   # the three outputs the block reads, without the view-dependent head
+                    clip_feat_diff, omega_diff, diffuse_diff = self.smooth_branch(xyzs_diff, frozen_density=frozen)
+                else:
+                    _, clip_feat_diff, omega_diff, _, _, diffuse_diff = self(xyzs_diff, dirs, frozen_density=frozen)
+                pred_clip = bool(self.opt.pred_clip)
+                smooth_norm = palette_smooth(xyzs, xyzs_diff, diffuse, diffuse_diff.reshape(M, 3), omega.reshape(M, nb), omega_diff.reshape(M, nb),
+                                             clip_feat if pred_clip else None, clip_feat_diff.reshape(M, clip_dim) if pred_clip else None,
+                                             self.bound, self.opt.smooth_sigma_xyz, self.opt.smooth_sigma_color, self.opt.smooth_sigma_clip)
+            elif self.require_smooth_loss:
                 xyzs_diff = (xyzs + torch.rand_like(xyzs) * self.bound * 0.03).clamp(-self.bound, self.bound)
                 _, clip_feat_diff, omega_diff, _, _, diffuse_diff = self(xyzs_diff, dirs, frozen_density=bool(getattr(self, "fused_train_density", True)))
                 omega_diff = omega_diff.reshape(M, nb, 1)
