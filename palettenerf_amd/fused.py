@@ -444,8 +444,9 @@ class StaleFrame(RuntimeError):
 
 
 class _FrameToken:
-    """A frame between frame_prepare and frame_finish: its argument struct, outputs, host-side stats arrays and what a re-render needs."""
-    __slots__ = ("a", "p", "out", "stats", "kms", "watch_state", "watch", "finished", "nears", "fars", "again", "keep", "stream", "depth_raw", "edit", "valid", "gen", "noises")
+    """A frame between frame_prepare and frame_finish: the argument struct the C calls are given (`args`) and its pnr_nerf_frame_args part (`base`: the struct
+    itself for a NeRF frame, its first member for a palette frame), outputs, host-side stats arrays and what a re-render needs."""
+    __slots__ = ("args", "base", "out", "stats", "kms", "watch_state", "watch", "finished", "nears", "fars", "again", "keep", "stream", "depth_raw", "edit", "valid", "gen", "noises")
 
     def __init__(self, **kw):
         self.valid = None
@@ -458,6 +459,159 @@ def _frame_valid(fused, tok):
     if not fused._watch_end(tok.watch_state):
         return 1
     return 2 if (tok.watch and tok.stats[5]) else 0
+
+
+class _FrameLoop:
+    """The host side of the device-driven frame loop, once for both fields (as `render_frame_impl` in csrc/frame.hip is one function for both ABIs): the whole
+    frame call, the same call in three steps, the kept argument struct, the two retries.  What a field class supplies:
+      _frame_entry, _frame_finish_mask           its C entry points (looked up on the library object by name at every call: profiles/frame_host_time.py
+                                                 wraps them there) and pnr_nerf_frame_args::finish for a call that applies the epilogue
+      _frame_struct()                            -> (the struct the C calls are given, its pnr_nerf_frame_args part)
+      _frame_key(m, enc)                         the plan key's terms for what _frame_fill reads
+      _frame_workspace_bytes(lib, N)
+      _frame_fill(args, a, m, enc)               the kept struct's table pointers and the fields only this kind has -> the tensors whose addresses it stored
+      _frame_extras(tok, N, dev)                 per-frame outputs and struct fields only this kind has (the token is complete otherwise)
+      _frame_outputs(tok, stats)                 the result tuple"""
+
+    _frame_finish_mask = 3       # (7: the epilogue also goes over the palette frame's aux_map)
+
+    def _frame_extras(self, tok, N, dev):
+        pass
+
+    def _frame_outputs(self, tok, stats):
+        return tok.out + (stats,)
+
+    @torch.no_grad()
+    def render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0, noises=None):
+        """One inference frame through the device-driven loop (pnr_nerf_render_frame / pnr_palette_render_frame).  Returns
+        (weights_sum [N], depth [N], image [N,3], stats dict); a palette field (weights_sum, depth, image, aux_map [N, aux_channels], stats).
+        bg_color None: raw accumulations (bg mix and depth normalisation are the caller's); a number, 3 numbers or an [N,3] tensor: the call's last launch also
+        applies run_cuda's epilogue (image + (1 - ws) bg, normalised depth; palette/renderer.py:520-540: also aux_map[:, 0:3] = direct_rgb blended with the
+        background, the raw depth kept in stats['depth_raw']) -- stats['finished'] says so.  aabb (device tensor of 6 floats) with nears = fars = None: the call
+        computes near / far in its first launch (near_far_from_aabb's arithmetic); stats['nears'], stats['fars'] hold them.  noises ([N] fp32 on the device, by ray
+        id): the first-sample jitter of march_rays(perturb=True), applied in the frame's first iteration (pnr_nerf_frame_args::noises); None: no jitter."""
+        with self._held():
+            return self._render_frame(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
+
+    # The same frame in three steps (round 6; <entry>_submit / _finish): frame_prepare does everything in front of the library call (outputs, argument
+    # struct, source checksums) and may run while the PREVIOUS frame is still on the device; frame_launch enqueues the frame and returns at once; frame_finish waits
+    # for it and returns what render_frame returns.  A caller with a queue of frames (a video path, a rank's shard loop) runs
+    #     tok = prepare(0); launch(tok);  for i in 1..: nxt = prepare(i); out = finish(tok); launch(nxt); tok = nxt; consume(out)
+    # so that the host's work for frame i + 1 lies under frame i's kernels.  Two argument structs alternate (a frame's struct must stay as it was until its finish).
+    @torch.no_grad()
+    def frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0, noises=None):
+        with self._held():
+            return self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
+
+    def frame_launch(self, tok):
+        if tok.gen != self.__dict__.get("_gen", 0):
+            raise StaleFrame("the frame was prepared before the packed blobs were rebuilt")
+        tok.stream = stream_ptr()
+        name = self._frame_entry + "_submit"
+        _lib.check(getattr(_lib.load(), name)(ctypes.byref(tok.args), tok.stream), name)
+        return tok
+
+    def frame_wait(self, tok):
+        """The library's finish call alone: waits for the frame (and enqueues what it still needs).  True: the frame's outputs are valid -- the caller may enqueue
+        its next frame before it asks for frame_result(); False: the frame has to be rendered again (sources rewritten behind torch's counters, an fp16
+        overflow), which frame_result() does -- ask for it BEFORE launching another frame."""
+        name = self._frame_entry + "_finish"
+        _lib.check(getattr(_lib.load(), name)(ctypes.byref(tok.args), tok.stream), name)
+        tok.valid = _frame_valid(self, tok)
+        return tok.valid == 0
+
+    @torch.no_grad()
+    def frame_result(self, tok):
+        with self._held():
+            return self._frame_post(tok)
+
+    def frame_finish(self, tok):
+        self.frame_wait(tok)
+        return self.frame_result(tok)
+
+    def _render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises=None):
+        tok = self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
+        rc = getattr(_lib.load(), self._frame_entry)(ctypes.byref(tok.args), stream_ptr())
+        _lib.check(rc, self._frame_entry)
+        return self._frame_post(tok)
+
+    def _frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises=None):
+        from . import raymarching
+        m = self.model
+        N = rays_o.shape[0]
+        dev = rays_o.device
+        slot = self._slot = 1 - self.__dict__.get("_slot", 1)
+        watch_state = self._watch_begin(slot)
+        ws = torch.empty(N, dtype=torch.float32, device=dev)
+        depth = torch.empty(N, dtype=torch.float32, device=dev)
+        image = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        order = getattr(self, "ray_order", None)
+        if order is not None and order.numel() != N:
+            order = None
+        enc = m.encoder
+        # Everything of the argument struct that only changes when a parameter, a table or a setting does is filled once and kept (the "plan"): the key holds
+        # the identity and version of every source (the watch's keys, formed above), the frame size and the settings read here and in _frame_fill.  A frame whose
+        # key matches sets the per-frame fields only -- a third of the call's host time in front of the first launch went into re-deriving the same fifty values.
+        plan_key = (self._watch_keys, N, dev, int(self.precision), bool(self.table_half), self.__dict__.get("_overflowed_key"), None if order is None else (id(order), order.data_ptr()),
+                    float(m.bound), int(m.cascade), int(m.grid_size), float(m.density_scale), enc.num_levels, enc.per_level_scale, enc.base_resolution, enc.gridtype_id,
+                    self._frame_key(m, enc))
+        plans = self.__dict__.get("_frame_plan")
+        if plans is None:
+            plans = self._frame_plan = {}
+        plan = plans.get(slot)
+        if plan is None or plan[0] != plan_key or PARANOID:
+            nbytes = int(self._frame_workspace_bytes(_lib.load(), N))
+            if getattr(self, "_ws", None) is None or self._ws.numel() < nbytes or self._ws.device != dev:
+                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            prec, watch = self.frame_precision()
+            args, a = self._frame_struct()
+            a.table_dtype = 1 if self.table_half else 0
+            a.N = N
+            a.bound, a.C, a.H = float(m.bound), int(m.cascade), int(m.grid_size)
+            a.offsets = enc.offsets.data_ptr()
+            a.num_levels, a.S, a.base_resolution, a.gridtype = enc.num_levels, float(np.log2(enc.per_level_scale)), enc.base_resolution, enc.gridtype_id
+            a.field_precision, a.watch_overflow = int(prec), int(watch)
+            for k, v in enumerate(self.enc_scales(prec)):
+                a.enc_scale[k] = v
+            a.density_scale = float(m.density_scale)
+            a.workspace, a.workspace_bytes = self._ws.data_ptr(), nbytes
+            a.ray_order = order.data_ptr() if order is not None else None
+            plan = plans[slot] = (plan_key, args, a, prec, watch, (self._ws, order) + self._frame_fill(args, a, m, enc))     # (the tensors whose addresses the struct holds)
+        args, a, prec, watch = plan[1], plan[2], plan[3], plan[4]
+        # The packed blob is NOT part of the plan: it is looked up per frame (a key compare when nothing changed) and the token keeps it alive; a repack -- new
+        # weights, or the stand-alone ops (`self(x, d)` from network.forward) asking for THEIR precision -- goes into another tensor (_pack).
+        blob = self._pack(prec)
+        a.packed_weights = blob.data_ptr()
+        mip = raymarching.occupancy_mip(m.density_bitfield, m.cascade, m.grid_size, m.bound)
+        stats = (ctypes.c_uint64 * 6)()
+        kms = (ctypes.c_float * 2)()
+        a.rays_o, a.rays_d = rays_o.data_ptr(), rays_d.data_ptr()
+        nears, fars = _set_near_far(a, nears, fars, aabb, min_near, N, dev)
+        a.bitfield = m.density_bitfield.data_ptr()
+        a.mip = mip.data_ptr() if mip is not None else None
+        a.dt_gamma, a.max_steps, a.T_thresh = float(dt_gamma), int(max_steps), float(T_thresh)
+        a.weights_sum, a.depth, a.image = ws.data_ptr(), depth.data_ptr(), image.data_ptr()
+        a.stats = ctypes.cast(stats, ctypes.c_void_p)
+        a.kernel_ms = ctypes.cast(kms, ctypes.c_void_p) if getattr(self, "time_grid_kernel", False) else None     # (bench.py sets it; a palette object has none until then)
+        finished = _set_finish(a, bg_color, N, self._frame_finish_mask)
+        a.noises = _noises_ptr(noises, N, dev)
+        for t, name in ((rays_o, "rays_o"), (rays_d, "rays_d"), (nears, "nears"), (fars, "fars")):
+            require(t, torch.float32, name)
+        tok = _FrameToken(gen=self.__dict__.get("_gen", 0), args=args, base=a, out=(ws, depth, image), stats=stats, kms=kms, watch_state=watch_state, watch=watch, finished=finished,
+                          nears=nears, fars=fars,
+                          again=(rays_o, rays_d, None if aabb is not None else nears, None if aabb is not None else fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises),
+                          keep=(mip, bg_color, blob), noises=noises)
+        self._frame_extras(tok, N, dev)
+        return tok
+
+    def _frame_post(self, tok):
+        valid = tok.valid if tok.valid is not None else _frame_valid(self, tok)
+        if valid:
+            (self._watch_failed if valid == 1 else self._note_overflow)()
+            return self._render_frame(*tok.again)
+        stats, kms = tok.stats, tok.kms
+        return self._frame_outputs(tok, {"iterations": int(stats[0]), "rendered": int(stats[1]), "rows": int(stats[2]), "enqueued": int(stats[3]), "looks": int(stats[4]),
+                                         "grid_ms": float(kms[0]), "grid_launches": int(kms[1]), "finished": tok.finished, "nears": tok.nears, "fars": tok.fars})
 
 
 class BackgroundFused:
@@ -569,7 +723,7 @@ def background_fused(model):
     return f
 
 
-class NeRFFieldFused(_PrecisionGuard, _SourceWatch):
+class NeRFFieldFused(_PrecisionGuard, _SourceWatch, _FrameLoop):
     """Caches the MFMA-ordered weight blob of a NeRFNetwork and evaluates (sigma, rgb) for sample batches."""
 
     def __init__(self, model):
@@ -640,139 +794,24 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch):
         self.versions, self.packed = hit      # (the blob handed out last and its key)
         return hit[1]
 
-    @torch.no_grad()
-    def render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0, noises=None):
-        """One inference frame through the device-driven loop (pnr_nerf_render_frame).  Returns
-        (weights_sum [N], depth [N], image [N,3], stats dict).  bg_color None: raw accumulations (bg mix and depth normalisation are
-        the caller's); a number, 3 numbers or an [N,3] tensor: the call also applies run_cuda's epilogue (image + (1 - ws) bg,
-        normalised depth) -- stats['finished'] says so.  aabb (device tensor of 6 floats) with nears = fars = None: the call computes
-        near / far in its first launch (near_far_from_aabb's arithmetic); stats['nears'], stats['fars'] hold them.  noises ([N] fp32 on the device, by ray
-        id): the first-sample jitter of march_rays(perturb=True), applied in the frame's first iteration (pnr_nerf_frame_args::noises); None: no jitter."""
-        with self._held():
-            return self._render_frame(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
+    _frame_entry = "pnr_nerf_render_frame"
 
-    # The same frame in three steps (round 6; pnr_nerf_render_frame_submit / _finish): frame_prepare does everything in front of the library call (outputs, argument
-    # struct, source checksums) and may run while the PREVIOUS frame is still on the device; frame_launch enqueues the frame and returns at once; frame_finish waits
-    # for it and returns what render_frame returns.  A caller with a queue of frames (a video path, a rank's shard loop) runs
-    #     tok = prepare(0); launch(tok);  for i in 1..: nxt = prepare(i); out = finish(tok); launch(nxt); tok = nxt; consume(out)
-    # so that the host's work for frame i + 1 lies under frame i's kernels.  Two argument structs alternate (a frame's struct must stay as it was until its finish).
-    @torch.no_grad()
-    def frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0, noises=None):
-        with self._held():
-            return self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
+    def _frame_struct(self):
+        a = _lib.NerfFrameArgs()
+        return a, a
 
-    def frame_launch(self, tok):
-        if tok.gen != self.__dict__.get("_gen", 0):
-            raise StaleFrame("the frame was prepared before the packed blobs were rebuilt")
-        tok.stream = stream_ptr()
-        _lib.check(_lib.load().pnr_nerf_render_frame_submit(ctypes.byref(tok.a), tok.stream), "pnr_nerf_render_frame_submit")
-        return tok
+    def _frame_key(self, m, enc):
+        return _pkey(enc.offsets)
 
-    def frame_wait(self, tok):
-        """The library's finish call alone: waits for the frame (and enqueues what it still needs).  True: the frame's outputs are valid -- the caller may enqueue
-        its next frame before it asks for frame_result(); False: the frame has to be rendered again (sources rewritten behind torch's counters, an fp16
-        overflow), which frame_result() does -- ask for it BEFORE launching another frame."""
-        _lib.check(_lib.load().pnr_nerf_render_frame_finish(ctypes.byref(tok.a), tok.stream), "pnr_nerf_render_frame_finish")
-        tok.valid = _frame_valid(self, tok)
-        return tok.valid == 0
+    def _frame_workspace_bytes(self, lib, N):
+        return lib.pnr_nerf_frame_workspace_bytes(N)
 
-    @torch.no_grad()
-    def frame_result(self, tok):
-        with self._held():
-            return self._frame_post(tok)
-
-    def frame_finish(self, tok):
-        self.frame_wait(tok)
-        return self.frame_result(tok)
-
-    def _render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises=None):
-        tok = self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
-        rc = _lib.load().pnr_nerf_render_frame(ctypes.byref(tok.a), stream_ptr())
-        _lib.check(rc, "pnr_nerf_render_frame")
-        return self._frame_post(tok)
-
-    def _frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises=None):
-        from . import raymarching
-        m = self.model
-        N = rays_o.shape[0]
-        dev = rays_o.device
-        lib = _lib.load()
-        slot = self._slot = 1 - self.__dict__.get("_slot", 1)
-        watch_state = self._watch_begin(slot)
-        ws = torch.empty(N, dtype=torch.float32, device=dev)
-        depth = torch.empty(N, dtype=torch.float32, device=dev)
-        image = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        order = getattr(self, "ray_order", None)
-        if order is not None and order.numel() != N:
-            order = None
-        enc = m.encoder
-        # Everything of the argument struct that only changes when a parameter, a table or a setting does is filled once and kept (the "plan"): the key holds
-        # the identity and version of every source (the watch's keys, formed above), the frame size and the settings read here.  A frame whose key matches
-        # sets the per-frame fields only -- a third of the call's host time in front of the first launch went into re-deriving the same fifty values.
-        plan_key = (self._watch_keys, N, dev, int(self.precision), bool(self.table_half), self.__dict__.get("_overflowed_key"), None if order is None else (id(order), order.data_ptr()),
-                    float(m.bound), int(m.cascade), int(m.grid_size), float(m.density_scale), enc.num_levels, enc.per_level_scale, enc.base_resolution, enc.gridtype_id,
-                    _pkey(enc.offsets))
-        plans = self.__dict__.get("_frame_plan")
-        if plans is None:
-            plans = self._frame_plan = {}
-        plan = plans.get(slot)
-        if plan is None or plan[0] != plan_key or PARANOID:
-            nbytes = int(lib.pnr_nerf_frame_workspace_bytes(N))
-            if getattr(self, "_ws", None) is None or self._ws.numel() < nbytes or self._ws.device != dev:
-                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            emb = require(enc.embeddings.detach(), torch.float32, "embeddings")
-            if self.table_half:   # the reference's --fp16 tables (`embeddings.to(torch.half)` per forward, gridencoder/grid.py:38): converted once per update here
-                emb = _half_copy(self, "_emb_half", enc.embeddings)
-            prec, watch = self.frame_precision()
-            a = _lib.NerfFrameArgs()
-            a.table_dtype = 1 if self.table_half else 0
-            a.N = N
-            a.bound, a.C, a.H = float(m.bound), int(m.cascade), int(m.grid_size)
-            a.embeddings, a.offsets = emb.data_ptr(), enc.offsets.data_ptr()
-            a.num_levels, a.S, a.base_resolution, a.gridtype = enc.num_levels, float(np.log2(enc.per_level_scale)), enc.base_resolution, enc.gridtype_id
-            a.field_precision, a.watch_overflow = int(prec), int(watch)
-            for k, v in enumerate(self.enc_scales(prec)):
-                a.enc_scale[k] = v
-            a.density_scale = float(m.density_scale)
-            a.workspace, a.workspace_bytes = self._ws.data_ptr(), nbytes
-            a.ray_order = order.data_ptr() if order is not None else None
-            plan = plans[slot] = (plan_key, a, prec, watch, (emb, self._ws, order))     # (the tensors whose addresses the struct holds)
-        a, prec, watch = plan[1], plan[2], plan[3]
-        # The packed blob is NOT part of the plan: it is looked up per frame (a key compare when nothing changed) and the token keeps it alive; a repack -- new
-        # weights, or the stand-alone ops (`self(x, d)` from network.forward) asking for THEIR precision -- goes into another tensor (_pack).
-        blob = self._pack(prec)
-        a.packed_weights = blob.data_ptr()
-        mip = raymarching.occupancy_mip(m.density_bitfield, m.cascade, m.grid_size, m.bound)
-        stats = (ctypes.c_uint64 * 6)()
-        a.rays_o, a.rays_d = rays_o.data_ptr(), rays_d.data_ptr()
-        nears, fars = _set_near_far(a, nears, fars, aabb, min_near, N, dev)
-        a.bitfield = m.density_bitfield.data_ptr()
-        a.mip = mip.data_ptr() if mip is not None else None
-        a.dt_gamma, a.max_steps, a.T_thresh = float(dt_gamma), int(max_steps), float(T_thresh)
-        a.weights_sum, a.depth, a.image = ws.data_ptr(), depth.data_ptr(), image.data_ptr()
-        a.stats = ctypes.cast(stats, ctypes.c_void_p)
-        kms = (ctypes.c_float * 2)()
-        a.kernel_ms = ctypes.cast(kms, ctypes.c_void_p) if self.time_grid_kernel else None
-        finished = _set_finish(a, bg_color, N, 3)
-        a.noises = _noises_ptr(noises, N, dev)
-        for t, name in ((rays_o, "rays_o"), (rays_d, "rays_d"), (nears, "nears"), (fars, "fars")):
-            require(t, torch.float32, name)
-        return _FrameToken(gen=self.__dict__.get("_gen", 0), a=a, out=(ws, depth, image), stats=stats, kms=kms, watch_state=watch_state, watch=watch, finished=finished, nears=nears, fars=fars,
-                           again=(rays_o, rays_d, None if aabb is not None else nears, None if aabb is not None else fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises),
-                           keep=(mip, bg_color, blob), noises=noises)
-
-    def _frame_post(self, tok):
-        valid = tok.valid if tok.valid is not None else _frame_valid(self, tok)
-        if valid == 1:
-            self._watch_failed()
-            return self._render_frame(*tok.again)
-        stats, kms = tok.stats, tok.kms
-        if valid == 2:
-            self._note_overflow()
-            return self._render_frame(*tok.again)
-        ws, depth, image = tok.out
-        return ws, depth, image, {"iterations": int(stats[0]), "rendered": int(stats[1]), "rows": int(stats[2]), "enqueued": int(stats[3]), "looks": int(stats[4]),
-                                  "grid_ms": float(kms[0]), "grid_launches": int(kms[1]), "finished": tok.finished, "nears": tok.nears, "fars": tok.fars}
+    def _frame_fill(self, args, a, m, enc):
+        emb = require(enc.embeddings.detach(), torch.float32, "embeddings")
+        if self.table_half:   # the reference's --fp16 tables (`embeddings.to(torch.half)` per forward, gridencoder/grid.py:38): converted once per update here
+            emb = _half_copy(self, "_emb_half", enc.embeddings)
+        a.embeddings = emb.data_ptr()
+        return (emb,)
 
     @torch.no_grad()
     def __call__(self, x, d):
@@ -828,7 +867,7 @@ def density_fused(model):
     return d
 
 
-class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
+class PaletteFieldFused(_PrecisionGuard, _SourceWatch, _FrameLoop):
     """Fused PaletteNeRF field + colour-basis composite (pnr_palette_field_forward).  Produces, per sample,
     sigma * density_scale, rgb and one packed aux row [direct 3 | view_dep 3 | omega nb | basis_rgb 3nb | unscaled 3nb | clip | pad]."""
 
@@ -1009,144 +1048,49 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch):
             setattr(self, name + "_key", key)
         return getattr(self, name)
 
-    def render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0, noises=None):
-        """One PaletteNeRF inference frame through the device-driven loop (pnr_palette_render_frame).
-        Returns (weights_sum [N], depth [N], image [N,3], aux_map [N, aux_channels], stats).  bg_color None: raw accumulations; a number, 3 numbers
-        or an [N,3] tensor: the call's last launch also applies run_cuda's epilogue (palette/renderer.py:520-540: image and aux_map[:, 0:3] = direct_rgb
-        blended with the background, depth normalised, the raw depth kept in stats['depth_raw']) -- stats['finished'] says so.  aabb with
-        nears = fars = None: near / far computed by the call's first launch (stats['nears'], stats['fars']).  noises: NeRFFieldFused.render_frame explains."""
-        with torch.no_grad(), self._held():
-            return self._render_frame(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
+    _frame_entry = "pnr_palette_render_frame"
+    _frame_finish_mask = 7
 
-    # prepare / launch / finish: NeRFFieldFused explains (pnr_palette_render_frame_submit / _finish)
-    def frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color=None, aabb=None, min_near=0.0, noises=None):
-        with torch.no_grad(), self._held():
-            return self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
+    def _frame_struct(self):
+        p = _lib.PaletteFrameArgs()
+        return p, p.base
 
-    def frame_launch(self, tok):
-        if tok.gen != self.__dict__.get("_gen", 0):
-            raise StaleFrame("the frame was prepared before the packed blobs were rebuilt")
-        tok.stream = stream_ptr()
-        _lib.check(_lib.load().pnr_palette_render_frame_submit(ctypes.byref(tok.p), tok.stream), "pnr_palette_render_frame_submit")
-        return tok
+    def _frame_key(self, m, enc):
+        return (bool(self.interleave_tables), float(m.offsets_weight), float(m.view_dep_weight),
+                tuple((_pkey(o.offsets), o.per_level_scale) for o in (enc, m.encoder_palette, m.encoder_clip)))
 
-    def frame_wait(self, tok):
-        _lib.check(_lib.load().pnr_palette_render_frame_finish(ctypes.byref(tok.p), tok.stream), "pnr_palette_render_frame_finish")
-        tok.valid = _frame_valid(self, tok)
-        return tok.valid == 0
+    def _frame_workspace_bytes(self, lib, N):
+        return lib.pnr_palette_frame_workspace_bytes(N, self.nb, self.clip_dim, int(self.pred_clip))
 
-    def frame_result(self, tok):
-        with torch.no_grad(), self._held():
-            return self._frame_post(tok)
+    def _frame_fill(self, p, a, m, enc):
+        # (once per set of offset buffers: torch.equal is a device comparison plus a host read)
+        for other in (m.encoder_palette, m.encoder_clip):
+            if not torch.equal(other.offsets, enc.offsets) or other.per_level_scale != enc.per_level_scale:
+                raise RuntimeError("the three hash grids must share one level layout")
+        a.embeddings = require(enc.embeddings.detach(), torch.float32, "embeddings").data_ptr()
+        p.embeddings_palette = require(m.encoder_palette.embeddings.detach(), torch.float32, "embeddings").data_ptr()
+        p.embeddings_clip = require(m.encoder_clip.embeddings.detach(), torch.float32, "embeddings").data_ptr() if self.pred_clip else None
+        p.num_basis, p.clip_dim, p.pred_clip = self.nb, self.clip_dim, int(self.pred_clip)
+        p.offsets_weight, p.view_dep_weight = float(m.offsets_weight), float(m.view_dep_weight)
+        pair = self._pair_table() if ((self.interleave_tables or self.table_half) and not self.pred_clip) else None
+        p.embeddings_pair = pair.data_ptr() if pair is not None else None
+        triple = self._triple_table() if ((self.interleave_tables or self.table_half) and self.pred_clip) else None
+        p.embeddings_triple = triple.data_ptr() if triple is not None else None
+        return pair, triple
 
-    def frame_finish(self, tok):
-        self.frame_wait(tok)
-        return self.frame_result(tok)
-
-    def _render_frame(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises=None):
-        tok = self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
-        rc = _lib.load().pnr_palette_render_frame(ctypes.byref(tok.p), stream_ptr())
-        _lib.check(rc, "pnr_palette_render_frame")
-        return self._frame_post(tok)
-
-    def _frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises=None):
-        from . import raymarching
-        m = self.model
-        N = rays_o.shape[0]
-        dev = rays_o.device
-        lib = _lib.load()
-        slot = self._slot = 1 - self.__dict__.get("_slot", 1)
-        watch_state = self._watch_begin(slot)
-        ws = torch.empty(N, dtype=torch.float32, device=dev)
-        depth = torch.empty(N, dtype=torch.float32, device=dev)
-        image = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    def _frame_extras(self, tok, N, dev):
+        p, a, finished = tok.args, tok.base, tok.finished
         aux_map = torch.empty(N, self.aux_channels, dtype=torch.float32, device=dev)
-        order = getattr(self, "ray_order", None)
-        if order is not None and order.numel() != N:
-            order = None
-        enc = m.encoder
-        # the kept argument struct (NeRFFieldFused._frame_prepare explains): key = identity and version of every source + frame size + the settings read below
-        plan_key = (self._watch_keys, N, dev, int(self.precision), bool(self.table_half), bool(self.interleave_tables), self.__dict__.get("_overflowed_key"),
-                    None if order is None else (id(order), order.data_ptr()), float(m.bound), int(m.cascade), int(m.grid_size), float(m.density_scale),
-                    float(m.offsets_weight), float(m.view_dep_weight), enc.num_levels, enc.per_level_scale, enc.base_resolution, enc.gridtype_id,
-                    tuple((_pkey(o.offsets), o.per_level_scale) for o in (enc, m.encoder_palette, m.encoder_clip)))
-        plans = self.__dict__.get("_frame_plan")
-        if plans is None:
-            plans = self._frame_plan = {}
-        plan = plans.get(slot)
-        if plan is None or plan[0] != plan_key or PARANOID:
-            nbytes = int(lib.pnr_palette_frame_workspace_bytes(N, self.nb, self.clip_dim, int(self.pred_clip)))
-            if getattr(self, "_ws", None) is None or self._ws.numel() < nbytes or self._ws.device != dev:
-                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            # (once per set of offset buffers: torch.equal is a device comparison plus a host read)
-            for other in (m.encoder_palette, m.encoder_clip):
-                if not torch.equal(other.offsets, enc.offsets) or other.per_level_scale != enc.per_level_scale:
-                    raise RuntimeError("the three hash grids must share one level layout")
-            prec, watch = self.frame_precision()
-            p = _lib.PaletteFrameArgs()
-            a = p.base
-            a.N = N
-            a.bound, a.C, a.H = float(m.bound), int(m.cascade), int(m.grid_size)
-            a.embeddings = require(enc.embeddings.detach(), torch.float32, "embeddings").data_ptr()
-            a.offsets = enc.offsets.data_ptr()
-            a.num_levels, a.S, a.base_resolution, a.gridtype = enc.num_levels, float(np.log2(enc.per_level_scale)), enc.base_resolution, enc.gridtype_id
-            a.field_precision, a.watch_overflow = int(prec), int(watch)
-            for k, v in enumerate(self.enc_scales(prec)):
-                a.enc_scale[k] = v
-            a.density_scale = float(m.density_scale)
-            a.workspace, a.workspace_bytes = self._ws.data_ptr(), nbytes
-            a.ray_order = order.data_ptr() if order is not None else None
-            p.embeddings_palette = require(m.encoder_palette.embeddings.detach(), torch.float32, "embeddings").data_ptr()
-            p.embeddings_clip = require(m.encoder_clip.embeddings.detach(), torch.float32, "embeddings").data_ptr() if self.pred_clip else None
-            p.num_basis, p.clip_dim, p.pred_clip = self.nb, self.clip_dim, int(self.pred_clip)
-            p.offsets_weight, p.view_dep_weight = float(m.offsets_weight), float(m.view_dep_weight)
-            pair = self._pair_table() if ((self.interleave_tables or self.table_half) and not self.pred_clip) else None
-            p.embeddings_pair = pair.data_ptr() if pair is not None else None
-            triple = self._triple_table() if ((self.interleave_tables or self.table_half) and self.pred_clip) else None
-            p.embeddings_triple = triple.data_ptr() if triple is not None else None
-            a.table_dtype = 1 if self.table_half else 0
-            plan = plans[slot] = (plan_key, p, prec, watch, (self._ws, order, pair, triple))     # (the tensors whose addresses the struct holds)
-        p, prec, watch = plan[1], plan[2], plan[3]
-        a = p.base
-        a.packed_weights = self._pack(prec).data_ptr()     # every frame (NeRFFieldFused._frame_prepare explains): a stand-alone call may have packed ANOTHER tensor since
-        mip = raymarching.occupancy_mip(m.density_bitfield, m.cascade, m.grid_size, m.bound)
-        stats = (ctypes.c_uint64 * 6)()
-        kms = (ctypes.c_float * 2)()
-        a.rays_o, a.rays_d = rays_o.data_ptr(), rays_d.data_ptr()
-        nears, fars = _set_near_far(a, nears, fars, aabb, min_near, N, dev)
-        a.bitfield = m.density_bitfield.data_ptr()
-        a.mip = mip.data_ptr() if mip is not None else None
-        a.dt_gamma, a.max_steps, a.T_thresh = float(dt_gamma), int(max_steps), float(T_thresh)
-        a.weights_sum, a.depth, a.image = ws.data_ptr(), depth.data_ptr(), image.data_ptr()
-        a.stats = ctypes.cast(stats, ctypes.c_void_p)
-        a.kernel_ms = ctypes.cast(kms, ctypes.c_void_p) if getattr(self, "time_grid_kernel", False) else None
-        finished = _set_finish(a, bg_color, N, 7)
-        a.noises = _noises_ptr(noises, N, dev)
-        depth_raw = torch.empty(N, dtype=torch.float32, device=dev) if finished else None
-        a.depth_raw = depth_raw.data_ptr() if finished else None
+        tok.out += (aux_map,)
         p.aux_map = aux_map.data_ptr()
-        edit = self._edit_struct()
+        tok.depth_raw = torch.empty(N, dtype=torch.float32, device=dev) if finished else None
+        a.depth_raw = tok.depth_raw.data_ptr() if finished else None
+        edit = tok.edit = self._edit_struct()
         p.edit = ctypes.cast(ctypes.pointer(edit), ctypes.c_void_p) if edit is not None else None
-        for t, name in ((rays_o, "rays_o"), (rays_d, "rays_d"), (nears, "nears"), (fars, "fars")):
-            require(t, torch.float32, name)
-        return _FrameToken(gen=self.__dict__.get("_gen", 0), a=a, p=p, out=(ws, depth, image, aux_map), stats=stats, kms=kms, watch_state=watch_state, watch=watch, finished=finished, nears=nears, fars=fars,
-                           depth_raw=depth_raw, edit=edit,
-                           again=(rays_o, rays_d, None if aabb is not None else nears, None if aabb is not None else fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises),
-                           keep=(mip, bg_color, self.packed), noises=noises)
 
-    def _frame_post(self, tok):
-        valid = tok.valid if tok.valid is not None else _frame_valid(self, tok)
-        if valid == 1:
-            self._watch_failed()
-            return self._render_frame(*tok.again)
-        stats, kms = tok.stats, tok.kms
-        if valid == 2:
-            self._note_overflow()
-            return self._render_frame(*tok.again)
-        ws, depth, image, aux_map = tok.out
-        return ws, depth, image, aux_map, {"iterations": int(stats[0]), "rendered": int(stats[1]), "rows": int(stats[2]), "enqueued": int(stats[3]), "looks": int(stats[4]),
-                                           "grid_ms": float(kms[0]), "grid_launches": int(kms[1]), "finished": tok.finished, "depth_raw": tok.depth_raw,
-                                           "nears": tok.nears, "fars": tok.fars}
+    def _frame_outputs(self, tok, stats):
+        stats["depth_raw"] = tok.depth_raw
+        return tok.out + (stats,)
 
     @torch.no_grad()
     def network_forward(self, x, d):

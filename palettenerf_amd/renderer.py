@@ -379,6 +379,22 @@ class _RendererBase(nn.Module):
         with torch.no_grad():
             return pending.complete(pending.fused.frame_result(pending.tok))
 
+    def _native_frame(self, frame_args, frame_kw, phase, complete):
+        """run_cuda's native branch behind its arguments: the frame through self._fused -- prepared only (phase "prepare": render_prepare(); the frame itself goes
+        out in render_launch / render_finish) or rendered -- and `complete` for its result dict.  Under fp16 autocast (the reference's -O mode) the loop looks
+        the hash tables up as fp16 with the reference's half interpolation (gridencoder/grid.py:36-39), the field stays on its fp32-accurate matrix path;
+        outputs are fp32 as the reference's are."""
+        fused = self._fused
+        was_half = fused.table_half
+        fused.table_half = was_half or torch.is_autocast_enabled()
+        try:
+            if phase == "prepare":
+                return PendingFrame(fused, fused.frame_prepare(*frame_args, **frame_kw), complete)
+            ret = fused.render_frame(*frame_args, **frame_kw)
+        finally:
+            fused.table_half = was_half
+        return complete(ret)
+
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=4096, **kwargs):
         """nerf/renderer.py:564-603 / palette/renderer.py:554-573 -- never staged when cuda_ray."""
         if self.cuda_ray:
@@ -569,19 +585,8 @@ class NeRFRenderer(_OccupancyMaintenance, _RendererBase):
                 from .fused import NeRFFieldFused
                 self._fused = NeRFFieldFused(self)
             noises = _frame_noises(perturb, kwargs.get("noises"), N, rays_o)
-            # under fp16 autocast (the reference's -O mode) the loop looks the hash table up as fp16 with the reference's half interpolation
-            # (gridencoder/grid.py:36-39), the field stays on its fp32-accurate matrix path; outputs are fp32 as the reference's are
-            was_half = self._fused.table_half
-            self._fused.table_half = was_half or torch.is_autocast_enabled()
             frame_args = (rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh)
             frame_kw = dict(bg_color=bg_color, aabb=aabb if native_frame else None, min_near=self.min_near, noises=noises)
-            try:
-                if kwargs.get("_phase") == "prepare":   # render_prepare(): everything in front of the library call, now; the frame itself in render_launch / render_finish
-                    tok = self._fused.frame_prepare(*frame_args, **frame_kw)
-                else:
-                    ret = self._fused.render_frame(*frame_args, **frame_kw)
-            finally:
-                self._fused.table_half = was_half
 
             def complete(ret):
                 weights_sum, depth_acc, image_acc, stats = ret
@@ -603,9 +608,7 @@ class NeRFRenderer(_OccupancyMaintenance, _RendererBase):
                 results["weights_sum"] = weights_sum
                 return results
 
-            if kwargs.get("_phase") == "prepare":
-                return PendingFrame(self._fused, tok, complete)
-            return complete(ret)
+            return self._native_frame(frame_args, frame_kw, kwargs.get("_phase"), complete)
         else:
             def shade(st, n_alive, n_step, xyzs, dirs, deltas):
                 sigmas, rgbs = self(xyzs, dirs)
@@ -965,18 +968,9 @@ class PaletteRenderer(_RendererBase):
             return results
 
         if native:  # device-driven loop: same schedule and arithmetic, no per-iteration host sync (pnr_palette_render_frame)
-            was_half = self._fused.table_half
-            self._fused.table_half = was_half or torch.is_autocast_enabled()     # -O mode: fp16 tables with the reference's half interpolation
             frame_args = (rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh)
             frame_kw = dict(bg_color=bg_color, aabb=aabb if native_near_far else None, min_near=self.min_near,
                             noises=_frame_noises(perturb, kwargs.get("noises"), N, rays_o))
-            try:
-                if kwargs.get("_phase") == "prepare":   # render_prepare(): the frame itself goes out in render_launch / render_finish
-                    tok = self._fused.frame_prepare(*frame_args, **frame_kw)
-                else:
-                    ret = self._fused.render_frame(*frame_args, **frame_kw)
-            finally:
-                self._fused.table_half = was_half
 
             def complete(ret):
                 ws_n, depth_n, image_n, aux_n, stats = ret
@@ -988,9 +982,7 @@ class PaletteRenderer(_RendererBase):
                 # finished: the frame call's last launch applied the epilogue itself (same fp32 operations; eleven launches less)
                 return tail(st, aux_n, stats["finished"], stats, stats["nears"], stats["fars"])
 
-            if kwargs.get("_phase") == "prepare":
-                return PendingFrame(self._fused, tok, lambda ret: complete(ret))
-            return complete(ret)
+            return self._native_frame(frame_args, frame_kw, kwargs.get("_phase"), complete)
         if kwargs.get("noises") is not None:
             raise RuntimeError("noises= belongs to the native frame (march_mode = 'native', fused_field); the per-op loops draw their own with perturb")
         st = self._infer_loop(rays_o, rays_d, nears, fars, perturb, dt_gamma, max_steps, shade_fused if use_fused else shade)

@@ -977,11 +977,17 @@ def test_frame_call_computes_near_far_and_epilogue_itself(cuda, kind, sorted_ray
 
 
 @pytest.mark.gpu
-def test_kept_frame_arguments_follow_every_setting(cuda):
+@pytest.mark.parametrize("kind", ["nerf", "palette"])
+def test_kept_frame_arguments_follow_every_setting(cuda, kind):
     """The frame calls keep their argument struct between frames (fused.py: `_frame_plan`).  Everything the struct is filled from must be part of its key:
-    after each change of a setting, the same object's next frame equals the frame of a fresh PaletteFieldFused built after the change."""
-    from palettenerf_amd.fused import PaletteFieldFused, tile_ray_order
-    m = network.PaletteNetwork(renderer.default_opt(), bound=2, cuda_ray=True, density_scale=100.0)
+    after each change of a setting, the same object's next frame equals the frame of a fresh NeRFFieldFused / PaletteFieldFused built after the change."""
+    from palettenerf_amd.fused import NeRFFieldFused, PaletteFieldFused, tile_ray_order
+    if kind == "nerf":
+        m = network.NeRFNetwork(bound=2, cuda_ray=True, density_scale=100.0)
+        cls = NeRFFieldFused
+    else:
+        m = network.PaletteNetwork(renderer.default_opt(), bound=2, cuda_ray=True, density_scale=100.0)
+        cls = PaletteFieldFused
     scene.seed_field_(m, 0)
     m = m.to(cuda).eval()
     m.density_grid.copy_(torch.from_numpy(scene.brick_density_grid()).to(cuda))
@@ -990,26 +996,28 @@ def test_kept_frame_arguments_follow_every_setting(cuda):
     ro, rd = scene.get_rays(torch.from_numpy(scene.lookat_pose(azimuth_deg=40.0))[None], scene.intrinsics_from_fov(H, W), H, W)
     ro, rd = ro[0].to(cuda).contiguous(), rd[0].to(cuda).contiguous()
     N = H * W
-    kept = PaletteFieldFused(m)
+    kept = cls(m)
 
     def frames_agree(what):
-        fresh = PaletteFieldFused(m)
+        fresh = cls(m)
         fresh.ray_order, fresh.precision, fresh.table_half = kept.ray_order if hasattr(kept, "ray_order") else None, kept.precision, kept.table_half
         a = kept.render_frame(ro, rd, None, None, 0.0, 1024, 1e-4, bg_color=1, aabb=m.aabb_infer, min_near=m.min_near)
         b = fresh.render_frame(ro, rd, None, None, 0.0, 1024, 1e-4, bg_color=1, aabb=m.aabb_infer, min_near=m.min_near)
         assert a[-1]["rendered"] == b[-1]["rendered"] > 1000, what
-        for x, y in zip(a[:4], b[:4]):
+        assert len(a) == len(b) == (4 if kind == "nerf" else 5)
+        for x, y in zip(a[:-1], b[:-1]):          # every output: weights_sum, depth, image (and aux_map)
             assert torch.equal(x, y), what
         return a
 
     kept.ray_order = None
-    base = frames_agree("first frame")
+    base = v = frames_agree("first frame")
     frames_agree("second frame, nothing changed")
-    m.view_dep_weight = 0.25
-    v = frames_agree("view_dep_weight")
-    assert not torch.equal(v[2], base[2])
-    m.offsets_weight = 0.5
-    frames_agree("offsets_weight")
+    if kind == "palette":
+        m.view_dep_weight = 0.25
+        v = frames_agree("view_dep_weight")
+        assert not torch.equal(v[2], base[2])
+        m.offsets_weight = 0.5
+        frames_agree("offsets_weight")
     m.density_scale = 50.0
     d = frames_agree("density_scale")
     assert not torch.equal(d[0], v[0])
@@ -1018,9 +1026,20 @@ def test_kept_frame_arguments_follow_every_setting(cuda):
     kept.precision = 0
     frames_agree("precision fp32")
     kept.precision = 1
-    with torch.no_grad():
-        m.basis_color.add_(0.03)                       # an in-place torch op: the version counter moves
-    frames_agree("palette changed in place")
+    if kind == "nerf":
+        f = frames_agree("precision split-fp16 again")
+        kept.table_half = True
+        h = frames_agree("table_half on")
+        assert not torch.equal(h[2], f[2])
+        kept.table_half = False
+        g = frames_agree("table_half off")
+        assert torch.equal(g[2], f[2])
+    with torch.no_grad():                              # an in-place torch op: the version counter moves
+        if kind == "nerf":
+            m.color_net[1].weight.mul_(0.9)
+        else:
+            m.basis_color.add_(0.03)
+    frames_agree("weights / palette changed in place")
     m.density_grid.mul_(0.0).add_(torch.from_numpy(scene.brick_density_grid()).to(cuda).roll(3, dims=1))
     raymarching.packbits(m.density_grid, 0.5, m.density_bitfield)       # another occupancy grid: bitfield version, mip
     frames_agree("occupancy grid")
@@ -1031,8 +1050,8 @@ def test_kept_frame_arguments_follow_every_setting(cuda):
 def test_kept_frame_arguments_survive_a_stand_alone_field_call_at_another_precision(cuda, kind):
     """weights that fail the STATIC fp16 bound run the stand-alone ops (`model.forward` -> `self._fused(x, d)`) on the exact fp32 path
     (effective_precision() == 0) while the frame loops keep split-fp16 with the overflow watch (frame_precision()).  The stand-alone call repacks the blob for
-    ITS precision -- in place (NeRF) or into a new tensor (PaletteNeRF) -- so the frame call must not keep the blob's address or layout in its kept argument
-    struct: frame, stand-alone call, frame again = the same frame bit for bit, and equal to a fresh object's frame."""
+    ITS precision -- into a new tensor, its own blob of that precision (NeRF) or the one blob's replacement (PaletteNeRF) -- so the frame call must not keep
+    the blob's address or layout in its kept argument struct: frame, stand-alone call, frame again = the same frame bit for bit, and equal to a fresh object's frame."""
     from palettenerf_amd.fused import NeRFFieldFused, PaletteFieldFused
     if kind == "nerf":
         m = network.NeRFNetwork(bound=2, cuda_ray=True, density_scale=100.0)
@@ -1153,7 +1172,7 @@ def test_prepare_launch_finish_frames_equal_frames_rendered_one_by_one(cuda, kin
     tok_b = f.frame_prepare(ro[0], rd[0], None, None, 0.0, 1024, 1e-4, bg_color=1, aabb=m.aabb_infer, min_near=m.min_near)
     sub = lib.pnr_nerf_render_frame_submit if kind == "nerf" else lib.pnr_palette_render_frame_submit
     fin = lib.pnr_nerf_render_frame_finish if kind == "nerf" else lib.pnr_palette_render_frame_finish
-    arg = (lambda t: ctypes.byref(t.a)) if kind == "nerf" else (lambda t: ctypes.byref(t.p))
+    arg = lambda t: ctypes.byref(t.args)
     assert fin(arg(tok_a), None) == -1                         # nothing submitted
     f.frame_launch(tok_a)
     assert sub(arg(tok_b), tok_a.stream) == -1                 # one submitted frame per host thread and device
@@ -1332,7 +1351,7 @@ def test_finish_keeps_the_submit_stream_and_options(cuda, kind):
     rays = _queue_rays(cuda, 96, 128, 3, far_apart=True)
     (ro_long, rd_long), (ro_short, rd_short) = (rays[0][0][0], rays[0][1][0]), (rays[2][0][0], rays[2][1][0])
     fin = lib.pnr_nerf_render_frame_finish if kind == "nerf" else lib.pnr_palette_render_frame_finish
-    arg = (lambda t: ctypes.byref(t.a)) if kind == "nerf" else (lambda t: ctypes.byref(t.p))
+    arg = lambda t: ctypes.byref(t.args)
     args = lambda ro, rd: (ro, rd, None, None, 0.0, 1024, 1e-4)
     kw = dict(bg_color=1, aabb=m.aabb_infer, min_near=m.min_near)
 
