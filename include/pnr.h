@@ -372,13 +372,16 @@ int pnr_nerf_render_frame(const pnr_nerf_frame_args* args, pnr_stream_t stream);
  * launch and the 64-byte control-block read-back, and returns WITHOUT waiting: the host is free to prepare its next frame (rays, argument struct, outputs)
  * while this one runs -- the loop being replaced (nerf/renderer.py:344-380, palette/renderer.py:430-550) holds the host for the whole frame.  _finish waits for
  * the read-back, enqueues further iterations while the frame is not done (the iteration count is data) and fills `stats` / `kernel_ms`.  Rules: _finish follows
- * _submit on the same host thread, device and stream with the SAME argument struct (its address identifies the frame) whose N and workspace are unchanged --
- * PNR_ERR_INVALID otherwise, before anything is enqueued, and the frame stays submitted so that a correct _finish can still complete it; one submitted frame
- * per host thread and device (a second _submit is PNR_ERR_INVALID; a whole-frame call drops a submitted frame that was never finished); nothing the frame
- * reads or writes may be touched in between.  The frame keeps the pnr_set_option switches _submit saw (aux_fusion, composite_fusion, hosted_tail,
- * march_budget, march_budget0, march_blocks, iteration_margin, dynamic_tiles, block_skip, coop_march, palette_waves12): a pnr_set_option between the two
- * calls applies from the next frame on.  pnr_nerf_render_frame == _submit + _finish.  (`noises` is read by the frame's first iteration, which _submit
- * enqueues: it is one more input the caller leaves alone until _finish.) */
+ * _submit on the same host thread, device and stream with the SAME argument struct: its address identifies the frame, and its stream, N and workspace are
+ * checked -- PNR_ERR_INVALID otherwise, before anything is enqueued, and the frame stays submitted so that a correct _finish can still complete it.
+ * Everything else is what _submit saw: _submit derives the frame's whole configuration once and keeps it, _finish reads no other field of the struct (nor the
+ * HOST `edit` struct of a palette frame, which is copied), so a field rewritten between the two calls does not reach the frame; `stats` / `kernel_ms` are
+ * written through the pointers _submit was given.  One submitted frame per host thread and device (a second _submit is PNR_ERR_INVALID; a whole-frame call
+ * drops a submitted frame that was never finished); no DEVICE buffer the frame reads or writes may be touched in between.  The frame likewise keeps the
+ * pnr_set_option switches _submit saw (aux_fusion, composite_fusion, hosted_tail, march_budget, march_budget0, march_blocks, iteration_margin,
+ * dynamic_tiles, block_skip, coop_march, palette_waves12): a pnr_set_option between the two calls applies from the next frame on.
+ * pnr_nerf_render_frame == _submit + _finish.  (`noises` is read by the frame's first iteration, which _submit enqueues: it is one more input the caller
+ * leaves alone until _finish.) */
 int pnr_nerf_render_frame_submit(const pnr_nerf_frame_args* args, pnr_stream_t stream);
 int pnr_nerf_render_frame_finish(const pnr_nerf_frame_args* args, pnr_stream_t stream);
 

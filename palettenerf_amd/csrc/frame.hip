@@ -17,6 +17,7 @@
 #include "march_core.hpp"
 #include "grid_core.hpp"
 #include "field_core.hpp"
+#include "frame_plan.hpp"
 #include <hip/hip_ext.h>
 #include <vector>
 #include <stdlib.h>
@@ -43,7 +44,6 @@ struct FrameCtl {  // 64 bytes, two copies ping-ponged by iteration parity
 };
 static_assert(sizeof(FrameCtl) == 64, "FrameCtl layout");
 
-constexpr uint32_t kRayBlock = 256;
 constexpr uint32_t kHdr = 4;  // scratch header ints before the per-chunk counts
 
 // ------------------------------------------------------------------------------------------
@@ -61,10 +61,6 @@ struct StragglerRec { int32_t n, index, step; float t, last_t, far; int32_t pad0
 static_assert(sizeof(StragglerRec) == 32, "StragglerRec layout");
 constexpr int kQueueCtrs = 4;             // counters per set (two sets ping-ponged by iteration parity): [0] rays queued
 constexpr uint32_t kHostedBlocks = 256;   // workgroups of a lookup launch that serve the queue first (one wave per SIMD of the chip)
-#ifndef PNR_MAX_MARCH_BLOCKS
-#define PNR_MAX_MARCH_BLOCKS 4096   // (2048: a frame of 2 500 chunks gave 452 workgroups a second chunk behind their block barriers; first launch 88.1 -> 86.4 us on average)
-#endif
-constexpr uint32_t kMaxMarchBlocks = PNR_MAX_MARCH_BLOCKS;
 // What the hosted march tail needs on top of the lookup's own arguments.  The frame-constant part lives in the workspace (k_frame_begin
 // writes it there from its own arguments): the lookup kernels' argument block stays the size it had.
 struct HostedConst {
@@ -1146,8 +1142,6 @@ __global__ void __launch_bounds__(kRayBlock) k_frame_composite(const FrameCtl* _
     }
 }
 
-static inline uint64_t align256(uint64_t v) { return (v + 255) & ~uint64_t(255); }
-
 struct FrameWorkspace {
     FrameCtl* ctl;
     int32_t* alive[2];
@@ -1203,6 +1197,357 @@ static FrameWorkspace carve(void* base, uint32_t N, uint32_t aux_stride = 0, boo
     return w;
 }
 
+// The frame call's host driver.  A frame is PLANNED once (make_frame_plan: everything the loop needs that does not change from iteration to iteration, derived
+// from the caller's struct and the option switches as they are at that moment), BEGUN (frame_begin: the first launch), and then runs in chunks of iterations
+// (enqueue_chunk) between looks at the control block (frame_wait).  The whole-frame call is plan + begin + chunk + wait; _submit is plan + begin + chunk and
+// keeps plan and progress in the host thread's per-device record; _finish checks that it is given that frame and waits on the KEPT plan -- it derives nothing
+// a second time, so the chunks it enqueues cannot run under another configuration than the chunks already in the stream.
+// FrameOpts: the pnr_set_option switches a frame's launches depend on, read once per frame with the rest.
+struct FrameOpts {
+    int aux_fusion, composite_fusion, hosted_tail, dynamic_tiles, march_budget, march_budget0, march_blocks, iteration_margin, block_skip, coop_march, palette_waves12;
+};
+static FrameOpts frame_opts_now() {
+    return FrameOpts{g_opt_aux_fusion, g_opt_composite_fusion, g_opt_hosted_tail, g_opt_dynamic_tiles, g_opt_march_budget, g_opt_march_budget0, g_opt_march_blocks,
+                     g_opt_iteration_margin, g_opt_block_skip, g_opt_coop_march, g_opt_palette_waves12};
+}
+
+using UnsortKernel = decltype(&k_frame_unsort_outputs<4>);
+using MarchKernel = decltype(&k_frame_march<true, true, 1>);
+using GridKernel = decltype(&k_frame_grid);
+using FieldKernel = decltype(&k_frame_field<0, false>);
+
+struct FramePlan {
+    pnr_stream_t stream; const void* workspace;   // (with N: what a _finish call must be given again)
+    uint32_t N, max_steps, aux_stride, n_enc, march_lds;
+    float T_thresh, density_scale, enc_scale;
+    FrameWorkspace w;
+    // per-ray inputs and outputs in PROCESSING order (the caller's arrays, or the workspace copies of a frame with a ray_order) ...
+    const float *in_o, *in_d, *in_far, *noise_p;   // (the nears are only read by the first launch: rays_t; noise_p by processing slot, as the march indexes it)
+    float *out_ws, *out_depth, *out_image, *out_aux;
+    // ... and the caller's, by ray id, for the frame's last launch
+    const int32_t* ray_order;
+    float *ray_ws, *ray_depth, *ray_image, *ray_aux;
+    const uint8_t* bitfield; const uint32_t* mip; const float* packed_weights;
+    bool with_clip, half_tables, hosted, use_mip, pow2, pal_composite_fused, timing, has_edit;
+    int aux_fused;         // PaletteNeRF: the aux composite runs inside the field kernel
+    int composite_fused;   // NeRF: 1 = one-sample-per-ray iterations are composited inside the field kernel, 2 = all of them (no composite launch)
+    MarchParams mp;
+    GridArgs ga;
+    pnr_palette_field_args pf;   // PaletteNeRF: all but the fields an iteration sets (ctl, B, the alive list, the survivor counts, `edit`)
+    pnr_palette_edit edit;       // has_edit: RegionEdit / Stylizer, copied -- the field call looks at its mode per iteration, the parameters are uploaded once (frame_begin)
+    FrameFinish fin;
+    FrameOpts opt;
+    MarchKernel march, march_budgeted;   // MODE 1 for this frame's (mip, power-of-two) configuration; MODE 2 (hosted implies the mip and power-of-two configuration)
+    GridKernel lookup; uint32_t lookup_y, lookup_z;   // the lookup kernel of the frame's table layout and its grid behind x (levels, tables)
+    FieldKernel field;                                // NeRF: k_frame_field of (field_precision, watch_overflow)
+    uint64_t* stats; float* kernel_ms;                // HOST, optional
+};
+// What a chunk of iterations continues from.  alive_ub: host-side upper bound of n_alive (it only shrinks); prev_partials: workgroups of the previous march
+// launch (= sample partials to add up)
+struct FrameProgress { int iter = 0; uint32_t alive_ub = 0, chunk = 0, looks = 0, prev_partials = 0; size_t ev_used = 0; };
+// per host thread AND per device (a process may drive several GPUs): the pinned read-back slot, the timing events and the iteration
+// prediction of the previous frame rendered there
+// (released when the host thread ends: a pool that replaces its worker threads does not accumulate pinned blocks and events)
+struct PerDevice {
+    FrameCtl* host_ctl = nullptr; std::vector<hipEvent_t> ev; uint32_t predicted_iterations = 0; hipEvent_t done_ev = nullptr;
+    // a frame submitted and not yet finished (pnr_*_render_frame_submit): the struct it was submitted with, its plan and how far it got
+    struct Pending { bool on = false; const void* args = nullptr; FramePlan plan; FrameProgress prog; } pending;
+    ~PerDevice() {
+        if (host_ctl) (void)hipHostFree(host_ctl);
+        if (done_ev) (void)hipEventDestroy(done_ev);
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+};
+static PerDevice& frame_device() {
+    static thread_local PerDevice per_device[kMaxDevices];
+    return per_device[current_device()];
+}
+
+// the per-chunk survivor counts: iteration i fills counts_of(i), its march reads counts_of(i + 1)
+static int32_t* counts_of(const FramePlan& p, int parity) { return p.w.scratch + kHdr + (uint32_t)(parity & 1) * (p.N / kRayBlock + 2); }
+
+// The frame's last launch: outputs back to ray ids and the epilogue, a no-op unless `done_ctl` says the frame is done.
+static void launch_last(const FramePlan& p, const FrameCtl* done_ctl) {
+    FrameFinish fin = p.fin;
+    fin.ctl = done_ctl;
+    const bool sorted = p.ray_order != nullptr, aux = p.aux_stride != 0;
+    if (!sorted && !fin.on && !fin.depth_raw) return;   // nothing to move, nothing to apply
+    UnsortKernel kernel;
+    uint32_t blocks;   // lanes per ray: 32 / 16 with an aux row to move, 4 without (unsorted frame: the same kernel in place)
+    if (sorted && aux && p.aux_stride > 64) { kernel = k_frame_unsort_outputs<32>; blocks = cdiv(p.N, kRayBlock / 32); }
+    else if (sorted && aux) { kernel = k_frame_unsort_outputs<16>; blocks = cdiv(p.N * 16, kRayBlock); }
+    else { kernel = k_frame_unsort_outputs<4>; blocks = cdiv(p.N * 4, kRayBlock); }
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kRayBlock), 0, as_stream(p.stream), p.N, p.ray_order, p.out_ws, p.out_depth, p.out_image,
+                       sorted ? (const float*)p.out_aux : (const float*)nullptr, p.aux_stride, p.ray_ws, p.ray_depth, p.ray_image, p.ray_aux, fin);
+}
+
+static MarchKernel frame_march_kernel(bool mip, bool pow2, int mode) {
+    if (mode == 2) return k_frame_march<true, true, 2>;   // (hosted implies the mip and power-of-two configuration)
+    if (mip && pow2) return k_frame_march<true, true, 1>;
+    if (mip) return k_frame_march<true, false, 1>;
+    return pow2 ? k_frame_march<false, true, 1> : k_frame_march<false, false, 1>;
+}
+static FieldKernel frame_field_kernel(int precision, int watch_overflow) {
+    if (precision == PNR_FIELD_FP32) return k_frame_field<0, false>;
+    if (precision == PNR_FIELD_F16X2) return watch_overflow ? k_frame_field<2, true> : k_frame_field<2, false>;
+    return watch_overflow ? k_frame_field<1, true> : k_frame_field<1, false>;
+}
+
+// All validation and derivation of a frame; enqueues nothing.  N == 0: PNR_OK and plan->N == 0, there is no frame.
+static int make_frame_plan(const pnr_nerf_frame_args* a, const pnr_palette_frame_args* pal, pnr_stream_t stream, const FrameOpts& opt, FramePlan* plan) {
+    if (!a) return PNR_ERR_INVALID;
+    plan->N = a->N;
+    if (a->N == 0) return PNR_OK;
+    if (!a->rays_o || !a->rays_d || !a->nears || !a->fars || !a->bitfield || !a->embeddings || !a->offsets || !a->packed_weights || !a->weights_sum ||
+        !a->depth || !a->image || !a->workspace)
+        return PNR_ERR_INVALID;
+    if (a->C == 0 || a->C > 16 || a->H == 0 || a->max_steps == 0 || a->num_levels != 16) return PNR_ERR_UNSUPPORTED;
+    if (a->field_precision != PNR_FIELD_FP32 && a->field_precision != PNR_FIELD_F16X3 && a->field_precision != PNR_FIELD_F16X2) return PNR_ERR_UNSUPPORTED;
+    FramePlan& p = *plan;
+    p = FramePlan{};
+    p.stream = stream; p.workspace = a->workspace; p.N = a->N; p.max_steps = a->max_steps; p.T_thresh = a->T_thresh; p.density_scale = a->density_scale; p.opt = opt;
+    p.aux_stride = pal ? pnr_palette_aux_channels(pal->num_basis, pal->clip_dim) : 0;
+    p.with_clip = pal && pal->pred_clip;
+    const FrameWorkspace& w = p.w = carve(a->workspace, p.N, p.aux_stride, p.with_clip);
+    if (a->workspace_bytes < w.bytes) return PNR_ERR_INVALID;
+    FrameCtl*& host_ctl = frame_device().host_ctl;  // one in-flight frame per host thread and device
+    if (!host_ctl && hipHostMalloc(reinterpret_cast<void**>(&host_ctl), sizeof(FrameCtl), hipHostMallocPortable) != hipSuccess) return PNR_ERR_LAUNCH;
+
+    p.ray_order = a->ray_order;
+    p.ray_ws = a->weights_sum; p.ray_depth = a->depth; p.ray_image = a->image; p.ray_aux = pal ? pal->aux_map : nullptr;
+    const bool sorted = a->ray_order != nullptr;
+    p.in_o = sorted ? w.s_o : a->rays_o; p.in_d = sorted ? w.s_d : a->rays_d; p.in_far = sorted ? w.s_far : a->fars;
+    p.out_ws = sorted ? w.s_ws : p.ray_ws; p.out_depth = sorted ? w.s_depth : p.ray_depth; p.out_image = sorted ? w.s_image : p.ray_image;
+    p.out_aux = sorted ? w.s_aux : p.ray_aux;   // (w.s_aux is NULL without an aux map)
+    p.noise_p = a->noises ? (sorted ? w.s_noise : a->noises) : nullptr;
+    p.bitfield = a->bitfield; p.mip = static_cast<const uint32_t*>(a->mip); p.packed_weights = a->packed_weights;
+    p.stats = a->stats; p.kernel_ms = a->kernel_ms; p.timing = a->kernel_ms != nullptr;
+
+    p.n_enc = pal ? (p.with_clip ? 3u : 2u) : 1u;
+    p.aux_fused = (pal && opt.aux_fusion && pnr_palette_field_stages_aux(pal->num_basis, pal->clip_dim, pal->pred_clip)) ? 1 : 0;
+    p.composite_fused = (!pal && opt.composite_fusion) ? opt.composite_fusion : 0;
+    p.pal_composite_fused = pal && p.aux_fused && opt.composite_fusion == 2;   // PaletteNeRF: the ray state is composited inside the field kernel as well (needs the staged aux rows)
+    p.half_tables = a->table_dtype == PNR_DTYPE_F16;   // fp16 tables: nerf = `embeddings` as halves; palette = embeddings_pair (no clip head) or
+                                                       // embeddings_triple (clip head) as interleaved halves
+    if (p.half_tables && pal && (p.with_clip ? !pal->embeddings_triple : !pal->embeddings_pair)) return PNR_ERR_UNSUPPORTED;
+    if (a->table_dtype != PNR_DTYPE_F32 && a->table_dtype != PNR_DTYPE_F16) return PNR_ERR_UNSUPPORTED;
+
+    // the lookup launch: the kernel of the frame's table layout, its one table (interleaved kinds) or its n_enc separate ones
+    GridArgs& ga = p.ga;
+    ga.xyzs = w.xyzs; ga.deltas = w.deltas; ga.offsets = a->offsets; ga.lp = make_level_params(16, a->S, a->base_resolution); ga.level_stride = p.N;
+    ga.bound = a->bound; ga.two_bound = 2.0f * a->bound; ga.inv_two_bound = exact_reciprocal_or_zero(ga.two_bound);
+    ga.gridtype = a->gridtype;
+    ga.enc[0] = w.enc; ga.enc[1] = w.enc_pal; ga.enc[2] = w.enc_clip;
+    p.lookup_y = 16; p.lookup_z = 1;
+    if (p.half_tables && pal && p.with_clip) { p.lookup = k_frame_grid_h3; ga.table[0] = pal->embeddings_triple; }
+    else if (p.half_tables && pal) { p.lookup = k_frame_grid_h2; ga.table[0] = pal->embeddings_pair; }
+    else if (p.half_tables) { p.lookup = k_frame_grid_h1; ga.table[0] = a->embeddings; }
+    else if (pal && p.with_clip && pal->embeddings_triple) { p.lookup = k_frame_grid_triple; ga.table[0] = pal->embeddings_triple; }
+    else if (pal && !p.with_clip && pal->embeddings_pair) { p.lookup = k_frame_grid_pair; ga.table[0] = pal->embeddings_pair; p.lookup_y = PNR_FRAME_LEVEL_PAIRS_PAL ? 8 : 16; }
+    else {
+        p.lookup = k_frame_grid; p.lookup_y = PNR_FRAME_LEVEL_PAIRS == 2 ? 4 : (PNR_FRAME_LEVEL_PAIRS ? 8 : 16); p.lookup_z = p.n_enc;
+        ga.table[0] = a->embeddings; ga.table[1] = pal ? pal->embeddings_palette : nullptr; ga.table[2] = p.with_clip ? pal->embeddings_clip : nullptr;
+    }
+
+    if (pal) {
+        pnr_palette_field_args& pf = p.pf;
+        pf.enc = w.enc; pf.enc_palette = w.enc_pal; pf.enc_clip = w.enc_clip; pf.level_stride = p.N; pf.dirs = w.dirs; pf.deltas = w.deltas;
+        pf.packed = a->packed_weights; pf.num_basis = pal->num_basis;
+        pf.clip_dim = pal->clip_dim; pf.pred_clip = pal->pred_clip; pf.density_scale = a->density_scale; pf.offsets_weight = pal->offsets_weight;
+        pf.view_dep_weight = pal->view_dep_weight; pf.aux_stride = p.aux_stride; pf.sigmas = w.sigmas; pf.rgbs = w.rgbs; pf.aux = w.aux;
+        pf.precision = a->field_precision; pf.xyzs = w.xyzs;
+        for (int k = 0; k < 3; k++) pf.enc_scale[k] = a->enc_scale[k];
+        pf.overflow_flag = a->watch_overflow ? w.scratch + 1 : nullptr;
+        pf.tile_counter = opt.dynamic_tiles ? w.scratch + 2 : nullptr;
+        if (p.aux_fused) { pf.weights_sum = p.out_ws; pf.aux_map = p.out_aux; pf.T_thresh = a->T_thresh; }
+        if (p.pal_composite_fused) { pf.rays_t = w.rays_t; pf.weights_sum_rw = p.out_ws; pf.depth = p.out_depth; pf.image = p.out_image; }   // the field kernel does the whole compositing step: no composite launch
+        if (pal->edit && pal->edit->mode != 0) { p.has_edit = true; p.edit = *pal->edit; pf.edit_device = w.edit; }   // RegionEdit / Stylizer
+    } else {
+        p.enc_scale = a->enc_scale[0] > 0.0f ? a->enc_scale[0] : 1.0f;
+        p.field = frame_field_kernel(a->field_precision, a->watch_overflow);
+    }
+
+    p.use_mip = a->mip && (a->H % 4) == 0 && pnr_occupancy_mip_bytes(a->C, a->H) <= 64 * 1024;
+    p.pow2 = is_pow2f(a->bound) && (a->H & (a->H - 1)) == 0;
+    p.mp = make_march_params(a->bound, a->dt_gamma, a->max_steps, a->C, a->H, p.use_mip);
+    p.mp.block_skip = opt.block_skip ? 1u : 0u; p.mp.coop = opt.coop_march ? 1u : 0u;   // (the frame's snapshot, not the switches as they are now)
+    p.march_lds = p.mp.mip_words ? (2 * p.mp.mip_words + 8) * 4 : 0;
+    p.hosted = opt.hosted_tail && p.use_mip && p.pow2 && p.mp.mip_words != 0 && (a->H % 64u) == 0;   // (what MODE 2 and hosted_march_tail are compiled for)
+    p.march = frame_march_kernel(p.use_mip, p.pow2, 1); p.march_budgeted = frame_march_kernel(true, true, 2);
+
+    FrameFinish& fin = p.fin;
+    fin.on = a->finish; fin.bg[0] = a->bg_color[0]; fin.bg[1] = a->bg_color[1]; fin.bg[2] = a->bg_color[2];
+    fin.bg_map = a->bg_map; fin.nears = a->nears; fin.fars = a->fars;   // indexed by ray id
+    fin.depth_raw = a->depth_raw;
+    return PNR_OK;
+}
+
+// A frame's first launches: the edit parameters, the zeroed aux map and k_frame_begin (the caller's struct is the one the plan was made from).
+static int frame_begin(const pnr_nerf_frame_args* a, const FramePlan& p) {
+    const FrameWorkspace& w = p.w;
+    hipStream_t s = as_stream(p.stream);
+    if (p.has_edit) {   // uploaded once for the whole frame
+        const int rc = pnr_internal_edit_upload(&p.edit, w.edit, s);
+        if (rc != PNR_OK) return rc;
+    }
+    HostedConst hconst = {};
+    hconst.qctr_all = w.qctr; hconst.qrecs = w.qrecs; hconst.rays_o = p.in_o; hconst.rays_d = p.in_d; hconst.bitfield = p.bitfield; hconst.mip = p.mip; hconst.p = p.mp;
+    hconst.xyzs = w.xyzs; hconst.dirs = w.dirs; hconst.deltas = w.deltas; hconst.partials[0] = w.partials[0]; hconst.partials[1] = w.partials[1];
+    FrameBegin fb = {};
+    fb.order = a->ray_order; fb.rays_o = a->rays_o; fb.rays_d = a->rays_d; fb.nears_in = a->nears; fb.fars_in = a->fars;
+    fb.aabb = a->aabb; fb.min_near = a->min_near; fb.nears_out = a->nears; fb.fars_out = a->fars;
+    fb.so = w.s_o; fb.sd = w.s_d; fb.sf = w.s_far; fb.noises = a->noises; fb.snoise = w.s_noise;
+    if (p.aux_stride) {   // the aux map starts at zero (palette/renderer.py:436-441): inside the first launch when rows are float4-aligned
+        if ((p.aux_stride & 3u) == 0 && (reinterpret_cast<uintptr_t>(p.out_aux) & 15u) == 0) { fb.aux_zero = p.out_aux; fb.aux_stride = p.aux_stride; }
+        else if (hipMemsetAsync(p.out_aux, 0, (size_t)p.N * p.aux_stride * 4, s) != hipSuccess) return PNR_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(k_frame_begin, dim3(cdiv(p.N, kRayBlock)), dim3(kRayBlock), 0, s, p.N, fb, w.alive[1], w.rays_t, p.out_ws, p.out_depth, p.out_image,
+                       w.ctl, counts_of(p, 1), w.scratch, w.qctr, hconst, w.hosted);
+    return PNR_OK;
+}
+
+// optional live timing of the roofline kernel: the device's pool of HIP events, two per lookup launch
+static hipEvent_t next_event(PerDevice& dev, FrameProgress& g) {
+    if (g.ev_used == dev.ev.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return nullptr; dev.ev.push_back(e); }
+    return dev.ev[g.ev_used++];
+}
+
+// Iteration g.iter: march, lookup, field and (unless the field kernel does it) composite; look: the control block is read back behind the march.
+static int enqueue_iteration(const FramePlan& p, FrameProgress& g, PerDevice& dev, bool look) {
+    const FrameWorkspace& w = p.w;
+    hipStream_t s = as_stream(p.stream);
+    const int iter = g.iter;
+    FrameCtl* cur = w.ctl + (iter & 1);                 // this iteration's control block, written by its march launch
+    const FrameCtl* prev = w.ctl + ((iter + 1) & 1);    // the previous iteration's (k_frame_begin's in front of iteration 0)
+    int32_t* alive_in = w.alive[iter & 1];              // this iteration's compacted list (the march writes it, the composite punches holes)
+    const int32_t* alive_prev = w.alive[(iter + 1) & 1];
+    const uint32_t rows_ub = rows_upper_bound(g.alive_ub, p.N);
+    const uint32_t budget = march_budget(p.hosted, iter, p.opt.march_budget0, p.opt.march_budget);
+    const int mode = march_mode(budget);
+    const dim3 gm(march_blocks(g.alive_ub, mode, p.opt.march_blocks)), bm(kRayBlock);
+    hipLaunchKernelGGL(mode == 2 ? p.march_budgeted : p.march, gm, bm, p.march_lds, s, prev, cur, alive_prev, alive_in, counts_of(p, iter + 1), counts_of(p, iter),
+                       w.scratch, p.N, p.max_steps, w.partials[(iter + 1) & 1], g.prev_partials, w.rays_t, p.in_o, p.in_d, p.mp, p.bitfield, p.in_far, w.xyzs, w.dirs,
+                       w.deltas, p.mip, w.partials[iter & 1], budget, w.qctr, w.qrecs, w.rowflag, p.noise_p);
+    if (look) {
+        // The look: the march launch is the only writer of the control block (sample and row totals of everything in front of it, the overflow flag,
+        // `done`), so the chunk's last one is read back right behind itself -- the host wakes up while that iteration's lookup and field
+        // launches (empty when the frame is done, which is what the chunk length bets on) and the frame's last launch are still running.
+        // Wait for THIS read-back, not for the stream: another host thread may already have queued the next frame behind it (pipeline.FramesInFlight
+        // with a shared stream: frames back to back without the host's gap between them, kernels never overlapping)
+        if (hipMemcpyAsync(dev.host_ctl, cur, sizeof(FrameCtl), hipMemcpyDeviceToHost, s) != hipSuccess) return PNR_ERR_LAUNCH;
+        if (!dev.done_ev && hipEventCreateWithFlags(&dev.done_ev, hipEventDisableTiming) != hipSuccess) return PNR_ERR_LAUNCH;
+        if (hipEventRecord(dev.done_ev, s) != hipSuccess) return PNR_ERR_LAUNCH;
+    }
+    const uint32_t gxc = lookup_blocks_capped(rows_ub);
+    HostedArgs ha = {};
+    if (mode == 2) { ha.hc = w.hosted; ha.rowflag = w.rowflag; ha.blocks = kHostedBlocks; ha.partial_base = gm.x; ha.gx = gxc; ha.n_tab = p.n_enc; }
+    // live timing of the roofline kernel: the launch carries its own start / stop events (hipExtLaunchKernelGGL: the dispatch's begin and end
+    // time stamps, what rocprofv3 reports) -- events recorded around the launch are packets of their own and measured 79.7 us where the
+    // kernel took 71.0
+    hipEvent_t e0 = p.timing ? next_event(dev, g) : nullptr, e1 = p.timing ? next_event(dev, g) : nullptr;
+    // (with hosted workgroups the launch is one-dimensional: they come first, see HostedArgs)
+    hipExtLaunchKernelGGL(p.lookup, ha.blocks ? dim3(ha.blocks + gxc * p.lookup_y * p.lookup_z) : dim3(gxc, p.lookup_y, p.lookup_z), dim3(256),
+                          mode == 2 ? p.march_lds : 0u, s, e0, e1, 0, cur, p.ga, ha);
+    if (p.aux_stride) {
+        pnr_palette_field_args pf = p.pf;
+        pf.ctl = cur; pf.B = rows_ub; pf.edit = p.has_edit ? &p.edit : nullptr;
+        if (p.aux_fused) pf.rays_alive = alive_in;
+        if (p.pal_composite_fused) { pf.rays_alive_rw = alive_in; pf.counts_cur = counts_of(p, iter); }
+        const int rc = pnr_internal_palette_field_forward(&pf, p.stream, p.opt.palette_waves12);
+        if (rc != PNR_OK) return rc;
+    } else
+        hipLaunchKernelGGL(p.field, dim3(field_blocks(rows_ub)), dim3(kFieldThreads), 0, s, cur, w.enc, p.N, w.dirs, w.deltas, p.packed_weights, p.density_scale,
+                           p.enc_scale, w.sigmas, w.rgbs, p.composite_fused, p.T_thresh, alive_in, w.rays_t, p.out_ws, p.out_depth, p.out_image, w.scratch,
+                           counts_of(p, iter));
+    if (p.composite_fused != 2 && !p.pal_composite_fused)   // (the field kernels composite every iteration themselves)
+        hipLaunchKernelGGL(k_frame_composite, gm, bm, 0, s, cur, p.T_thresh, alive_in, w.rays_t, w.sigmas, w.rgbs, w.deltas, p.out_ws, p.out_depth, p.out_image,
+                           counts_of(p, iter), (const float*)w.aux, p.out_aux, p.aux_stride, p.aux_fused, p.composite_fused);
+    g.prev_partials = gm.x + ha.blocks;
+    return PNR_OK;
+}
+
+// g.chunk iterations, the look behind the last one's march, and the frame's last launch.
+static int enqueue_chunk(const FramePlan& p, FrameProgress& g, PerDevice& dev) {
+    for (uint32_t k = 0; k < g.chunk; k++, g.iter++)
+        if (int rc = enqueue_iteration(p, g, dev, k + 1 == g.chunk)) return rc;
+    // The frame's last launch goes out BEHIND the read-back and BEFORE the host waits for it: the kernel looks at the same control block and does
+    // nothing unless the frame is done, so a chunk that fell short costs an empty launch -- and when the guess holds (nearly always along a camera
+    // path) the host wakes up, returns and prepares the caller's next frame while this launch runs, instead of launching it after waking up
+    // (an eighth of the garden frame: 0.40 of 2.4 ms were the host's turnaround between frames).  The in-place finish of an unsorted frame is
+    // not idempotent across looks either way: guarded by the same flag.
+    launch_last(p, p.w.ctl + ((g.iter - 1) & 1));
+    return PNR_OK;
+}
+
+// Wait for the chunk in the stream; while the frame is not done (the iteration count is data), enqueue another one.  Then the prediction for the next
+// frame, kernel_ms and stats.
+static int frame_wait(const FramePlan& p, FrameProgress& g, PerDevice& dev) {
+    const FrameCtl* host_ctl = dev.host_ctl;
+    for (;;) {
+        if (hipEventSynchronize(dev.done_ev) != hipSuccess) return PNR_ERR_LAUNCH;     // (polling hipEventQuery instead measured the same: the runtime's wait already spins)
+        if (host_ctl->done) break;
+        g.alive_ub = (uint32_t)host_ctl->n_alive;
+        g.chunk = next_chunk(g.chunk, g.looks, dev.predicted_iterations);
+        if (int rc = enqueue_chunk(p, g, dev)) return rc;
+    }
+    dev.predicted_iterations = (uint32_t)host_ctl->iterations;
+    if (p.timing) {  // only the iterations that did work (the tail of the last chunk are no-op launches)
+        float total = 0.0f;
+        uint32_t counted = 0;
+        for (size_t i = 0; i + 1 < g.ev_used && counted < (uint32_t)host_ctl->iterations; i += 2, counted++) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, dev.ev[i], dev.ev[i + 1]) == hipSuccess) total += ms;
+        }
+        p.kernel_ms[0] = total;
+        p.kernel_ms[1] = (float)counted * (float)p.lookup_z;  // a k_frame_grid launch covers n_enc tables (count table-launches); the interleaved kinds (pair, triple, h1 .. h3) are one launch for all
+    }
+    if (p.stats) {
+        p.stats[0] = (uint64_t)host_ctl->iterations;
+        p.stats[1] = host_ctl->rendered;
+        p.stats[2] = host_ctl->rows;
+        p.stats[3] = (uint64_t)g.iter;  // iterations enqueued (>= executed)
+        p.stats[4] = (uint64_t)g.looks + 1;  // host looks at the control block (stream synchronisations) this frame took
+        p.stats[5] = (uint64_t)(host_ctl->pad0 != 0);  // an operand of the split-fp16 field left fp16's range (watch_overflow): render again in fp32
+    }
+    return check_launch();
+}
+
+// kWhole = the frame call; kSubmit = enqueue the frame's first chunk of iterations, its last launch and the control-block read-back, then return WITHOUT
+// waiting (the caller prepares its next frame while this one runs); kFinish = wait for that read-back, enqueue further chunks while the frame is not done,
+// fill stats / kernel_ms.  `args` is the struct the caller passed: its address names a submitted frame.
+enum FramePhase { kWhole = 0, kSubmit = 1, kFinish = 2 };
+static int render_frame_impl(const void* args, const pnr_nerf_frame_args* a, const pnr_palette_frame_args* pal, pnr_stream_t stream, FramePhase phase) {
+    if (phase == kFinish) {
+        // _finish continues exactly the frame _submit started.  Every check comes before anything is enqueued: a finish with another stream, frame size or
+        // workspace is refused and the frame stays pending, so that the right finish call can still complete it.  Nothing else of the struct is read.
+        if (!a) return PNR_ERR_INVALID;
+        if (a->N == 0) return PNR_OK;
+        PerDevice& dev = frame_device();
+        PerDevice::Pending& pending = dev.pending;
+        if (!pending.on || pending.args != args) return PNR_ERR_INVALID;   // no frame of THIS struct was submitted on this thread and device
+        if (pending.plan.stream != stream || pending.plan.N != a->N || pending.plan.workspace != a->workspace) return PNR_ERR_INVALID;
+        pending.on = false;
+        return frame_wait(pending.plan, pending.prog, dev);
+    }
+    FramePlan plan;
+    const int rc = make_frame_plan(a, pal, stream, frame_opts_now(), &plan);
+    if (rc != PNR_OK || plan.N == 0) return rc;
+    PerDevice& dev = frame_device();
+    // one submitted frame per host thread and device: a second _submit is refused (finish the first one).  A WHOLE-frame call drops a submitted frame that
+    // was never finished (the caller gave it up -- an exception between its two halves): its launches are in the stream in front of this frame's, nothing
+    // waits for them any more, and this call would otherwise be refused for as long as the thread lives.
+    if (dev.pending.on && phase == kSubmit) return PNR_ERR_INVALID;
+    dev.pending.on = false;
+    FrameProgress prog;
+    prog.alive_ub = plan.N;
+    prog.chunk = first_chunk(dev.predicted_iterations, (uint32_t)plan.opt.iteration_margin);
+    if (int rc2 = frame_begin(a, plan)) return rc2;
+    if (int rc2 = enqueue_chunk(plan, prog, dev)) return rc2;
+    if (phase == kWhole) return frame_wait(plan, prog, dev);
+    dev.pending.args = args; dev.pending.plan = plan; dev.pending.prog = prog; dev.pending.on = true;
+    return check_launch();
+}
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -1238,365 +1583,22 @@ uint64_t pnr_palette_frame_workspace_bytes(uint32_t N, uint32_t num_basis, uint3
     return carve(nullptr, N, pnr_palette_aux_channels(num_basis, clip_dim), pred_clip != 0).bytes;
 }
 
-// phase: kWhole = the frame call; kSubmit = enqueue the frame's first chunk of iterations, its last launch and the control-block read-back, then return WITHOUT
-// waiting (the caller prepares its next frame while this one runs); kFinish = wait for that read-back, enqueue further chunks while the frame is not done (the
-// iteration count is data), fill stats / kernel_ms.  kFinish must follow kSubmit on the same host thread, device, stream and argument struct, with nothing of the
-// frame's buffers touched in between (the stream, N and the workspace are checked; the option switches are the ones kSubmit read); kWhole = kSubmit + kFinish.
-enum FramePhase { kWhole = 0, kSubmit = 1, kFinish = 2 };
-// The pnr_set_option switches a frame's launches depend on, read ONCE per frame: by kWhole / kSubmit, and kept for kFinish in the submitted frame's record,
-// so that a pnr_set_option between the two halves cannot give the finish call's chunks another configuration than the chunks already in the stream.
-struct FrameOpts {
-    int aux_fusion, composite_fusion, hosted_tail, dynamic_tiles, march_budget, march_budget0, march_blocks, iteration_margin, block_skip, coop_march, palette_waves12;
-};
-static FrameOpts frame_opts_now() {
-    FrameOpts o;
-    o.aux_fusion = g_opt_aux_fusion; o.composite_fusion = g_opt_composite_fusion; o.hosted_tail = g_opt_hosted_tail; o.dynamic_tiles = g_opt_dynamic_tiles;
-    o.march_budget = g_opt_march_budget; o.march_budget0 = g_opt_march_budget0; o.march_blocks = g_opt_march_blocks; o.iteration_margin = g_opt_iteration_margin;
-    o.block_skip = g_opt_block_skip; o.coop_march = g_opt_coop_march; o.palette_waves12 = g_opt_palette_waves12;
-    return o;
-}
-static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_frame_args* pal, pnr_stream_t stream, FramePhase phase);
+int pnr_nerf_render_frame(const pnr_nerf_frame_args* a, pnr_stream_t stream) { return render_frame_impl(a, a, nullptr, stream, kWhole); }
+int pnr_nerf_render_frame_submit(const pnr_nerf_frame_args* a, pnr_stream_t stream) { return render_frame_impl(a, a, nullptr, stream, kSubmit); }
+int pnr_nerf_render_frame_finish(const pnr_nerf_frame_args* a, pnr_stream_t stream) { return render_frame_impl(a, a, nullptr, stream, kFinish); }
 
-int pnr_nerf_render_frame(const pnr_nerf_frame_args* a, pnr_stream_t stream) { return render_frame_impl(a, nullptr, stream, kWhole); }
-int pnr_nerf_render_frame_submit(const pnr_nerf_frame_args* a, pnr_stream_t stream) { return render_frame_impl(a, nullptr, stream, kSubmit); }
-int pnr_nerf_render_frame_finish(const pnr_nerf_frame_args* a, pnr_stream_t stream) { return render_frame_impl(a, nullptr, stream, kFinish); }
-
-static int palette_frame_check(const pnr_palette_frame_args* p) {
+static int palette_frame(const pnr_palette_frame_args* p, pnr_stream_t stream, FramePhase phase) {
     if (!p) return PNR_ERR_INVALID;
-    if (p->num_basis < 1 || p->num_basis > PNR_MAX_BASIS || p->clip_dim > PNR_MAX_CLIP) return PNR_ERR_UNSUPPORTED;
-    if (p->edit && (p->edit->mode < 0 || p->edit->mode > 2)) return PNR_ERR_UNSUPPORTED;
-    if (p->base.N && (!p->embeddings_palette || !p->aux_map || (p->pred_clip && !p->embeddings_clip))) return PNR_ERR_INVALID;
-    return PNR_OK;
+    if (phase != kFinish) {   // (a frame being finished was checked when it was submitted)
+        if (p->num_basis < 1 || p->num_basis > PNR_MAX_BASIS || p->clip_dim > PNR_MAX_CLIP) return PNR_ERR_UNSUPPORTED;
+        if (p->edit && (p->edit->mode < 0 || p->edit->mode > 2)) return PNR_ERR_UNSUPPORTED;
+        if (p->base.N && (!p->embeddings_palette || !p->aux_map || (p->pred_clip && !p->embeddings_clip))) return PNR_ERR_INVALID;
+    }
+    return render_frame_impl(p, &p->base, p, stream, phase);
 }
-int pnr_palette_render_frame(const pnr_palette_frame_args* p, pnr_stream_t stream) {
-    if (int rc = palette_frame_check(p)) return rc;
-    return render_frame_impl(&p->base, p, stream, kWhole);
-}
-int pnr_palette_render_frame_submit(const pnr_palette_frame_args* p, pnr_stream_t stream) {
-    if (int rc = palette_frame_check(p)) return rc;
-    return render_frame_impl(&p->base, p, stream, kSubmit);
-}
-int pnr_palette_render_frame_finish(const pnr_palette_frame_args* p, pnr_stream_t stream) {
-    if (int rc = palette_frame_check(p)) return rc;
-    return render_frame_impl(&p->base, p, stream, kFinish);
-}
-
-static int render_frame_impl(const pnr_nerf_frame_args* a, const pnr_palette_frame_args* pal, pnr_stream_t stream, FramePhase phase) {
-    if (!a) return PNR_ERR_INVALID;
-    if (a->N == 0) return PNR_OK;
-    if (!a->rays_o || !a->rays_d || !a->nears || !a->fars || !a->bitfield || !a->embeddings || !a->offsets || !a->packed_weights || !a->weights_sum ||
-        !a->depth || !a->image || !a->workspace)
-        return PNR_ERR_INVALID;
-    if (a->C == 0 || a->C > 16 || a->H == 0 || a->max_steps == 0 || a->num_levels != 16) return PNR_ERR_UNSUPPORTED;
-    if (a->field_precision != PNR_FIELD_FP32 && a->field_precision != PNR_FIELD_F16X3 && a->field_precision != PNR_FIELD_F16X2) return PNR_ERR_UNSUPPORTED;
-    const uint32_t aux_stride = pal ? pnr_palette_aux_channels(pal->num_basis, pal->clip_dim) : 0;
-    const bool with_clip = pal && pal->pred_clip;
-    hipStream_t s = as_stream(stream);
-    const uint32_t N = a->N;
-    FrameWorkspace w = carve(a->workspace, N, aux_stride, with_clip);
-    if (a->workspace_bytes < w.bytes) return PNR_ERR_INVALID;
-    const bool sorted = a->ray_order != nullptr;
-    const float *in_o = a->rays_o, *in_d = a->rays_d, *in_far = a->fars;   // (the nears are only read by the first launch: rays_t)
-    float *out_ws = a->weights_sum, *out_depth = a->depth, *out_image = a->image, *out_aux = pal ? pal->aux_map : nullptr;
-    if (sorted) {
-        in_o = w.s_o; in_d = w.s_d; in_far = w.s_far;
-        out_ws = w.s_ws; out_depth = w.s_depth; out_image = w.s_image; out_aux = pal ? w.s_aux : nullptr;
-    }
-    // per host thread AND per device (a process may drive several GPUs): the pinned read-back slot, the timing events and the iteration
-    // prediction of the previous frame rendered there
-    // (released when the host thread ends: a pool that replaces its worker threads does not accumulate pinned blocks and events)
-    struct PerDevice {
-        FrameCtl* host_ctl = nullptr; std::vector<hipEvent_t> ev; uint32_t predicted_iterations = 0; hipEvent_t done_ev = nullptr;
-        // a frame submitted and not yet finished (pnr_*_render_frame_submit): what its finish call continues from, and what it must be continued WITH --
-        // the stream, the frame's size and workspace (checked) and the option snapshot its launches were shaped by (reused)
-        struct Pending {
-            bool on = false; const void* args = nullptr; int iter = 0; uint32_t alive_ub = 0, chunk = 0, looks = 0, prev_partials = 0; size_t ev_used = 0;
-            pnr_stream_t stream = nullptr; uint32_t N = 0; const void* workspace = nullptr; FrameOpts opts = {};
-        } pending;
-        ~PerDevice() {
-            if (host_ctl) (void)hipHostFree(host_ctl);
-            if (done_ev) (void)hipEventDestroy(done_ev);
-            for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        }
-    };
-    static thread_local PerDevice per_device[kMaxDevices];
-    PerDevice& dev_state = per_device[current_device()];
-    FrameCtl*& host_ctl = dev_state.host_ctl;  // one in-flight frame per host thread and device
-    if (!host_ctl && hipHostMalloc(reinterpret_cast<void**>(&host_ctl), sizeof(FrameCtl), hipHostMallocPortable) != hipSuccess) return PNR_ERR_LAUNCH;
-
-    auto& pending = dev_state.pending;
-    // _finish continues exactly the frame _submit started.  Every check comes before anything is enqueued: a finish with another stream, frame size or workspace
-    // would launch over another carve of the workspace (or into another stream) -- it is refused and the frame stays pending, so that the right finish call
-    // can still complete it.
-    if (phase == kFinish) {
-        if (!pending.on || pending.args != static_cast<const void*>(pal ? static_cast<const void*>(pal) : static_cast<const void*>(a))) return PNR_ERR_INVALID;   // no frame of THIS struct was submitted on this thread and device
-        if (pending.stream != stream || pending.N != a->N || pending.workspace != a->workspace) return PNR_ERR_INVALID;
-    }
-    const FrameOpts opt = phase == kFinish ? pending.opts : frame_opts_now();
-
-    const float* tables[3] = {a->embeddings, pal ? pal->embeddings_palette : nullptr, with_clip ? pal->embeddings_clip : nullptr};
-    const uint32_t n_enc = pal ? (with_clip ? 3u : 2u) : 1u;
-    const int aux_fused = (pal && opt.aux_fusion && pnr_palette_field_stages_aux(pal->num_basis, pal->clip_dim, pal->pred_clip)) ? 1 : 0;
-    const int composite_fused = (!pal && opt.composite_fusion) ? opt.composite_fusion : 0;   // NeRF: 1 = one-sample-per-ray iterations are composited inside the field kernel, 2 = all of them (no composite launch)
-    const bool pal_composite_fused = pal && aux_fused && opt.composite_fusion == 2;   // PaletteNeRF: the ray state is composited inside the field kernel as well (needs the staged aux rows)
-    const bool half_tables = a->table_dtype == PNR_DTYPE_F16;   // fp16 tables: nerf = `embeddings` as halves; palette = embeddings_pair (no clip head) or
-                                                                // embeddings_triple (clip head) as interleaved halves
-    if (half_tables && pal && (with_clip ? !pal->embeddings_triple : !pal->embeddings_pair)) return PNR_ERR_UNSUPPORTED;
-    if (a->table_dtype != PNR_DTYPE_F32 && a->table_dtype != PNR_DTYPE_F16) return PNR_ERR_UNSUPPORTED;
-    const float4* pair_table = (pal && !half_tables && !with_clip && pal->embeddings_pair) ? reinterpret_cast<const float4*>(pal->embeddings_pair) : nullptr;
-    const float4* triple_table = (pal && !half_tables && with_clip && pal->embeddings_triple) ? reinterpret_cast<const float4*>(pal->embeddings_triple) : nullptr;
-    pnr_palette_field_args pf = {};
-    if (pal) {
-        pf.enc = w.enc; pf.enc_palette = w.enc_pal; pf.enc_clip = w.enc_clip; pf.level_stride = N; pf.dirs = w.dirs; pf.deltas = w.deltas;
-        pf.packed = a->packed_weights; pf.num_basis = pal->num_basis;
-        pf.clip_dim = pal->clip_dim; pf.pred_clip = pal->pred_clip; pf.density_scale = a->density_scale; pf.offsets_weight = pal->offsets_weight;
-        pf.view_dep_weight = pal->view_dep_weight; pf.aux_stride = aux_stride; pf.sigmas = w.sigmas; pf.rgbs = w.rgbs; pf.aux = w.aux;
-        pf.precision = a->field_precision; pf.xyzs = w.xyzs;
-        for (int k = 0; k < 3; k++) pf.enc_scale[k] = a->enc_scale[k];
-        pf.overflow_flag = a->watch_overflow ? w.scratch + 1 : nullptr;
-        pf.tile_counter = opt.dynamic_tiles ? w.scratch + 2 : nullptr;
-        if (pal->edit && pal->edit->mode != 0) {   // RegionEdit / Stylizer: parameters uploaded once for the whole frame
-            if (phase != kFinish) {
-                const int rc = pnr_internal_edit_upload(pal->edit, w.edit, s);
-                if (rc != PNR_OK) return rc;
-            }
-            pf.edit = pal->edit; pf.edit_device = w.edit;
-        }
-    }
-
-    const float enc_scale = a->enc_scale[0] > 0.0f ? a->enc_scale[0] : 1.0f;
-    const bool use_mip = a->mip && (a->H % 4) == 0 && pnr_occupancy_mip_bytes(a->C, a->H) <= 64 * 1024;
-    const bool pow2 = is_pow2f(a->bound) && (a->H & (a->H - 1)) == 0;
-    MarchParams mp = make_march_params(a->bound, a->dt_gamma, a->max_steps, a->C, a->H, use_mip);
-    mp.block_skip = opt.block_skip ? 1u : 0u; mp.coop = opt.coop_march ? 1u : 0u;   // (the frame's snapshot, not the switches as they are now)
-    const uint32_t march_lds = mp.mip_words ? (2 * mp.mip_words + 8) * 4 : 0;
-    const LevelParams lp = make_level_params(16, a->S, a->base_resolution);
-    const uint32_t* mip = static_cast<const uint32_t*>(a->mip);
-    const bool hosted = opt.hosted_tail && use_mip && pow2 && mp.mip_words != 0 && (a->H % 64u) == 0;   // (what MODE 2 and hosted_march_tail are compiled for)
-
-    const uint32_t cstride = N / kRayBlock + 2;
-    auto counts_of = [&](int parity) { return w.scratch + kHdr + (uint32_t)(parity & 1) * cstride; };   // iteration i fills counts_of(i), its march reads counts_of(i + 1)
-    HostedConst hconst = {};
-    hconst.qctr_all = w.qctr; hconst.qrecs = w.qrecs; hconst.rays_o = in_o; hconst.rays_d = in_d; hconst.bitfield = a->bitfield; hconst.mip = mip; hconst.p = mp;
-    hconst.xyzs = w.xyzs; hconst.dirs = w.dirs; hconst.deltas = w.deltas; hconst.partials[0] = w.partials[0]; hconst.partials[1] = w.partials[1];
-    FrameBegin fb = {};
-    fb.order = a->ray_order; fb.rays_o = a->rays_o; fb.rays_d = a->rays_d; fb.nears_in = a->nears; fb.fars_in = a->fars;
-    fb.aabb = a->aabb; fb.min_near = a->min_near; fb.nears_out = a->nears; fb.fars_out = a->fars;
-    fb.so = w.s_o; fb.sd = w.s_d; fb.sf = w.s_far; fb.noises = a->noises; fb.snoise = w.s_noise;
-    const float* noise_p = a->noises ? (sorted ? w.s_noise : a->noises) : nullptr;   // by processing slot, as the march indexes it
-    if (phase != kFinish) {
-        // one submitted frame per host thread and device: a second _submit is refused (finish the first one).  A WHOLE-frame call drops a submitted frame that
-        // was never finished (the caller gave it up -- an exception between its two halves): its launches are in the stream in front of this frame's, nothing
-        // waits for them any more, and this call would otherwise be refused for as long as the thread lives.
-        if (pending.on && phase == kSubmit) return PNR_ERR_INVALID;
-        pending.on = false;
-        if (pal) {   // the aux map starts at zero (palette/renderer.py:436-441): inside the first launch when rows are float4-aligned
-            if ((aux_stride & 3u) == 0 && (reinterpret_cast<uintptr_t>(out_aux) & 15u) == 0) { fb.aux_zero = out_aux; fb.aux_stride = aux_stride; }
-            else if (hipMemsetAsync(out_aux, 0, (size_t)N * aux_stride * 4, s) != hipSuccess) return PNR_ERR_LAUNCH;
-        }
-        hipLaunchKernelGGL(k_frame_begin, dim3(cdiv(N, kRayBlock)), dim3(kRayBlock), 0, s, N, fb, w.alive[1], w.rays_t, out_ws, out_depth, out_image,
-                           w.ctl, counts_of(1), w.scratch, w.qctr, hconst, w.hosted);
-    }
-    // optional live timing of the roofline kernel: HIP events on the launch stream around every k_frame_grid launch
-    std::vector<hipEvent_t>& ev = dev_state.ev;
-    size_t ev_used = 0;
-    auto next_event = [&]() -> hipEvent_t {
-        if (ev_used == ev.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return nullptr; ev.push_back(e); }
-        return ev[ev_used++];
-    };
-    const bool timing = a->kernel_ms != nullptr;
-    FrameFinish fin = {};
-    fin.on = a->finish; fin.bg[0] = a->bg_color[0]; fin.bg[1] = a->bg_color[1]; fin.bg[2] = a->bg_color[2];
-    fin.bg_map = a->bg_map; fin.nears = a->nears; fin.fars = a->fars;   // indexed by ray id
-    fin.depth_raw = a->depth_raw;
-    auto launch_last = [&](const FrameCtl* done_ctl) {
-        fin.ctl = done_ctl;
-        if (sorted && pal && aux_stride > 64)
-            hipLaunchKernelGGL(k_frame_unsort_outputs<32>, dim3(cdiv(N, kRayBlock / 32)), dim3(kRayBlock), 0, s, N, a->ray_order, w.s_ws, w.s_depth, w.s_image,
-                               w.s_aux, aux_stride, a->weights_sum, a->depth, a->image, pal->aux_map, fin);
-        else if (sorted && pal)
-            hipLaunchKernelGGL(k_frame_unsort_outputs<16>, dim3(cdiv(N * 16, kRayBlock)), dim3(kRayBlock), 0, s, N, a->ray_order, w.s_ws, w.s_depth, w.s_image,
-                               w.s_aux, aux_stride, a->weights_sum, a->depth, a->image, pal->aux_map, fin);
-        else if (sorted)
-            hipLaunchKernelGGL(k_frame_unsort_outputs<4>, dim3(cdiv(N * 4, kRayBlock)), dim3(kRayBlock), 0, s, N, a->ray_order, w.s_ws, w.s_depth, w.s_image,
-                               (const float*)nullptr, 0u, a->weights_sum, a->depth, a->image, (float*)nullptr, fin);
-        else if (fin.on || fin.depth_raw)   // unsorted frame: the same kernel in place
-            hipLaunchKernelGGL(k_frame_unsort_outputs<4>, dim3(cdiv(N * 4, kRayBlock)), dim3(kRayBlock), 0, s, N, (const int32_t*)nullptr, a->weights_sum, a->depth,
-                               a->image, (const float*)nullptr, aux_stride, a->weights_sum, a->depth, a->image, pal ? pal->aux_map : (float*)nullptr, fin);
-    };
-    uint32_t alive_ub = N;   // host-side upper bound of n_alive (it only shrinks)
-    // Iterations enqueued between two looks at the control block.  Consecutive frames of a camera path need nearly the same
-    // number of iterations, so the first chunk is the previous frame's count (one look per frame when the guess holds; launches
-    // past the end are no-ops that cost a few microseconds each); after that, short chunks that grow for long, translucent marches.
-    uint32_t& predicted_iterations = dev_state.predicted_iterations;
-    // (+1: the launch that finds no ray left is the one that reports it; + g_opt_iteration_margin spare iterations.  Along a camera path the
-    // count drifts by one or two from frame to frame; a spare iteration is four early-exit launches (~19 us), a wrong guess one host round
-    // trip.  Measured on the moving-camera benchmark the round trip is the cheaper of the two: the margin defaults to 0)
-    const uint32_t want = predicted_iterations + 1u + (uint32_t)opt.iteration_margin;
-    uint32_t chunk = predicted_iterations ? (want < 1024u ? want : 1024u) : 8u;
-    uint32_t looks = 0;
-    uint32_t prev_partials = 0;   // workgroups of the previous march launch (= sample partials to add up)
-    int iter = 0;
-    if (phase == kFinish) {   // continue where the submit call stopped: its chunk, the frame's last launch and the read-back are in the stream
-        iter = pending.iter; alive_ub = pending.alive_ub; chunk = pending.chunk; looks = pending.looks; prev_partials = pending.prev_partials; ev_used = pending.ev_used;
-        pending.on = false;
-    }
-    auto enqueue_chunk = [&]() -> int {
-        for (uint32_t k = 0; k < chunk; k++, iter++) {
-            FrameCtl* cur = w.ctl + (iter & 1);                 // this iteration's control block, written by its march launch
-            const FrameCtl* prev = w.ctl + ((iter + 1) & 1);    // the previous iteration's (k_frame_begin's in front of iteration 0)
-            int32_t* alive_in = w.alive[iter & 1];              // this iteration's compacted list (the march writes it, the composite punches holes)
-            const int32_t* alive_prev = w.alive[(iter + 1) & 1];
-            const uint32_t ray_blocks = cdiv(alive_ub, kRayBlock);
-            const uint32_t rows_ub = (uint64_t)alive_ub * 8 < N ? alive_ub * 8 : N;
-            // hosted tail (MODE 2): the march gives every ray `budget` sample-less probes and queues the rest for the lookup launch's first workgroups
-            const uint32_t budget = hosted ? (uint32_t)(iter == 0 ? opt.march_budget0 : opt.march_budget) : 0u;
-            const int mode = budget ? 2 : 1;
-            // MODE 2 runs five workgroups per CU (1 280 resident).  A typical later lego launch has 1 352 chunks: its last 72 workgroups start ~8 us late
-            // (launch 16.9 us), and capping the launch at 1 280 is no way out -- a workgroup's second chunk waits at the block barriers for the slowest
-            // wave of its first one (18.4 us).  With three chunks and more per resident workgroup (garden: 4 256) the cap does pay: the chunks of a
-            // workgroup share its prologue (mip staging, chunk sums): 38.7 -> 33.1 us per launch.  "march_blocks" overrides (0 / 65536 = this rule).
-            const uint32_t kResident = 1280;
-            uint32_t march_cap = kMaxMarchBlocks;
-            if (mode == 2) {
-                if (opt.march_blocks > 0 && opt.march_blocks < 65536) march_cap = (uint32_t)opt.march_blocks < kMaxMarchBlocks ? (uint32_t)opt.march_blocks : kMaxMarchBlocks;
-                else if (ray_blocks >= 2 * kResident) march_cap = kResident;
-            }
-            const dim3 gm(ray_blocks < march_cap ? ray_blocks : march_cap), bm(kRayBlock);
-#define PNR_LAUNCH_MARCH(MIPV, P2V, MODEV)                                                                                                                \
-            hipLaunchKernelGGL((k_frame_march<MIPV, P2V, MODEV>), gm, bm, march_lds, s, prev, cur, alive_prev, alive_in, counts_of(iter + 1), counts_of(iter), w.scratch, N, a->max_steps,    \
-                               w.partials[(iter + 1) & 1], prev_partials, w.rays_t, in_o, in_d, mp, a->bitfield, in_far, w.xyzs, w.dirs, w.deltas, mip,           \
-                               w.partials[iter & 1], budget, w.qctr, w.qrecs, w.rowflag, noise_p)
-            if (mode == 2) PNR_LAUNCH_MARCH(true, true, 2);   // (hosted implies the mip and power-of-two configuration)
-            else if (use_mip && pow2) PNR_LAUNCH_MARCH(true, true, 1);
-            else if (use_mip) PNR_LAUNCH_MARCH(true, false, 1);
-            else if (pow2) PNR_LAUNCH_MARCH(false, true, 1);
-            else PNR_LAUNCH_MARCH(false, false, 1);
-#undef PNR_LAUNCH_MARCH
-            if (k + 1 == chunk) {
-                // The look: the march launch is the only writer of the control block (sample and row totals of everything in front of it, the overflow flag,
-                // `done`), so the chunk's last one is read back right behind itself -- the host wakes up while that iteration's lookup and field
-                // launches (empty when the frame is done, which is what the chunk length bets on) and the frame's last launch are still running.
-                // Wait for THIS read-back, not for the stream: another host thread may already have queued the next frame behind it (pipeline.FramesInFlight
-                // with a shared stream: frames back to back without the host's gap between them, kernels never overlapping)
-                if (hipMemcpyAsync(host_ctl, cur, sizeof(FrameCtl), hipMemcpyDeviceToHost, s) != hipSuccess) return PNR_ERR_LAUNCH;
-                if (!dev_state.done_ev && hipEventCreateWithFlags(&dev_state.done_ev, hipEventDisableTiming) != hipSuccess) return PNR_ERR_LAUNCH;
-                if (hipEventRecord(dev_state.done_ev, s) != hipSuccess) return PNR_ERR_LAUNCH;
-            }
-            const uint32_t gx = cdiv(rows_ub, 256);
-            const uint32_t gxc = gx < 1024u ? gx : 1024u;
-            HostedArgs ha = {};
-            if (mode == 2) { ha.hc = w.hosted; ha.rowflag = w.rowflag; ha.blocks = kHostedBlocks; ha.partial_base = gm.x; ha.gx = gxc; ha.n_tab = n_enc; }
-            const uint32_t grid_lds = mode == 2 ? march_lds : 0u;
-            GridArgs ga = {};
-            ga.xyzs = w.xyzs; ga.deltas = w.deltas; ga.offsets = a->offsets; ga.lp = lp; ga.level_stride = N; ga.bound = a->bound; ga.two_bound = 2.0f * a->bound;
-            ga.inv_two_bound = exact_reciprocal_or_zero(ga.two_bound);
-            ga.gridtype = a->gridtype;
-            ga.enc[0] = w.enc; ga.enc[1] = w.enc_pal; ga.enc[2] = w.enc_clip;
-            // live timing of the roofline kernel: the launch carries its own start / stop events (hipExtLaunchKernelGGL: the dispatch's begin and end
-            // time stamps, what rocprofv3 reports) -- events recorded around the launch are packets of their own and measured 79.7 us where the
-            // kernel took 71.0
-            hipEvent_t e0 = timing ? next_event() : nullptr, e1 = timing ? next_event() : nullptr;
-#define PNR_LAUNCH_GRID(KERNEL, GRID) hipExtLaunchKernelGGL(KERNEL, (ha.blocks ? dim3(ha.blocks + (GRID).x * (GRID).y * (GRID).z) : (GRID)), dim3(256), grid_lds, s, e0, e1, 0, cur, ga, ha)
-            if (half_tables && pal && with_clip) {
-                ga.table[0] = pal->embeddings_triple;
-                PNR_LAUNCH_GRID(k_frame_grid_h3, dim3(gxc, 16));
-            } else if (half_tables && pal) {
-                ga.table[0] = pal->embeddings_pair;
-                PNR_LAUNCH_GRID(k_frame_grid_h2, dim3(gxc, 16));
-            } else if (half_tables) {
-                ga.table[0] = a->embeddings;
-                PNR_LAUNCH_GRID(k_frame_grid_h1, dim3(gxc, 16));
-            } else if (triple_table) {
-                ga.table[0] = triple_table;
-                PNR_LAUNCH_GRID(k_frame_grid_triple, dim3(gxc, 16));
-            } else if (pair_table) {
-                ga.table[0] = pair_table;
-                PNR_LAUNCH_GRID(k_frame_grid_pair, dim3(gxc, PNR_FRAME_LEVEL_PAIRS_PAL ? 8 : 16));
-            } else {
-                for (int k = 0; k < 3; k++) ga.table[k] = tables[k];
-                PNR_LAUNCH_GRID(k_frame_grid, dim3(gxc, PNR_FRAME_LEVEL_PAIRS == 2 ? 4 : (PNR_FRAME_LEVEL_PAIRS ? 8 : 16), n_enc));
-            }
-#undef PNR_LAUNCH_GRID
-            if (pal) {
-                pf.ctl = cur; pf.B = rows_ub;
-                if (aux_fused) { pf.rays_alive = alive_in; pf.weights_sum = out_ws; pf.aux_map = out_aux; pf.T_thresh = a->T_thresh; }
-                if (pal_composite_fused) {   // the field kernel does the whole compositing step: no composite launch
-                    pf.rays_t = w.rays_t; pf.weights_sum_rw = out_ws; pf.depth = out_depth; pf.image = out_image; pf.rays_alive_rw = alive_in; pf.counts_cur = counts_of(iter);
-                }
-                const int rc = pnr_internal_palette_field_forward(&pf, stream, opt.palette_waves12);
-                if (rc != PNR_OK) return rc;
-            } else if (a->field_precision == PNR_FIELD_FP32)
-                hipLaunchKernelGGL((k_frame_field<0, false>), dim3(gx < 512u ? gx : 512u), dim3(kFieldThreads), 0, s, cur, w.enc, N, w.dirs, w.deltas,
-                                   a->packed_weights, a->density_scale, enc_scale, w.sigmas, w.rgbs, composite_fused, a->T_thresh, alive_in, w.rays_t, out_ws, out_depth,
-                                   out_image, w.scratch, counts_of(iter));
-            else if (a->field_precision == PNR_FIELD_F16X2 && a->watch_overflow)
-                hipLaunchKernelGGL((k_frame_field<2, true>), dim3(gx < 512u ? gx : 512u), dim3(kFieldThreads), 0, s, cur, w.enc, N, w.dirs, w.deltas,
-                                   a->packed_weights, a->density_scale, enc_scale, w.sigmas, w.rgbs, composite_fused, a->T_thresh, alive_in, w.rays_t, out_ws, out_depth,
-                                   out_image, w.scratch, counts_of(iter));
-            else if (a->field_precision == PNR_FIELD_F16X2)
-                hipLaunchKernelGGL((k_frame_field<2, false>), dim3(gx < 512u ? gx : 512u), dim3(kFieldThreads), 0, s, cur, w.enc, N, w.dirs, w.deltas,
-                                   a->packed_weights, a->density_scale, enc_scale, w.sigmas, w.rgbs, composite_fused, a->T_thresh, alive_in, w.rays_t, out_ws, out_depth,
-                                   out_image, w.scratch, counts_of(iter));
-            else if (a->watch_overflow)
-                hipLaunchKernelGGL((k_frame_field<1, true>), dim3(gx < 512u ? gx : 512u), dim3(kFieldThreads), 0, s, cur, w.enc, N, w.dirs, w.deltas,
-                                   a->packed_weights, a->density_scale, enc_scale, w.sigmas, w.rgbs, composite_fused, a->T_thresh, alive_in, w.rays_t, out_ws, out_depth,
-                                   out_image, w.scratch, counts_of(iter));
-            else
-                hipLaunchKernelGGL((k_frame_field<1, false>), dim3(gx < 512u ? gx : 512u), dim3(kFieldThreads), 0, s, cur, w.enc, N, w.dirs, w.deltas,
-                                   a->packed_weights, a->density_scale, enc_scale, w.sigmas, w.rgbs, composite_fused, a->T_thresh, alive_in, w.rays_t, out_ws, out_depth,
-                                   out_image, w.scratch, counts_of(iter));
-            if (composite_fused != 2 && !pal_composite_fused)   // (the field kernels composite every iteration themselves)
-                hipLaunchKernelGGL(k_frame_composite, gm, bm, 0, s, cur, a->T_thresh, alive_in, w.rays_t, w.sigmas, w.rgbs, w.deltas, out_ws, out_depth, out_image,
-                                   counts_of(iter), (const float*)w.aux, out_aux, aux_stride, aux_fused, composite_fused);
-            prev_partials = gm.x + ha.blocks;
-        }
-        // The frame's last launch goes out BEHIND the read-back and BEFORE the host waits for it: the kernel looks at the same control block and does
-        // nothing unless the frame is done, so a chunk that fell short costs an empty launch -- and when the guess holds (nearly always along a camera
-        // path) the host wakes up, returns and prepares the caller's next frame while this launch runs, instead of launching it after waking up
-        // (an eighth of the garden frame: 0.40 of 2.4 ms were the host's turnaround between frames).  The in-place finish of an unsorted frame is
-        // not idempotent across looks either way: guarded by the same flag.
-        launch_last(w.ctl + ((iter - 1) & 1));
-        return PNR_OK;
-    };
-    if (phase != kFinish) {
-        if (int rc = enqueue_chunk()) return rc;
-        if (phase == kSubmit) {
-            pending.on = true; pending.args = pal ? static_cast<const void*>(pal) : static_cast<const void*>(a);
-            pending.iter = iter; pending.alive_ub = alive_ub; pending.chunk = chunk; pending.looks = looks; pending.prev_partials = prev_partials; pending.ev_used = ev_used;
-            pending.stream = stream; pending.N = N; pending.workspace = a->workspace; pending.opts = opt;
-            return check_launch();
-        }
-    }
-    for (;;) {
-        if (hipEventSynchronize(dev_state.done_ev) != hipSuccess) return PNR_ERR_LAUNCH;     // (polling hipEventQuery instead measured the same: the runtime's wait already spins)
-        if (host_ctl->done) break;
-        alive_ub = (uint32_t)host_ctl->n_alive;
-        if (looks == 0) chunk = predicted_iterations ? 4u : 8u;
-        if (++looks >= 4 && chunk < 64) chunk *= 2;
-        if (int rc = enqueue_chunk()) return rc;
-    }
-    predicted_iterations = (uint32_t)host_ctl->iterations;
-    if (timing) {  // only the iterations that did work (the tail of the last chunk are no-op launches)
-        float total = 0.0f;
-        uint32_t counted = 0;
-        for (size_t i = 0; i + 1 < ev_used && counted < (uint32_t)host_ctl->iterations; i += 2, counted++) {
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) total += ms;
-        }
-        a->kernel_ms[0] = total;
-        a->kernel_ms[1] = (float)counted * ((pair_table || triple_table || half_tables) ? 1.0f : (float)n_enc);  // a k_frame_grid launch covers n_enc tables (count table-launches); the interleaved kinds (pair, triple, h2, h3) are one launch for all
-    }
-    if (a->stats) {
-        a->stats[0] = (uint64_t)host_ctl->iterations;
-        a->stats[1] = host_ctl->rendered;
-        a->stats[2] = host_ctl->rows;
-        a->stats[3] = (uint64_t)iter;  // iterations enqueued (>= executed)
-        a->stats[4] = (uint64_t)looks + 1;  // host looks at the control block (stream synchronisations) this frame took
-        a->stats[5] = (uint64_t)(host_ctl->pad0 != 0);  // an operand of the split-fp16 field left fp16's range (watch_overflow): render again in fp32
-    }
-    return check_launch();
-}
+int pnr_palette_render_frame(const pnr_palette_frame_args* p, pnr_stream_t stream) { return palette_frame(p, stream, kWhole); }
+int pnr_palette_render_frame_submit(const pnr_palette_frame_args* p, pnr_stream_t stream) { return palette_frame(p, stream, kSubmit); }
+int pnr_palette_render_frame_finish(const pnr_palette_frame_args* p, pnr_stream_t stream) { return palette_frame(p, stream, kFinish); }
 
 }  // extern "C"
 

@@ -1390,3 +1390,50 @@ def test_finish_keeps_the_submit_stream_and_options(cuda, kind):
                     equal(got, want, (name, submit_value))
         finally:
             lib.pnr_set_option(b"hosted_tail", 1); lib.pnr_set_option(b"composite_fusion", 2); lib.pnr_set_option(b"aux_fusion", 1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["nerf", "palette"])
+def test_finish_continues_from_the_submitted_plan(cuda, kind):
+    """pnr_*_render_frame_finish derives nothing from the caller's struct: the chunks it enqueues (looks > 1) and the frame's last launch run under the plan
+    _submit made.  Scalar fields of the kept struct overwritten between the two halves -- T_thresh, density_scale, finish, bg_color, for a palette frame also
+    offsets_weight and view_dep_weight -- do not reach the frame: every output equals, bit for bit, the whole-frame call under the original values.  (Scalars
+    only: an implementation that did read them would give another image, never a wild access.)"""
+    from palettenerf_amd.fused import NeRFFieldFused, PaletteFieldFused
+    m = _queue_model(kind, cuda)
+    f = m._fused = NeRFFieldFused(m) if kind == "nerf" else PaletteFieldFused(m)
+    rays = _queue_rays(cuda, 96, 128, 3, far_apart=True)
+    (ro_long, rd_long), (ro_short, rd_short) = (rays[0][0][0], rays[0][1][0]), (rays[2][0][0], rays[2][1][0])
+    args = lambda ro, rd: (ro, rd, None, None, 0.0, 1024, 1e-4)
+    kw = dict(bg_color=1, aabb=m.aabb_infer, min_near=m.min_near)
+    with torch.no_grad():
+        want = [t.clone() if torch.is_tensor(t) else t for t in f.render_frame(*args(ro_long, rd_long), **kw)]
+        f.render_frame(*args(ro_short, rd_short), **kw)        # this thread's prediction: a few iterations -> the long frame's submit call falls short
+        tok = f.frame_prepare(*args(ro_long, rd_long), **kw)
+        f.frame_launch(tok)
+        a, p = tok.base, tok.args
+        kept = (a.T_thresh, a.density_scale, a.finish, tuple(a.bg_color))
+        assert kept[2] != 0 and kept[3] == (1.0, 1.0, 1.0) and kept[1] > 0
+        a.T_thresh, a.density_scale, a.finish = 0.5, 0.5 * kept[1], 0
+        for k in range(3):
+            a.bg_color[k] = 0.0
+        if kind == "palette":
+            kept_pal = (p.offsets_weight, p.view_dep_weight)
+            p.offsets_weight, p.view_dep_weight = 0.0, 0.0
+        try:
+            got = f.frame_finish(tok)
+        finally:
+            a.T_thresh, a.density_scale, a.finish = kept[:3]
+            for k in range(3):
+                a.bg_color[k] = kept[3][k]
+            if kind == "palette":
+                p.offsets_weight, p.view_dep_weight = kept_pal
+            f.invalidate_caches()       # the struct is the kept one of the object's frame plan: the next frame fills a new one
+    assert got[-1]["looks"] > 1
+    assert got[-1]["rendered"] == want[-1]["rendered"] > 1000 and got[-1]["iterations"] == want[-1]["iterations"]
+    tensors = [(x, y) for x, y in zip(got[:-1], want[:-1]) if torch.is_tensor(x)]
+    assert len(tensors) == (3 if kind == "nerf" else 4)
+    for x, y in tensors:
+        assert torch.equal(torch.isnan(x), torch.isnan(y)) and torch.equal(torch.nan_to_num(x), torch.nan_to_num(y))
+    if kind == "palette":
+        assert torch.equal(got[-1]["depth_raw"], want[-1]["depth_raw"])

@@ -196,6 +196,34 @@ def test_lattice_advance_equals_the_stepping_loop(tmp_path_factory):
         assert lib.lattice_case(tc, d, tt, *ptrs) == 1, (tc, d, tt, [float(o[0]) for o in out])
 
 
+# ------------------------------------------------------------------ the frame call's host arithmetic (csrc/frame_plan.hpp, compiled for the host)
+def test_frame_plan_rules_equal_the_expressions_they_replaced(tmp_path):
+    """tests/native/frame_plan_check.cpp: chunk lengths, row bounds, launch sizes and the march cap of csrc/frame_plan.hpp against a transcription of the
+    expressions the frame driver held inline, exhaustively over the ranges listed there; a stand-alone program under the address and undefined-behaviour
+    sanitizers (its own process, nothing preloaded).  Exit status 0 = every case agrees."""
+    import subprocess
+    exe = tmp_path / "frame_plan_check"
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "frame_plan_check.cpp")
+    subprocess.check_call(["g++", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-o", str(exe), src])
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr
+
+
+def test_frame_workspace_sizes_are_pinned():
+    """The frame workspace's layout (frame.hip: carve) is part of what callers allocate: its totals for a few frame sizes and model shapes, as literals."""
+    import ctypes
+    from palettenerf_amd import _lib
+    lib = _lib.load()
+    u32, i32 = ctypes.c_uint32, ctypes.c_int
+    sizes = (0, 1, 255, 256, 257, 12288)
+    assert [lib.pnr_nerf_frame_workspace_bytes(u32(n)) for n in sizes] == [40448, 40448, 105728, 105728, 110336, 3390720]
+    want = {(4, 0, 0): [42240, 42240, 213248, 213248, 218624, 8503552],
+            (8, 0, 0): [42240, 42240, 270080, 270592, 275968, 11256064],
+            (4, 16, 1): [42496, 42496, 278784, 278784, 284416, 11649280]}
+    for (nb, clip_dim, pred_clip), totals in want.items():
+        assert [lib.pnr_palette_frame_workspace_bytes(u32(n), u32(nb), u32(clip_dim), i32(pred_clip)) for n in sizes] == totals, (nb, clip_dim, pred_clip)
+
+
 # ------------------------------------------------------------------ f3: the reference's checkpoint files
 def _layout():
     import json
