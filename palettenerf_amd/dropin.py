@@ -6,6 +6,9 @@ unchanged on MI355X:
     import raymarching                      # -> palettenerf_amd.raymarching
     from gridencoder import GridEncoder     # -> palettenerf_amd.gridencoder.GridEncoder
     from shencoder import SHEncoder         # -> palettenerf_amd.shencoder.SHEncoder
+
+Two opt-in steps beyond the operator boundary, each bound on ONE model instance (no class and no reference file is touched):
+fuse_field(model) -- forward() on the fused field kernel; fuse_loop(model) -- run_cuda() on the device-driven frame loop; unfuse(model) removes both.
 """
 import sys
 import types
@@ -89,6 +92,120 @@ def fuse_field(model, precision="f16x3", pair_lookup=False):
     model._fused = fused
     model.forward = forward      # instance attribute: nn.Module.__call__ resolves self.forward here
     bind_background(model)
+    return model
+
+
+_LOOP_PRECISION = {"fp32": 0, "f16x3": 1, "f16x2": 2}
+
+
+class _Loop:
+    """What fuse_loop keeps on the instance (`model._loop`): the precision it was asked for and the all-zero maps the frames hand out
+    (renderer._zero_map).  The field object itself is `model._fused`, shared with fuse_field and looked up per frame."""
+
+    def __init__(self, precision):
+        self.precision = precision
+
+
+def fuse_loop(model, precision="f16x3"):
+    """Opt-in, one step beyond fuse_field: give a NeRFNetwork or PaletteNetwork -- the REFERENCE's own class (built over the drop-in encoders after
+    install()) or this package's mirror -- the device-driven frame loop as its run_cuda() for inference frames.  The reference's renderer file stays
+    unchanged; what changes is what `model.run_cuda(rays_o, rays_d, ...)` (and so `model.render`) executes for a frame: instead of the while loop of
+    nerf/renderer.py:336-386 / palette/renderer.py:430-550 -- march_rays, forward, six flex composites, composite_rays and a boolean-mask compaction
+    with its host sync per iteration -- ONE call of pnr_nerf_render_frame / pnr_palette_render_frame (fused._FrameLoop.render_frame), which also
+    computes near / far, the background blend and the depth normalisation.  Same signature, unknown keywords ignored, the reference's result keys
+    with its shapes in fp32 (plus the mirror's n_samples / rendered / iterations ...); every tensor is the caller's to keep.
+
+    A call takes the native frame when model.cuda_ray is set, the model is in eval mode, autograd is off and the rays are fp32 on the model's HIP
+    device; under fp16 autocast (-O) the frame reads half tables, perturb draws the one torch.rand(N) the per-op loop draws (or takes `noises=`),
+    bg_radius > 0 costs one launch (the model's own background() when its architecture is not the reference's), model.edit and -- in gui_mode --
+    model.stylizer run in the field kernel's epilogue.  Every other call (training, autograd on, CPU tensors, the Stylizer outside gui_mode) goes to
+    the class's own run_cuda, untouched.  The model is read as it is at each call: bitfield, aabb, scalars, palette, edit state, every weight and
+    table -- writes through `.data` included (torch_ema's copy_to / restore): the frame's source checksums notice them, rebuild the packed blobs and
+    render the frame again (a warning says so; invalidate_fused_caches(model) after such a write avoids the double render; a write to only PART of a
+    table needs it, see fused._SourceWatch).
+    The model must have the shipped architecture (hashgrid 16 x 2, 64-wide nets, SH degree 4): RuntimeError here otherwise.  precision as fuse_field's
+    ("f16x2" is honoured where the frame kernels have that form).  Composes with fuse_field in either order; unfuse(model) removes both."""
+    import torch
+    from . import renderer as _rd
+    from .fused import NeRFFieldFused, PaletteFieldFused, background_fused
+    palette = hasattr(model, "encoder_palette")
+    make = PaletteFieldFused if palette else NeRFFieldFused
+    if precision not in _LOOP_PRECISION:
+        raise ValueError(f"precision must be one of {sorted(_LOOP_PRECISION)}")
+    if model.__dict__.get("_fused") is None:
+        model._fused = make(model)       # (raises for another architecture; one that is there already has passed this check)
+    loop = model._loop = _Loop(_LOOP_PRECISION[precision])
+
+    def native(rays_o, rays_d, kwargs):
+        """The frame can go to the frame call as far as the rays and the model's mode say."""
+        return (bool(model.cuda_ray) and not model.training and not torch.is_grad_enabled() and rays_o.is_cuda and rays_o.dtype == torch.float32
+                and rays_d.dtype == torch.float32 and rays_d.device == rays_o.device and rays_o.shape == rays_d.shape and rays_o.numel() > 0
+                and model.aabb_infer.device == rays_o.device and kwargs.get("_phase") is None)
+
+    def field():
+        fused = model.__dict__.get("_fused")
+        if fused is None:               # (invalidated by hand: `model._fused = None`)
+            fused = model._fused = make(model)
+        return fused
+
+    def frame(fused, call):
+        was = fused.precision
+        fused.precision = loop.precision
+        try:
+            return call()
+        finally:
+            fused.precision = was
+
+    def flat_rays(rays_o, rays_d):
+        return rays_o.shape[:-1], rays_o.contiguous().view(-1, 3), rays_d.contiguous().view(-1, 3)
+
+    def bg_of(rays_o, rays_d, bg_color):
+        if model.bg_radius > 0:         # nerf/renderer.py:274-277: one launch, or the model's own background() as the frame's bg_map
+            bg = background_fused(model)
+            if bg is not None:
+                return bg.from_rays(rays_o, rays_d)
+            return model.background(_rm.sph_from_ray(rays_o, rays_d, model.bg_radius), rays_d)
+        return 1 if bg_color is None else bg_color
+
+    if palette:
+        def run_cuda(rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-4, gui_mode=False, **kwargs):
+            if not native(rays_o, rays_d, kwargs) or (model.stylizer is not None and not gui_mode):
+                return type(model).run_cuda(model, rays_o, rays_d, dt_gamma=dt_gamma, bg_color=bg_color, perturb=perturb, force_all_rays=force_all_rays,
+                                            max_steps=max_steps, T_thresh=T_thresh, gui_mode=gui_mode, **kwargs)
+            prefix, rays_o, rays_d = flat_rays(rays_o, rays_d)
+            bg_color = bg_of(rays_o, rays_d, bg_color)
+            noises = _rd._frame_noises(perturb, kwargs.get("noises"), rays_o.shape[0], rays_o)
+            fused = field()
+            return frame(fused, lambda: _rd.palette_native_frame(model, fused, loop, rays_o, rays_d, prefix, model.aabb_infer, None, None, bg_color, noises,
+                                                                 dt_gamma, max_steps, T_thresh, gui_mode))
+    else:
+        def run_cuda(rays_o, rays_d, rays_gt=None, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-4, **kwargs):
+            if not native(rays_o, rays_d, kwargs):
+                return type(model).run_cuda(model, rays_o, rays_d, rays_gt=rays_gt, dt_gamma=dt_gamma, bg_color=bg_color, perturb=perturb,
+                                            force_all_rays=force_all_rays, max_steps=max_steps, T_thresh=T_thresh, **kwargs)
+            prefix, rays_o, rays_d = flat_rays(rays_o, rays_d)
+            bg_color = bg_of(rays_o, rays_d, bg_color)
+            noises = _rd._frame_noises(perturb, kwargs.get("noises"), rays_o.shape[0], rays_o)
+            fused = field()
+            return frame(fused, lambda: _rd.nerf_native_frame(model, fused, loop, rays_o, rays_d, prefix, model.aabb_infer, None, None, bg_color, noises,
+                                                              dt_gamma, max_steps, T_thresh))
+
+    model.run_cuda = run_cuda    # instance attribute: render() and the Trainer resolve self.run_cuda here; type(model).run_cuda stays what it was
+    return model
+
+
+def unfuse(model):
+    """Remove what fuse_loop and fuse_field bound: run_cuda, forward and background are the class's methods again, and the fused objects (with their
+    packed blobs, table copies and workspaces) are dropped."""
+    for name in ("run_cuda", "forward", "background", "_loop"):
+        model.__dict__.pop(name, None)
+    from .renderer import _RendererBase
+    for name in ("_fused", "_bg_fused"):
+        if name in model.__dict__:
+            if isinstance(model, _RendererBase):    # the mirror's constructors define both (None until first use)
+                model.__dict__[name] = None
+            else:
+                del model.__dict__[name]
     return model
 
 

@@ -16,6 +16,7 @@ import threading
 import torch
 
 _FUSED_SETTINGS = ("precision", "table_half", "interleave_tables", "stand_alone_pair", "ray_order", "time_grid_kernel")
+_TWIN_OWN = ("_fused", "_density_fused", "_bg_fused", "background", "run_cuda", "_loop", "_occ_ws", "_occ_blob")    # what a twin keeps for itself (sync_twin)
 
 
 def clone_for_concurrent_frames(model):
@@ -34,6 +35,10 @@ def clone_for_concurrent_frames(model):
     if "background" in twin.__dict__:       # dropin.fuse_field bound the model's background over the MODEL's BackgroundFused: the twin's goes over its own
         from .dropin import bind_background
         bind_background(twin)
+    if "run_cuda" in twin.__dict__:         # dropin.fuse_loop bound the model's frames over the MODEL's state: the twin's go over its own
+        from .dropin import fuse_loop
+        fuse_loop(twin)
+        twin._loop.precision = model._loop.precision
     for name in _FUSED_SETTINGS:
         if hasattr(fused, name):
             setattr(twin._fused, name, getattr(fused, name))
@@ -44,9 +49,9 @@ def clone_for_concurrent_frames(model):
 def sync_twin(model, twin):
     """Bring a twin's plain attributes up to date with the model's (everything but its own fused-field object and its private caches):
     `model.edit = RegionEdit(...)`, a changed offsets_weight or density_scale after the clone would otherwise be shadowed by the snapshot."""
-    keep = {k: twin.__dict__[k] for k in ("_fused", "_density_fused", "_bg_fused", "background", "_occ_ws", "_occ_blob") if k in twin.__dict__}
+    keep = {k: twin.__dict__[k] for k in _TWIN_OWN if k in twin.__dict__}
     for k, v in model.__dict__.items():
-        if k not in ("_fused", "_density_fused", "_bg_fused", "background", "_occ_ws", "_occ_blob", "_fused_twins"):
+        if k not in _TWIN_OWN and k != "_fused_twins":
             twin.__dict__[k] = v
     for k in list(twin.__dict__):
         if k not in model.__dict__ and k not in keep:
@@ -57,6 +62,8 @@ def sync_twin(model, twin):
         for name in _FUSED_SETTINGS:
             if hasattr(src, name):
                 setattr(twin._fused, name, getattr(src, name))
+    if "_loop" in twin.__dict__ and "_loop" in model.__dict__:
+        twin._loop.precision = model._loop.precision
 
 
 class _Worker(threading.Thread):

@@ -379,22 +379,6 @@ class _RendererBase(nn.Module):
         with torch.no_grad():
             return pending.complete(pending.fused.frame_result(pending.tok))
 
-    def _native_frame(self, frame_args, frame_kw, phase, complete):
-        """run_cuda's native branch behind its arguments: the frame through self._fused -- prepared only (phase "prepare": render_prepare(); the frame itself goes
-        out in render_launch / render_finish) or rendered -- and `complete` for its result dict.  Under fp16 autocast (the reference's -O mode) the loop looks
-        the hash tables up as fp16 with the reference's half interpolation (gridencoder/grid.py:36-39), the field stays on its fp32-accurate matrix path;
-        outputs are fp32 as the reference's are."""
-        fused = self._fused
-        was_half = fused.table_half
-        fused.table_half = was_half or torch.is_autocast_enabled()
-        try:
-            if phase == "prepare":
-                return PendingFrame(fused, fused.frame_prepare(*frame_args, **frame_kw), complete)
-            ret = fused.render_frame(*frame_args, **frame_kw)
-        finally:
-            fused.table_half = was_half
-        return complete(ret)
-
     def render(self, rays_o, rays_d, staged=False, max_ray_batch=4096, **kwargs):
         """nerf/renderer.py:564-603 / palette/renderer.py:554-573 -- never staged when cuda_ray."""
         if self.cuda_ray:
@@ -449,6 +433,97 @@ def _zero_map(owner, name, shape, like):
     z = torch.zeros(*shape, dtype=torch.float32, device=like.device)
     owner.__dict__[key] = (z, z._version)
     return z
+
+
+def _native_frame(fused, frame_args, frame_kw, phase, complete):
+    """The native branches behind their arguments: the frame through `fused` -- prepared only (phase "prepare": render_prepare(); the frame itself goes
+    out in render_launch / render_finish) or rendered -- and `complete` for its result dict.  Under fp16 autocast (the reference's -O mode) the loop looks
+    the hash tables up as fp16 with the reference's half interpolation (gridencoder/grid.py:36-39), the field stays on its fp32-accurate matrix path;
+    outputs are fp32 as the reference's are."""
+    was_half = fused.table_half
+    fused.table_half = was_half or torch.is_autocast_enabled()
+    try:
+        if phase == "prepare":
+            return PendingFrame(fused, fused.frame_prepare(*frame_args, **frame_kw), complete)
+        ret = fused.render_frame(*frame_args, **frame_kw)
+    finally:
+        fused.table_half = was_half
+    return complete(ret)
+
+
+def nerf_native_frame(m, fused, owner, rays_o, rays_d, prefix, aabb, nears, fars, bg_color, noises, dt_gamma, max_steps, T_thresh, phase=None):
+    """One inference frame of a NeRF model on the device-driven loop (pnr_nerf_render_frame): same schedule and arithmetic as the per-op loop, no
+    per-iteration host sync.  `m` is any model with the reference's attributes (NeRFRenderer.run_cuda's native branch and dropin.fuse_loop both end
+    here), read as it is NOW; `fused` its NeRFFieldFused; `owner` keeps the shared all-zero map.  rays [N,3]; aabb with nears = fars = None: the
+    frame call computes near / far itself."""
+    results = {}
+    frame_args = (rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh)
+    frame_kw = dict(bg_color=bg_color, aabb=aabb, min_near=m.min_near, noises=noises)
+
+    def complete(ret):
+        weights_sum, depth_acc, image_acc, stats = ret
+        nears, fars = stats["nears"], stats["fars"]
+        if stats["finished"]:   # the frame call applied the epilogue below itself (same fp32 operations, one launch less each)
+            image, depth = image_acc, depth_acc
+        else:
+            image = image_acc + (1 - weights_sum).unsqueeze(-1) * bg_color
+            depth = torch.clamp(depth_acc - nears, min=0) / (fars - nears)
+        image = image.view(*prefix, 3)
+        depth = depth.view(*prefix)
+        results["n_samples"] = stats["rows"]
+        results["rendered"] = torch.tensor([stats["rendered"]], dtype=torch.int64)   # host tensor: the count came back with the control block
+        results["iterations"], results["host_looks"] = stats["iterations"], stats["looks"]
+        results["grid_ms"], results["grid_launches"] = stats["grid_ms"], stats["grid_launches"]
+        results["depth"] = depth
+        results["image"] = image
+        results["rgb_norm"] = _zero_map(owner, "rgb_norm", tuple(prefix), image)
+        results["weights_sum"] = weights_sum
+        return results
+
+    return _native_frame(fused, frame_args, frame_kw, phase, complete)
+
+
+def palette_native_frame(m, fused, owner, rays_o, rays_d, prefix, aabb, nears, fars, bg_color, noises, dt_gamma, max_steps, T_thresh, gui_mode, phase=None):
+    """nerf_native_frame for a PaletteNeRF model (pnr_palette_render_frame): the frame call composites one packed aux row per ray, unpacked here into the
+    reference's maps (palette/renderer.py:531-550); RegionEdit and the Stylizer run inside the field kernel's epilogue."""
+    nb, clip_dim = m.num_basis, m.opt.clip_dim
+    N = rays_o.shape[0]
+    results = {}
+    # without a clip head the map is zero whatever happens (palette/renderer.py:446, 477): the packed row leaves those channels out
+    clip_zero = _zero_map(owner, "clip_feat", (N, clip_dim), rays_o) if fused.clip_dim != clip_dim else None
+    frame_args = (rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh)
+    frame_kw = dict(bg_color=bg_color, aabb=aabb, min_near=m.min_near, noises=noises)
+
+    def complete(ret):
+        weights_sum, depth_acc, image_acc, aux_map, stats = ret
+        results["iterations"], results["grid_ms"], results["grid_launches"] = stats["iterations"], stats["grid_ms"], stats["grid_launches"]
+        results["host_looks"] = stats["looks"]
+        direct_rgb_map = aux_map[:, 0:3]
+        clip_feat_map = aux_map[:, 6 + 7 * nb:6 + 7 * nb + clip_dim] if clip_zero is None else clip_zero
+        if stats["finished"]:   # the frame call's last launch applied the epilogue itself (same fp32 operations; eleven launches less)
+            image, depth, depth_origin = image_acc, depth_acc, stats["depth_raw"]
+        else:
+            nears, fars = stats["nears"], stats["fars"]
+            image = image_acc + (1 - weights_sum).unsqueeze(-1) * bg_color
+            depth_origin = depth_acc.clone()
+            depth = torch.clamp(depth_acc - nears, min=0) / (fars - nears)
+            direct_rgb_map = direct_rgb_map + (1 - weights_sum).unsqueeze(-1) * bg_color
+        results["depth"] = depth.view(*prefix)
+        results["depth_origin"] = depth_origin.view(*prefix)
+        results["image"] = image.view(*prefix, 3)
+        results["weights_sum"] = weights_sum
+        results["clip_feat"] = clip_feat_map.reshape(*prefix, clip_dim)
+        results["n_samples"] = stats["rows"]
+        results["rendered"] = torch.tensor([stats["rendered"]], dtype=torch.int64)   # host tensor: the count came back with the control block
+        if not gui_mode:
+            results["direct_rgb"] = direct_rgb_map.reshape(*prefix, 3)
+            results["view_dep_rgb"] = aux_map[:, 3:6].reshape(*prefix, 3)
+            results["basis_rgb"] = aux_map[:, 6 + nb:6 + 4 * nb].reshape(*prefix, nb * 3)
+            results["unscaled_basis_rgb"] = aux_map[:, 6 + 4 * nb:6 + 7 * nb].reshape(*prefix, nb * 3)
+            results["basis_acc"] = aux_map[:, 6:6 + nb].reshape(*prefix, nb)
+        return results
+
+    return _native_frame(fused, frame_args, frame_kw, phase, complete)
 
 
 class NeRFRenderer(_OccupancyMaintenance, _RendererBase):
@@ -585,30 +660,8 @@ class NeRFRenderer(_OccupancyMaintenance, _RendererBase):
                 from .fused import NeRFFieldFused
                 self._fused = NeRFFieldFused(self)
             noises = _frame_noises(perturb, kwargs.get("noises"), N, rays_o)
-            frame_args = (rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh)
-            frame_kw = dict(bg_color=bg_color, aabb=aabb if native_frame else None, min_near=self.min_near, noises=noises)
-
-            def complete(ret):
-                weights_sum, depth_acc, image_acc, stats = ret
-                nears, fars = stats["nears"], stats["fars"]
-                if stats["finished"]:   # the frame call applied the epilogue below itself (same fp32 operations, one launch less each)
-                    image, depth = image_acc, depth_acc
-                else:
-                    image = image_acc + (1 - weights_sum).unsqueeze(-1) * bg_color
-                    depth = torch.clamp(depth_acc - nears, min=0) / (fars - nears)
-                image = image.view(*prefix, 3)
-                depth = depth.view(*prefix)
-                results["n_samples"] = stats["rows"]
-                results["rendered"] = torch.tensor([stats["rendered"]], dtype=torch.int64)   # host tensor: the count came back with the control block
-                results["iterations"], results["host_looks"] = stats["iterations"], stats["looks"]
-                results["grid_ms"], results["grid_launches"] = stats["grid_ms"], stats["grid_launches"]
-                results["depth"] = depth
-                results["image"] = image
-                results["rgb_norm"] = _zero_map(self, "rgb_norm", tuple(prefix), image)
-                results["weights_sum"] = weights_sum
-                return results
-
-            return self._native_frame(frame_args, frame_kw, kwargs.get("_phase"), complete)
+            return nerf_native_frame(self, self._fused, self, rays_o, rays_d, prefix, aabb if native_frame else None, nears, fars, bg_color, noises, dt_gamma,
+                                     max_steps, T_thresh, kwargs.get("_phase"))
         else:
             def shade(st, n_alive, n_step, xyzs, dirs, deltas):
                 sigmas, rgbs = self(xyzs, dirs)
@@ -880,8 +933,10 @@ class PaletteRenderer(_RendererBase):
             if getattr(self, "_fused", None) is None:
                 from .fused import PaletteFieldFused
                 self._fused = PaletteFieldFused(self)
-            if not native:   # the device-driven loop brings its own (uninitialised, fully written) aux map
-                aux_map = torch.zeros(N, self._fused.aux_channels, **f32)
+            if native:  # device-driven loop: same schedule and arithmetic, no per-iteration host sync (pnr_palette_render_frame)
+                return palette_native_frame(self, self._fused, self, rays_o, rays_d, prefix, aabb if native_near_far else None, nears, fars, bg_color,
+                                            _frame_noises(perturb, kwargs.get("noises"), N, rays_o), dt_gamma, max_steps, T_thresh, gui_mode, kwargs.get("_phase"))
+            aux_map = torch.zeros(N, self._fused.aux_channels, **f32)
         if not use_fused:    # the reference's six maps (palette/renderer.py:436-441); the fused paths composite one packed aux row instead
             view_dep_rgb_map = torch.zeros(N, 3, **f32)
             direct_rgb_map = torch.zeros(N, 3, **f32)
@@ -889,7 +944,7 @@ class PaletteRenderer(_RendererBase):
             unscaled_basis_rgb_map = torch.zeros(N, 3 * nb, **f32)
             basis_acc_map = torch.zeros(N, nb, **f32)
         if not use_fused or self._fused.clip_dim != clip_dim:
-            clip_feat_map = _zero_map(self, "clip_feat", (N, clip_dim), rays_o) if native else torch.zeros(N, clip_dim, **f32)
+            clip_feat_map = torch.zeros(N, clip_dim, **f32)
 
         def shade_fused(st, n_alive, n_step, xyzs, dirs, deltas):
             # one fused field launch + ONE flex composite over the packed aux row instead of ~40 launches and 6 flex composites
@@ -936,7 +991,7 @@ class PaletteRenderer(_RendererBase):
             # must come last: the only composite that mutates rays_alive / rays_t / weights_sum (palette/renderer.py:517-519)
             raymarching.composite_rays(*a, st.rays_alive, st.rays_t, sigmas, rgbs, deltas, st.weights_sum, st.depth, st.image, T_thresh)
 
-        def tail(st, aux_map, finished, stats, nears, fars):
+        def tail(st, aux_map):
             nonlocal clip_feat_map, direct_rgb_map, view_dep_rgb_map, basis_acc_map, basis_rgb_map, unscaled_basis_rgb_map
             if use_fused:  # unpack the composited aux row into the reference's maps
                 direct_rgb_map, view_dep_rgb_map = aux_map[:, 0:3], aux_map[:, 3:6]
@@ -946,12 +1001,9 @@ class PaletteRenderer(_RendererBase):
                 if self._fused.clip_dim == clip_dim:
                     clip_feat_map = aux_map[:, 6 + 7 * nb:6 + 7 * nb + clip_dim]
             weights_sum = st.weights_sum
-            if finished:
-                image, depth, depth_origin = st.image, st.depth, stats["depth_raw"]
-            else:
-                image = st.image + (1 - weights_sum).unsqueeze(-1) * bg_color
-                depth_origin = st.depth.clone()
-                depth = torch.clamp(st.depth - nears, min=0) / (fars - nears)
+            image = st.image + (1 - weights_sum).unsqueeze(-1) * bg_color
+            depth_origin = st.depth.clone()
+            depth = torch.clamp(st.depth - nears, min=0) / (fars - nears)
             results["depth"] = depth.view(*prefix)
             results["depth_origin"] = depth_origin.view(*prefix)
             results["image"] = image.view(*prefix, 3)
@@ -960,30 +1012,14 @@ class PaletteRenderer(_RendererBase):
             results["n_samples"] = st.n_samples
             results["rendered"] = st.rendered
             if not gui_mode:
-                results["direct_rgb"] = (direct_rgb_map if finished else direct_rgb_map + (1 - weights_sum).unsqueeze(-1) * bg_color).reshape(*prefix, 3)
+                results["direct_rgb"] = (direct_rgb_map + (1 - weights_sum).unsqueeze(-1) * bg_color).reshape(*prefix, 3)
                 results["view_dep_rgb"] = view_dep_rgb_map.reshape(*prefix, 3)
                 results["basis_rgb"] = basis_rgb_map.reshape(*prefix, nb * 3)
                 results["unscaled_basis_rgb"] = unscaled_basis_rgb_map.reshape(*prefix, nb * 3)
                 results["basis_acc"] = basis_acc_map.reshape(*prefix, nb)
             return results
 
-        if native:  # device-driven loop: same schedule and arithmetic, no per-iteration host sync (pnr_palette_render_frame)
-            frame_args = (rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh)
-            frame_kw = dict(bg_color=bg_color, aabb=aabb if native_near_far else None, min_near=self.min_near,
-                            noises=_frame_noises(perturb, kwargs.get("noises"), N, rays_o))
-
-            def complete(ret):
-                ws_n, depth_n, image_n, aux_n, stats = ret
-                st = _MarchState.__new__(_MarchState)
-                st.weights_sum, st.depth, st.image, st.n_samples = ws_n, depth_n, image_n, stats["rows"]
-                st.rendered = torch.tensor([stats["rendered"]], dtype=torch.int64)   # host tensor: the count came back with the control block
-                results["iterations"], results["grid_ms"], results["grid_launches"] = stats["iterations"], stats["grid_ms"], stats["grid_launches"]
-                results["host_looks"] = stats["looks"]
-                # finished: the frame call's last launch applied the epilogue itself (same fp32 operations; eleven launches less)
-                return tail(st, aux_n, stats["finished"], stats, stats["nears"], stats["fars"])
-
-            return self._native_frame(frame_args, frame_kw, kwargs.get("_phase"), complete)
         if kwargs.get("noises") is not None:
             raise RuntimeError("noises= belongs to the native frame (march_mode = 'native', fused_field); the per-op loops draw their own with perturb")
         st = self._infer_loop(rays_o, rays_d, nears, fars, perturb, dt_gamma, max_steps, shade_fused if use_fused else shade)
-        return tail(st, aux_map if use_fused else None, False, None, nears, fars)
+        return tail(st, aux_map if use_fused else None)
