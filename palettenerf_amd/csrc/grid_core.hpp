@@ -92,6 +92,15 @@ __device__ __forceinline__ void corner_accumulate(float acc[C], float w, const f
         for (uint32_t ch = 0; ch < C; ch++) acc[ch] = fmaf(w, g[ch], acc[ch]);
     }
 }
+// half(w * v) with the reference's TWO roundings: the product to fp32, that to fp16.  Left as one expression the compiler may select v_fma_mixlo_f16
+// for it (an fp32 fma with ONE rounding to f16) -- it did in k_grid_fwd<__half, D, 1> for every D and in <__half, 4, 4> and <__half, 5, 4> -- and where the
+// fp32 product lands on the midpoint of two halves (~6e-5 of the products) the result is the other neighbour than the reference's and the oracle's
+// (tests/test_gpu_grid_variants.py).  The empty statement makes the fp32 product a value of its own, whichever instructions are selected around it.
+__device__ __forceinline__ __half half_of_product(float w, __half v) {
+    float p = w * __half2float(v);
+    asm("" : "+v"(p));
+    return __float2half(p);
+}
 template <uint32_t C>
 __device__ __forceinline__ void corner_accumulate(__half acc[C], float w, const __half* __restrict__ g) {
     __half v[C];
@@ -107,7 +116,7 @@ __device__ __forceinline__ void corner_accumulate(__half acc[C], float w, const 
     }
 #pragma unroll
     for (uint32_t ch = 0; ch < C; ch++)
-        acc[ch] = __float2half(__half2float(acc[ch]) + __half2float(__float2half(w * __half2float(v[ch]))));
+        acc[ch] = __float2half(__half2float(acc[ch]) + __half2float(half_of_product(w, v[ch])));
 }
 
 // 1 / v when v is a power of two (then x / v == x * (1 / v) bit for bit for every finite x that does not end subnormal), else 0: "divide"

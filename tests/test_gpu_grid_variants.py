@@ -1,0 +1,145 @@
+"""GPU: every compiled variant of the grid encoder -- k_grid_fwd<T, D, C>, k_grid_bwd<T, D, C, COMBINE> and k_grid_input_bwd<T> for T in {float, half},
+D in 1..5, C in {1, 2, 4, 8} -- through the public grid_encode, against the float64 statement of tests/grid_reference.py (bounds derived there from the
+precision of the number formats) and, where the oracle has the path, bit for bit against the oracle.
+
+One test per (D, C); inside it gridtype x align_corners x table dtype, on the encoder's own offsets, on tiny tables for D <= 2 (so that hashed levels
+occur) and on hand-made odd level sizes.  L = 6, H = 16, per_level_scale = 2: levels 0-4 run the run-combining backward kernel, level 5 the plain one.
+The ray-ordered input (999 rows: runs of 2-27 equal table rows anywhere in a wave, out-of-range rows inside runs, a ragged last wave) is what the
+segmented wave sum of k_grid_bwd<..., true> needs to be checked: a scan that drops or doubles one addend at a run boundary is far outside the bounds.
+
+Every test prints its worst error / bound ratio per dtype and quantity (pytest -s shows them)."""
+import numpy as np
+import pytest
+import torch
+
+import oracle
+from palettenerf_amd import gridencoder
+from palettenerf_amd._torch_glue import call, ptr
+from tests import grid_reference as gr
+
+pytestmark = pytest.mark.gpu
+
+L, H, PLS = gr.L, gr.H, gr.PLS
+
+
+def dev(a, cuda):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
+
+
+def host(t):
+    return t.detach().cpu().numpy()
+
+
+class _Checks:
+    """Collects every miss of one test (so that one run shows them all) and the worst error / bound ratio per (dtype, quantity)."""
+
+    def __init__(self):
+        self.fails, self.worst = [], {}
+
+    def bound(self, tag, dtype, what, got, want, bound):
+        r = gr.error_ratio(got, want, bound)
+        if not r <= self.worst.get((dtype, what), 0.0):      # also when r is NaN
+            self.worst[(dtype, what)] = r
+        if not r <= 1.0:
+            self.fails.append(f"{tag} {dtype} {what}: error / bound = {r}")
+
+    def same_bits(self, tag, what, got, want):
+        got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+        bits = {2: np.uint16, 4: np.uint32}[got.dtype.itemsize]
+        if got.dtype != want.dtype or got.shape != want.shape or not np.array_equal(got.view(bits), want.view(bits)):
+            self.fails.append(f"{tag} {what}: bits differ")
+
+    def true(self, tag, what, ok):
+        if not ok:
+            self.fails.append(f"{tag} {what}")
+
+
+def _encode(x, table, offsets, gridtype, ac, calc_grad_inputs=False):
+    return gridencoder.grid_encode(x, table, offsets, PLS, H, calc_grad_inputs, gridtype, ac)
+
+
+def _one_table(ck, cuda, tag, dtype, ref, x, table, offsets, gridtype, ac, g, D, C):
+    """forward (without and with dy_dx), backward (with and without input gradients) of one table dtype against float64."""
+    B = x.shape[0]
+    u = gr.U32 if dtype == "fp32" else gr.U16
+    tx, to = dev(x, cuda), dev(offsets, cuda)
+    out = _encode(tx, dev(table, cuda), to, gridtype, ac)
+    want, mag = ref.forward(table)
+    ck.true(tag, f"{dtype} output shape / dtype", out.shape == (B, L * C) and host(out).dtype == table.dtype)
+    ck.same_bits(tag, f"{dtype} forward against the oracle", host(out), oracle.grid_encode_forward(x, table, offsets, PLS, H, gridtype=gridtype, align_corners=ac))
+    ck.bound(tag, dtype, "forward", host(out).reshape(B, L, C), want, gr.forward_bound(D, mag, u))
+    ck.true(tag, f"{dtype} out-of-range rows give zeros", not host(out)[~ref.inr].any())
+
+    # with dy_dx, then backward through the autograd wrapper
+    te, txg = dev(table, cuda).requires_grad_(True), dev(x, cuda).requires_grad_(True)
+    out2 = _encode(txg, te, to, gridtype, ac, True)
+    ck.same_bits(tag, f"{dtype} forward with dy_dx requested", host(out2), host(out))
+    dy_gpu = host(out2.grad_fn.saved_tensors[3]).reshape(B, L, D, C)
+    dy, dmag = ref.dy_dx(table)
+    ck.true(tag, f"{dtype} dy_dx dtype", dy_gpu.dtype == table.dtype)
+    ck.bound(tag, dtype, "dy_dx", dy_gpu, dy, gr.dy_dx_bound(D, dmag) if dtype == "fp32" else gr.input_grad_bound(D, L, C, dmag, u))
+    ck.true(tag, f"{dtype} out-of-range rows give zero dy_dx", not dy_gpu[~ref.inr].any())
+    (out2 * dev(g, cuda)).sum().backward()
+    gt, gmag, n = ref.table_grad(g)
+    gbound = gr.table_grad_bound(D, gmag, n, u)
+    wi, imag = ref.input_grad(g, dy, dmag)
+    for label, grad in (("with input gradients", te.grad), ("without input gradients", None)):
+        if grad is None:
+            te2 = dev(table, cuda).requires_grad_(True)
+            (_encode(tx, te2, to, gridtype, ac) * dev(g, cuda)).sum().backward()
+            grad = te2.grad
+        got = host(grad)
+        ck.true(tag, f"{dtype} table gradient dtype {label}", got.dtype == table.dtype and got.shape == table.shape)
+        ck.bound(tag, dtype, "table gradient", got, gt, gbound)
+        ck.true(tag, f"{dtype} untouched rows are exactly 0 {label}", not got[n == 0].any())
+        r = abs(got.astype(np.float64).sum() - gt.sum()) / gbound.sum()
+        ck.true(tag, f"{dtype} checksum of the table gradient {label}: error / summed bound = {r}", r <= 1.0)
+    gi = host(txg.grad)
+    ck.true(tag, f"{dtype} input gradient dtype", gi.dtype == np.float32 and gi.shape == x.shape)
+    ck.bound(tag, dtype, "input gradient", gi, wi, gr.input_grad_bound(D, L, C, imag, u))
+    ck.true(tag, f"{dtype} out-of-range rows get exactly 0 input gradient", not gi[~ref.inr].any())
+    return out
+
+
+@pytest.mark.parametrize("C", [1, 2, 4, 8])
+@pytest.mark.parametrize("D", [1, 2, 3, 4, 5])
+def test_grid_variant_against_float64_and_the_oracle(cuda, D, C):
+    ck = _Checks()
+    for ci, (name, offsets, gridtype, ac) in enumerate(gr.variant_cases(D)):
+        emb, g999 = gr.variant_tables(D, C, ci)
+        emb16 = emb.astype(np.float16)
+        for xname, x in gr.variant_inputs(D).items():
+            tag = f"D{D} C{C} {name} {xname}"
+            ref = gr.variant_geometry(D, ci, xname)
+            g = g999[: x.shape[0]]
+            out32 = _one_table(ck, cuda, tag, "fp32", ref, x, emb, offsets, gridtype, ac, g, D, C)
+            out16 = _one_table(ck, cuda, tag, "fp16", ref, x, emb16, offsets, gridtype, ac, (g * 0.01).astype(np.float16), D, C)   # 0.01: nothing overflows half
+            # autocast: an fp32 parameter goes to a half table when C is even (the packed-half atomics need pairs); C = 1 stays fp32
+            with torch.autocast("cuda", dtype=torch.float16):
+                auto = _encode(dev(x, cuda), dev(emb, cuda), dev(offsets, cuda), gridtype, ac)
+            ck.same_bits(tag, "autocast forward", host(auto), host(out16 if C % 2 == 0 else out32))
+    for (dtype, what), r in sorted(ck.worst.items()):
+        print(f"grid variants D={D} C={C} {dtype} {what}: worst error / bound = {r:.3f}")
+    assert not ck.fails, "\n".join(ck.fails)
+
+
+@pytest.mark.parametrize("D,C,levels", [(6, 2, 4), (3, 3, 4), (3, 2, 33)])
+def test_grid_unsupported_shapes_raise_forward_and_backward(cuda, D, C, levels):
+    """D = 6, C = 3 and L = 33 are not compiled: RuntimeError `unsupported` from the forward (through grid_encode) and from the backward entry point
+    (the wrapper cannot reach it without a forward, so through the C ABI); nothing is launched and the gradient buffers stay as they were."""
+    B, rows = 16, 64
+    x = torch.rand(B, D, device=cuda)
+    offsets = torch.arange(levels + 1, dtype=torch.int32, device=cuda) * rows
+    for dtype_id, dtype in ((0, torch.float32), (1, torch.float16)):
+        table = torch.rand(rows * levels, C, device=cuda).to(dtype)
+        with pytest.raises(RuntimeError, match="unsupported"):
+            gridencoder.grid_encode(x, table, offsets, 2.0, 4, False, 0, False)
+        with pytest.raises(RuntimeError, match="unsupported"):
+            gridencoder.grid_encode(x, table, offsets, 2.0, 4, True, 0, False)
+        grad = torch.ones(levels, B, C, device=cuda, dtype=dtype)
+        gg, dy_dx, gi = torch.zeros_like(table), torch.zeros(B, levels * D * C, device=cuda, dtype=dtype), torch.zeros(B, D, device=cuda, dtype=dtype)
+        for with_inputs in (False, True):
+            with pytest.raises(RuntimeError, match="unsupported"):
+                call("pnr_grid_encode_backward", ptr(grad), ptr(x), ptr(table), ptr(offsets), ptr(gg), B, D, C, levels, 1.0, 4,
+                     ptr(dy_dx) if with_inputs else None, ptr(gi) if with_inputs else None, 0, 0, dtype_id)
+        assert not gg.any() and not gi.any()

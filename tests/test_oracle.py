@@ -9,6 +9,7 @@ import torch
 
 import oracle
 from palettenerf_amd import scene
+from tests import grid_reference as gr
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -335,6 +336,66 @@ def test_grid_encode_half_table_accumulates_in_half():
     assert h.dtype == np.float16
     np.testing.assert_allclose(h.astype(np.float32), f, atol=2e-3)
     assert np.abs(h.astype(np.float32) - f).max() > 0  # the half accumulator is visibly not the fp32 one
+
+
+@pytest.mark.parametrize("C", [1, 2, 4, 8])
+@pytest.mark.parametrize("D", [1, 2, 3, 4, 5])
+def test_grid_oracle_every_variant_against_float64(D, C):
+    """The oracle is what the GPU kernels are compared with, so it is itself compared with the float64 statement of tests/grid_reference.py for every
+    D x C x gridtype x align_corners (plus tiny tables for D <= 2 and hand-made odd level sizes), on ray-ordered and uniform inputs: fp32 forward, dy_dx,
+    table gradient, input gradient, and the half-table forward -- each inside the bound that module derives for the precision of the number format."""
+    L = gr.L
+    fails = []
+
+    def check(what, got, want, bound):
+        r = gr.error_ratio(got, want, bound)
+        if not r <= 1.0:
+            fails.append(f"{what}: error / bound = {r}")
+
+    cases = gr.variant_cases(D)
+    assert {(g, a) for _, _, g, a in cases} == {(0, False), (0, True), (1, False), (1, True)}
+    for ci, (name, offsets, gridtype, ac) in enumerate(cases):
+        emb, g999 = gr.variant_tables(D, C, ci)
+        emb16 = emb.astype(np.float16)
+        for xname, x in gr.variant_inputs(D).items():
+            B, g = x.shape[0], g999[: x.shape[0]]
+            ref = gr.variant_geometry(D, ci, xname)
+            tag = f"D{D} C{C} {name} {xname}"
+            out, dydx = oracle.grid_encode_forward(x, emb, offsets, gr.PLS, gr.H, calc_grad_inputs=True, gridtype=gridtype, align_corners=ac)
+            gg, gi = oracle.grid_encode_backward(g, x, emb.shape, offsets, gr.PLS, gr.H, gridtype=gridtype, align_corners=ac, dy_dx=dydx)
+            want, mag = ref.forward(emb)
+            check(tag + " forward", out.reshape(B, L, C), want, gr.forward_bound(D, mag))
+            dy, dmag = ref.dy_dx(emb)
+            check(tag + " dy_dx", dydx.reshape(B, L, D, C), dy, gr.dy_dx_bound(D, dmag))
+            gt, gmag, n = ref.table_grad(g)
+            check(tag + " table gradient", gg, gt, gr.table_grad_bound(D, gmag, n))
+            assert n.sum() == ref.inr.sum() * L * 2 ** D and not gg[n == 0].any()
+            wi, imag = ref.input_grad(g, dy, dmag)
+            check(tag + " input gradient", gi, wi, gr.input_grad_bound(D, L, C, imag))
+            assert not out[~ref.inr].any() and not dydx[~ref.inr].any() and not gi[~ref.inr].any()
+            half = oracle.grid_encode_forward(x, emb16, offsets, gr.PLS, gr.H, gridtype=gridtype, align_corners=ac)
+            want16, mag16 = ref.forward(emb16)
+            check(tag + " half forward", half.reshape(B, L, C), want16, gr.forward_bound(D, mag16, gr.U16))
+    assert not fails, "\n".join(fails)
+
+
+def test_grid_reference_runs_of_equal_rows_cover_the_segmented_sum_cases():
+    """What the GPU matrix relies on in its ray-ordered input: on the coarse levels consecutive samples share table rows in runs of many lengths, runs
+    cross wave (64) and block (256) edges, an out-of-range sample sits inside a run, and the last wave is ragged."""
+    for D in (1, 3, 5):
+        ref = gr.variant_geometry(D, 0, "rays")
+        assert ref.B == 999 and ref.B % 64 != 0 and (~ref.inr).sum() == 4 and not ref.inr[[100, 200, 500, 600]].any() and ref.inr[[400, 401]].all()
+        rows = np.where(ref.inr, ref.rows[0, 0], -1)          # level 0, corner 0: what the kernel compares between neighbouring lanes
+        edges = np.flatnonzero(np.diff(rows) != 0) + 1
+        lengths = np.diff(np.concatenate([[0], edges, [999]]))
+        assert lengths.max() >= 10 and len(set(lengths.tolist())) >= 5 and (lengths == 1).any()
+        assert any(ref.rows[l, 0, 99] == ref.rows[l, 0, 101] for l in range(5))   # the far-outside sample 100 breaks a run in two
+        for edge in (64, 256, 512):                           # some level has a run that continues across this wave / block edge
+            assert any(ref.rows[l, 0, edge - 1] == ref.rows[l, 0, edge] for l in range(5))
+        fine = np.where(ref.inr, ref.rows[4, 0], -1)
+        assert (np.diff(fine) != 0).mean() > 0.3              # level 4 (still the combining kernel): mostly short runs
+    uni = gr.variant_geometry(3, 0, "uniform")
+    assert uni.B == 257 and (np.diff(uni.rows[4, 0]) != 0).mean() > 0.95
 
 
 # ------------------------------------------------------------------------------------------ march
