@@ -106,6 +106,21 @@ int pnr_composite_rays_train_backward(const float* grad_weights_sum, const float
                                       const float* rgbs, const float* deltas, const int32_t* rays,
                                       const float* weights_sum, const float* image, uint32_t M, uint32_t N,
                                       float T_thresh, float* grad_sigmas, float* grad_rgbs, pnr_stream_t stream);
+/* The training composite with the NeRF stage's rgb_norm regulariser as a fourth composited quantity: what nerf/renderer.py:301-332 computes
+ * with spread_ray_to_sample (raymarching.cu:848-882), three elementwise ops, a repeat, a second composite_rays_train and a mean.
+ * rays_gt[N,3] is indexed by ray id (rays[n,0]), as kernel_spread_ray_to_sample indexes its input; rgb_norm[index] = sum_k w_k n_k with
+ * n_k = sum_c (rays_gt[index,c] - rgbs[k,c])^2 and the weights, stop rule and dead-ray rule of the plain entries.  weights_sum, depth and
+ * image carry the bits of pnr_composite_rays_train_forward.  Backward: grad_rgb_norm[N] is the norm's upstream gradient,
+ * grad_rgbs[k,c] = grad_image_c w_k + grad_rgb_norm w_k 2 (rgbs[k,c] - gt_c), and grad_sigmas takes the norm as a fourth channel of
+ * raymarching.cu:681-761.  rays_gt receives no gradient.  N == 0 (backward: or M == 0) is PNR_OK; a NULL array is PNR_ERR_INVALID. */
+int pnr_composite_rays_train_norm_forward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                          const float* rays_gt, uint32_t M, uint32_t N, float T_thresh, float* weights_sum,
+                                          float* depth, float* image, float* rgb_norm, pnr_stream_t stream);
+int pnr_composite_rays_train_norm_backward(const float* grad_weights_sum, const float* grad_image, const float* grad_rgb_norm,
+                                           const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                           const float* rays_gt, const float* weights_sum, const float* image,
+                                           const float* rgb_norm, uint32_t M, uint32_t N, float T_thresh, float* grad_sigmas,
+                                           float* grad_rgbs, pnr_stream_t stream);
 /* replaces composite_rays_flex_train_forward / _backward, raymarching.h:16-17, raymarching.cu:657-668, 831-844 */
 int pnr_composite_rays_flex_train_forward(const float* sigmas, const float* input, const float* deltas,
                                           const int32_t* rays, uint32_t M, uint32_t N, uint32_t n_channel,

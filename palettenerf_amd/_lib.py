@@ -25,6 +25,9 @@ SIGNATURES = {
                              _ptr, _ptr, _ptr],
     "pnr_composite_rays_train_forward": [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _f32, _ptr, _ptr, _ptr, _ptr],
     "pnr_composite_rays_train_backward": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _f32, _ptr, _ptr, _ptr],
+    "pnr_composite_rays_train_norm_forward": [_ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr],
+    "pnr_composite_rays_train_norm_backward": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _f32, _ptr, _ptr,
+                                               _ptr],
     "pnr_composite_rays_flex_train_forward": [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _f32, _ptr, _ptr],
     "pnr_composite_rays_flex_train_backward": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _f32, _ptr, _ptr],
     "pnr_spread_ray_to_sample": [_ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr],

@@ -16,19 +16,39 @@ constexpr int kAhead = 8;   // samples fetched ahead of the serial recurrence in
 // alpha of one sample; __expf == v_exp_f32(x * log2e), the gfx950 counterpart of CUDA's __expf
 __device__ __forceinline__ float alpha_of(float sigma, float delta) { return 1.0f - __expf(-sigma * delta); }
 
+// The NeRF stage's rgb_norm regulariser (nerf/renderer.py:301-332) as a fourth composited quantity of the training kernels below (kNorm): the
+// per-sample value n_k = sum_c (gt_c - c_kc)^2, with gt the ground-truth colour of the sample's RAY (what kernel_spread_ray_to_sample,
+// raymarching.cu:848-882, copies to every sample), is formed in registers from the colour the kernel already holds and composited with the
+// same weights: rgb_norm = sum_k w_k n_k.  Without kNorm the kernels are what they were.
+__device__ __forceinline__ float sq_dist3(float g0, float g1, float g2, float c0, float c1, float c2) {
+    const float e0 = g0 - c0, e1 = g1 - c1, e2 = g2 - c2;
+    return e0 * e0 + e1 * e1 + e2 * e2;   // fp32, channel order: torch's ((gt - rgb) ** 2).sum(-1)
+}
+
+// What the kNorm kernels take beyond the plain ones, as ONE trailing argument that is empty without kNorm: the plain instantiations keep the
+// argument layout, and with it the code, they had before the norm existed.
+template <bool kNorm> struct NormFwd {};
+template <> struct NormFwd<true> { const float* rays_gt; float* rgb_norm; };
+template <bool kNorm> struct NormBwd {};
+template <> struct NormBwd<true> { const float* grad_rgb_norm; const float* rays_gt; const float* rgb_norm; };
+
 // reference raymarching.cu:504-580
+template <bool kNorm>
 __global__ void __launch_bounds__(kBlock) k_composite_train_fwd(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                 const float* __restrict__ deltas, const int32_t* __restrict__ rays,
                                                                 uint32_t M, uint32_t N, float T_thresh, float* __restrict__ weights_sum,
-                                                                float* __restrict__ depth, float* __restrict__ image) {
+                                                                float* __restrict__ depth, float* __restrict__ image, const NormFwd<kNorm> nio) {
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     if (n >= N) return;
     const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
     if (num_steps == 0 || offset + num_steps > M) {
         weights_sum[index] = 0; depth[index] = 0;
         image[index * 3] = 0; image[index * 3 + 1] = 0; image[index * 3 + 2] = 0;
+        if constexpr (kNorm) nio.rgb_norm[index] = 0;
         return;
     }
+    float gt0 = 0, gt1 = 0, gt2 = 0, rn = 0;   // the ray's ground truth, read once; the running norm
+    if constexpr (kNorm) { gt0 = nio.rays_gt[index * 3]; gt1 = nio.rays_gt[index * 3 + 1]; gt2 = nio.rays_gt[index * 3 + 2]; }
     const float* s = sigmas + offset;
     const float* c = rgbs + (size_t)offset * 3;
     const float* dl = deltas + (size_t)offset * 2;
@@ -50,6 +70,7 @@ __global__ void __launch_bounds__(kBlock) k_composite_train_fwd(const float* __r
             const float alpha = alpha_of(sg[u], d0[u]);
             const float w = alpha * T;
             r = fmaf(w, cr[u], r); g = fmaf(w, cg[u], g); b = fmaf(w, cb[u], b);
+            if constexpr (kNorm) rn = fmaf(w, sq_dist3(gt0, gt1, gt2, cr[u], cg[u], cb[u]), rn);
             t += d1[u];
             d = fmaf(w, t, d);
             ws += w;
@@ -59,6 +80,7 @@ __global__ void __launch_bounds__(kBlock) k_composite_train_fwd(const float* __r
     }
     weights_sum[index] = ws; depth[index] = d;
     image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
+    if constexpr (kNorm) nio.rgb_norm[index] = rn;
 }
 
 // reference raymarching.cu:583-645
@@ -177,16 +199,19 @@ __device__ __forceinline__ float group_sum(float v) {
     return v;
 }
 
+template <bool kNorm>
 __global__ void __launch_bounds__(kBlock) k_composite_train_fwd_coop(const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                      const float* __restrict__ deltas, const int32_t* __restrict__ rays, uint32_t M,
                                                                      uint32_t N, float T_thresh, float* __restrict__ weights_sum,
-                                                                     float* __restrict__ depth, float* __restrict__ image) {
+                                                                     float* __restrict__ depth, float* __restrict__ image, const NormFwd<kNorm> nio) {
     const uint32_t n = (blockIdx.x * kBlock + threadIdx.x) / kLanesPerRay;
     const int q = (int)(threadIdx.x % kLanesPerRay);
     if (n >= N) return;   // whole 16-lane groups leave together
     const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
-    float r = 0, g = 0, b = 0, ws = 0, d = 0;
+    float r = 0, g = 0, b = 0, ws = 0, d = 0, rn = 0;
     if (num_steps != 0 && offset + num_steps <= M) {
+        float gt0 = 0, gt1 = 0, gt2 = 0;
+        if constexpr (kNorm) { gt0 = nio.rays_gt[index * 3]; gt1 = nio.rays_gt[index * 3 + 1]; gt2 = nio.rays_gt[index * 3 + 2]; }
         float T = 1.0f, t = 0.0f;   // transmittance / ray parameter in front of the current group
         for (uint32_t base = 0; base < num_steps && !(T < T_thresh); base += kLanesPerRay) {
             const uint32_t k = base + (uint32_t)q;
@@ -197,7 +222,9 @@ __global__ void __launch_bounds__(kBlock) k_composite_train_fwd_coop(const float
             const float Tq = T * group_excl_product(1.0f - alpha, q, keep);          // transmittance in front of this lane's sample
             const float tq = t + group_incl_sum(in ? deltas[row * 2 + 1] : 0.0f, q, tsum);
             const float w = (in && !(Tq < T_thresh)) ? alpha * Tq : 0.0f;            // the reference stops after the sample that drops T below the threshold
-            r = fmaf(w, rgbs[row * 3], r); g = fmaf(w, rgbs[row * 3 + 1], g); b = fmaf(w, rgbs[row * 3 + 2], b);
+            const float c0 = rgbs[row * 3], c1 = rgbs[row * 3 + 1], c2 = rgbs[row * 3 + 2];
+            r = fmaf(w, c0, r); g = fmaf(w, c1, g); b = fmaf(w, c2, b);
+            if constexpr (kNorm) rn = fmaf(w, sq_dist3(gt0, gt1, gt2, c0, c1, c2), rn);
             d = fmaf(w, tq, d);
             ws += w;
             T *= keep;
@@ -205,19 +232,24 @@ __global__ void __launch_bounds__(kBlock) k_composite_train_fwd_coop(const float
         }
     }
     r = group_sum(r); g = group_sum(g); b = group_sum(b); ws = group_sum(ws); d = group_sum(d);
+    if constexpr (kNorm) rn = group_sum(rn);
     if (q == 0) {
         weights_sum[index] = ws; depth[index] = d;
         image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
+        if constexpr (kNorm) nio.rgb_norm[index] = rn;
     }
 }
 
 // raymarching.cu:681-761 with the same lane layout: the running colour of the reference (r, g, b after sample k) is an inclusive prefix sum
+// kNorm: the norm is a fourth channel of that backward (running value R, final value rgb_norm, upstream gradient grad_rgb_norm), and reaches
+// the colours through n_k as well: grad_rgbs[k,c] += g_norm w_k 2 (c_kc - gt_c)
+template <bool kNorm>
 __global__ void __launch_bounds__(kBlock) k_composite_train_bwd_coop(const float* __restrict__ grad_weights_sum, const float* __restrict__ grad_image,
                                                                      const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                      const float* __restrict__ deltas, const int32_t* __restrict__ rays,
                                                                      const float* __restrict__ weights_sum, const float* __restrict__ image, uint32_t M,
                                                                      uint32_t N, float T_thresh, float* __restrict__ grad_sigmas,
-                                                                     float* __restrict__ grad_rgbs) {
+                                                                     float* __restrict__ grad_rgbs, const NormBwd<kNorm> nio) {
     const uint32_t n = (blockIdx.x * kBlock + threadIdx.x) / kLanesPerRay;
     const int q = (int)(threadIdx.x % kLanesPerRay);
     if (n >= N) return;
@@ -226,6 +258,11 @@ __global__ void __launch_bounds__(kBlock) k_composite_train_bwd_coop(const float
     const float gws = grad_weights_sum[index];
     const float g0 = grad_image[index * 3], g1 = grad_image[index * 3 + 1], g2 = grad_image[index * 3 + 2];
     const float r_final = image[index * 3], g_final = image[index * 3 + 1], b_final = image[index * 3 + 2], ws_final = weights_sum[index];
+    float gn = 0, gt0 = 0, gt1 = 0, gt2 = 0, rn_final = 0, rn = 0;
+    if constexpr (kNorm) {
+        gn = nio.grad_rgb_norm[index]; rn_final = nio.rgb_norm[index];
+        gt0 = nio.rays_gt[index * 3]; gt1 = nio.rays_gt[index * 3 + 1]; gt2 = nio.rays_gt[index * 3 + 2];
+    }
     float T = 1.0f, r = 0, g = 0, b = 0;   // state in front of the current group
     for (uint32_t base = 0; base < num_steps && !(T < T_thresh); base += kLanesPerRay) {
         const uint32_t k = base + (uint32_t)q;
@@ -239,17 +276,30 @@ __global__ void __launch_bounds__(kBlock) k_composite_train_bwd_coop(const float
         const bool live = in && !(Tq < T_thresh);
         const float w = live ? alpha * Tq : 0.0f;
         const float rq = r + group_incl_sum(w * c0, q, sr), gq = g + group_incl_sum(w * c1, q, sg), bq = b + group_incl_sum(w * c2, q, sb);
+        float nk = 0, nq = 0, sn = 0;
+        if constexpr (kNorm) {
+            nk = sq_dist3(gt0, gt1, gt2, c0, c1, c2);
+            nq = rn + group_incl_sum(w * nk, q, sn);
+        }
         if (live) {
             const float Ta = Tq * (1.0f - alpha);   // transmittance after this sample
-            grad_rgbs[row * 3] = g0 * w; grad_rgbs[row * 3 + 1] = g1 * w; grad_rgbs[row * 3 + 2] = g2 * w;
+            if constexpr (kNorm) {
+                const float gw2 = gn * w * 2.0f;
+                grad_rgbs[row * 3] = fmaf(gw2, c0 - gt0, g0 * w); grad_rgbs[row * 3 + 1] = fmaf(gw2, c1 - gt1, g1 * w);
+                grad_rgbs[row * 3 + 2] = fmaf(gw2, c2 - gt2, g2 * w);
+            } else {
+                grad_rgbs[row * 3] = g0 * w; grad_rgbs[row * 3 + 1] = g1 * w; grad_rgbs[row * 3 + 2] = g2 * w;
+            }
             float acc = g0 * fmaf(Ta, c0, -(r_final - rq));
             acc = fmaf(g1, fmaf(Ta, c1, -(g_final - gq)), acc);
             acc = fmaf(g2, fmaf(Ta, c2, -(b_final - bq)), acc);
+            if constexpr (kNorm) acc = fmaf(gn, fmaf(Ta, nk, -(rn_final - nq)), acc);
             acc = fmaf(gws, 1.0f - ws_final, acc);
             grad_sigmas[row] = dl0 * acc;
         }
         T *= keep;
         r += sr; g += sg; b += sb;
+        if constexpr (kNorm) rn += sn;
     }
 }
 
@@ -293,13 +343,14 @@ __global__ void __launch_bounds__(kBlock) k_composite_flex_train_bwd_coop(const 
     }
 }
 
-// reference raymarching.cu:681-761
+// reference raymarching.cu:681-761 (kNorm: as in the 16-lane form above)
+template <bool kNorm>
 __global__ void __launch_bounds__(kBlock) k_composite_train_bwd(const float* __restrict__ grad_weights_sum, const float* __restrict__ grad_image,
                                                                 const float* __restrict__ sigmas, const float* __restrict__ rgbs,
                                                                 const float* __restrict__ deltas, const int32_t* __restrict__ rays,
                                                                 const float* __restrict__ weights_sum, const float* __restrict__ image,
                                                                 uint32_t M, uint32_t N, float T_thresh, float* __restrict__ grad_sigmas,
-                                                                float* __restrict__ grad_rgbs) {
+                                                                float* __restrict__ grad_rgbs, const NormBwd<kNorm> nio) {
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     if (n >= N) return;
     const uint32_t index = (uint32_t)rays[n * 3], offset = (uint32_t)rays[n * 3 + 1], num_steps = (uint32_t)rays[n * 3 + 2];
@@ -312,6 +363,11 @@ __global__ void __launch_bounds__(kBlock) k_composite_train_bwd(const float* __r
     const float* dl = deltas + (size_t)offset * 2;
     float* gs = grad_sigmas + offset;
     float* gc = grad_rgbs + (size_t)offset * 3;
+    float gn = 0, gt0 = 0, gt1 = 0, gt2 = 0, rn_final = 0, rn = 0;
+    if constexpr (kNorm) {
+        gn = nio.grad_rgb_norm[index]; rn_final = nio.rgb_norm[index];
+        gt0 = nio.rays_gt[index * 3]; gt1 = nio.rays_gt[index * 3 + 1]; gt2 = nio.rays_gt[index * 3 + 2];
+    }
     float T = 1.0f, r = 0, g = 0, b = 0;
     bool stop = false;
     for (uint32_t base = 0; base < num_steps && !stop; base += kAhead) {   // kAhead samples fetched ahead, as in the forward
@@ -330,10 +386,20 @@ __global__ void __launch_bounds__(kBlock) k_composite_train_bwd(const float* __r
             const float w = alpha * T;
             r = fmaf(w, cr[u], r); g = fmaf(w, cg[u], g); b = fmaf(w, cb[u], b);
             T *= 1.0f - alpha;
-            gc[(size_t)k * 3] = g0 * w; gc[(size_t)k * 3 + 1] = g1 * w; gc[(size_t)k * 3 + 2] = g2 * w;
+            float nk = 0;
+            if constexpr (kNorm) {
+                nk = sq_dist3(gt0, gt1, gt2, cr[u], cg[u], cb[u]);
+                rn = fmaf(w, nk, rn);
+                const float gw2 = gn * w * 2.0f;
+                gc[(size_t)k * 3] = fmaf(gw2, cr[u] - gt0, g0 * w); gc[(size_t)k * 3 + 1] = fmaf(gw2, cg[u] - gt1, g1 * w);
+                gc[(size_t)k * 3 + 2] = fmaf(gw2, cb[u] - gt2, g2 * w);
+            } else {
+                gc[(size_t)k * 3] = g0 * w; gc[(size_t)k * 3 + 1] = g1 * w; gc[(size_t)k * 3 + 2] = g2 * w;
+            }
             float acc = g0 * fmaf(T, cr[u], -(r_final - r));
             acc = fmaf(g1, fmaf(T, cg[u], -(g_final - g)), acc);
             acc = fmaf(g2, fmaf(T, cb[u], -(b_final - b)), acc);
+            if constexpr (kNorm) acc = fmaf(gn, fmaf(T, nk, -(rn_final - rn)), acc);
             acc = fmaf(gws, 1.0f - ws_final, acc);
             gs[k] = d0[u] * acc;
             if (T < T_thresh) stop = true;
@@ -514,6 +580,31 @@ __global__ void __launch_bounds__(kMultiThreads) k_composite_rays_flex_multi(uin
 
 using namespace pnr;
 
+template <bool kNorm>
+static int composite_train_forward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M, uint32_t N, float T_thresh,
+                                   float* weights_sum, float* depth, float* image, const NormFwd<kNorm> nio, pnr_stream_t stream) {
+    if (M >= kCoopMinSamples)   // training batches: 16 lanes per ray
+        hipLaunchKernelGGL(k_composite_train_fwd_coop<kNorm>, dim3(cdiv(N * kLanesPerRay, kBlock)), dim3(kBlock), 0, as_stream(stream), sigmas, rgbs,
+                           deltas, rays, M, N, T_thresh, weights_sum, depth, image, nio);
+    else
+        hipLaunchKernelGGL(k_composite_train_fwd<kNorm>, dim3(cdiv(N, kBlock)), dim3(kBlock), 0, as_stream(stream), sigmas, rgbs, deltas, rays, M, N,
+                           T_thresh, weights_sum, depth, image, nio);
+    return check_launch();
+}
+
+template <bool kNorm>
+static int composite_train_backward(const float* grad_weights_sum, const float* grad_image, const float* sigmas, const float* rgbs, const float* deltas,
+                                    const int32_t* rays, const float* weights_sum, const float* image, uint32_t M, uint32_t N, float T_thresh,
+                                    float* grad_sigmas, float* grad_rgbs, const NormBwd<kNorm> nio, pnr_stream_t stream) {
+    if (M >= kCoopMinSamples)
+        hipLaunchKernelGGL(k_composite_train_bwd_coop<kNorm>, dim3(cdiv(N * kLanesPerRay, kBlock)), dim3(kBlock), 0, as_stream(stream),
+                           grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, nio);
+    else
+        hipLaunchKernelGGL(k_composite_train_bwd<kNorm>, dim3(cdiv(N, kBlock)), dim3(kBlock), 0, as_stream(stream), grad_weights_sum, grad_image,
+                           sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, nio);
+    return check_launch();
+}
+
 extern "C" {
 
 int pnr_composite_rays_train_forward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, uint32_t M, uint32_t N,
@@ -521,13 +612,7 @@ int pnr_composite_rays_train_forward(const float* sigmas, const float* rgbs, con
     if (N == 0) return PNR_OK;
     if (!rays || !weights_sum || !depth || !image) return PNR_ERR_INVALID;
     if (M > 0 && (!sigmas || !rgbs || !deltas)) return PNR_ERR_INVALID;
-    if (M >= kCoopMinSamples)   // training batches: 16 lanes per ray
-        hipLaunchKernelGGL(k_composite_train_fwd_coop, dim3(cdiv(N * kLanesPerRay, kBlock)), dim3(kBlock), 0, as_stream(stream), sigmas, rgbs, deltas,
-                           rays, M, N, T_thresh, weights_sum, depth, image);
-    else
-        hipLaunchKernelGGL(k_composite_train_fwd, dim3(cdiv(N, kBlock)), dim3(kBlock), 0, as_stream(stream), sigmas, rgbs, deltas, rays, M, N,
-                           T_thresh, weights_sum, depth, image);
-    return check_launch();
+    return composite_train_forward<false>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image, {}, stream);
 }
 
 int pnr_composite_rays_train_backward(const float* grad_weights_sum, const float* grad_image, const float* sigmas, const float* rgbs,
@@ -536,13 +621,29 @@ int pnr_composite_rays_train_backward(const float* grad_weights_sum, const float
     if (N == 0 || M == 0) return PNR_OK;
     if (!grad_weights_sum || !grad_image || !sigmas || !rgbs || !deltas || !rays || !weights_sum || !image || !grad_sigmas || !grad_rgbs)
         return PNR_ERR_INVALID;
-    if (M >= kCoopMinSamples)
-        hipLaunchKernelGGL(k_composite_train_bwd_coop, dim3(cdiv(N * kLanesPerRay, kBlock)), dim3(kBlock), 0, as_stream(stream), grad_weights_sum,
-                           grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs);
-    else
-        hipLaunchKernelGGL(k_composite_train_bwd, dim3(cdiv(N, kBlock)), dim3(kBlock), 0, as_stream(stream), grad_weights_sum, grad_image, sigmas,
-                           rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs);
-    return check_launch();
+    return composite_train_backward<false>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas,
+                                           grad_rgbs, {}, stream);
+}
+
+int pnr_composite_rays_train_norm_forward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays, const float* rays_gt,
+                                          uint32_t M, uint32_t N, float T_thresh, float* weights_sum, float* depth, float* image, float* rgb_norm,
+                                          pnr_stream_t stream) {
+    if (N == 0) return PNR_OK;
+    if (!rays || !rays_gt || !weights_sum || !depth || !image || !rgb_norm) return PNR_ERR_INVALID;
+    if (M > 0 && (!sigmas || !rgbs || !deltas)) return PNR_ERR_INVALID;
+    return composite_train_forward<true>(sigmas, rgbs, deltas, rays, M, N, T_thresh, weights_sum, depth, image, {rays_gt, rgb_norm}, stream);
+}
+
+int pnr_composite_rays_train_norm_backward(const float* grad_weights_sum, const float* grad_image, const float* grad_rgb_norm, const float* sigmas,
+                                           const float* rgbs, const float* deltas, const int32_t* rays, const float* rays_gt,
+                                           const float* weights_sum, const float* image, const float* rgb_norm, uint32_t M, uint32_t N,
+                                           float T_thresh, float* grad_sigmas, float* grad_rgbs, pnr_stream_t stream) {
+    if (N == 0 || M == 0) return PNR_OK;
+    if (!grad_weights_sum || !grad_image || !grad_rgb_norm || !sigmas || !rgbs || !deltas || !rays || !rays_gt || !weights_sum || !image ||
+        !rgb_norm || !grad_sigmas || !grad_rgbs)
+        return PNR_ERR_INVALID;
+    return composite_train_backward<true>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, T_thresh, grad_sigmas,
+                                          grad_rgbs, {grad_rgb_norm, rays_gt, rgb_norm}, stream);
 }
 
 int pnr_composite_rays_flex_train_forward(const float* sigmas, const float* input, const float* deltas, const int32_t* rays, uint32_t M,

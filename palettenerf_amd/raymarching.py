@@ -263,6 +263,59 @@ class _composite_rays_train(Function):
 composite_rays_train = _composite_rays_train.apply
 
 
+class _composite_rays_train_norm(Function):
+    """composite_rays_train with the NeRF stage's rgb_norm regulariser folded in (nerf/renderer.py:301-332: spread_ray_to_sample, the squared
+    distance to the ray's ground truth, a second composite of it repeated over three channels, their mean) -- one launch each way
+    (pnr_composite_rays_train_norm_*).  weights_sum, depth and image carry the bits of composite_rays_train; rays_gt [N, 3] is indexed by ray id
+    and receives no gradient."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, sigmas, rgbs, deltas, rays, rays_gt, T_thresh=1e-4):
+        sigmas, rgbs, deltas, rays_gt = sigmas.contiguous(), rgbs.contiguous(), deltas.contiguous(), rays_gt.contiguous()
+        M, N = sigmas.shape[0], rays.shape[0]
+        if rays_gt.shape[0] != N or rays_gt.shape[-1] != 3:
+            raise RuntimeError("composite_rays_train_norm: rays_gt must be [N, 3], one row per ray id")
+        weights_sum = torch.empty(N, dtype=sigmas.dtype, device=sigmas.device)
+        depth = torch.empty(N, dtype=sigmas.dtype, device=sigmas.device)
+        image = torch.empty(N, 3, dtype=sigmas.dtype, device=sigmas.device)
+        rgb_norm = torch.empty(N, dtype=sigmas.dtype, device=sigmas.device)
+        call("pnr_composite_rays_train_norm_forward", ptr(require(sigmas, torch.float32, "sigmas")), ptr(require(rgbs, torch.float32, "rgbs")),
+             ptr(require(deltas, torch.float32, "deltas")), ptr(require(rays, torch.int32, "rays")), ptr(require(rays_gt, torch.float32, "rays_gt")),
+             _u32(M), _u32(N), _f32(T_thresh), ptr(weights_sum), ptr(depth), ptr(image), ptr(rgb_norm))
+        ctx.save_for_backward(sigmas, rgbs, deltas, rays, rays_gt, weights_sum, image, rgb_norm)
+        ctx.dims = [M, N, T_thresh]
+        ctx.set_materialize_grads(False)
+        return weights_sum, depth, image, rgb_norm
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, grad_weights_sum, grad_depth, grad_image, grad_rgb_norm):
+        # grad_depth is ignored, as in composite_rays_train
+        sigmas, rgbs, deltas, rays, rays_gt, weights_sum, image, rgb_norm = ctx.saved_tensors
+        M, N, T_thresh = ctx.dims
+        if grad_weights_sum is None and grad_image is None and grad_rgb_norm is None:
+            return None, None, None, None, None, None
+        grad_weights_sum = torch.zeros_like(weights_sum) if grad_weights_sum is None else grad_weights_sum.contiguous()
+        grad_image = torch.zeros_like(image) if grad_image is None else grad_image.contiguous()
+        grad_sigmas, grad_rgbs = torch.zeros_like(sigmas), torch.zeros_like(rgbs)
+        gws, gim = ptr(require(grad_weights_sum, torch.float32, "grad_weights_sum")), ptr(require(grad_image, torch.float32, "grad_image"))
+        if grad_rgb_norm is None:   # nobody read the norm: the plain backward, its bits
+            call("pnr_composite_rays_train_backward", gws, gim, ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), ptr(weights_sum), ptr(image),
+                 _u32(M), _u32(N), _f32(T_thresh), ptr(grad_sigmas), ptr(grad_rgbs))
+        else:
+            grad_rgb_norm = grad_rgb_norm.contiguous()
+            call("pnr_composite_rays_train_norm_backward", gws, gim, ptr(require(grad_rgb_norm, torch.float32, "grad_rgb_norm")),
+                 ptr(sigmas), ptr(rgbs), ptr(deltas), ptr(rays), ptr(rays_gt), ptr(weights_sum), ptr(image), ptr(rgb_norm), _u32(M), _u32(N),
+                 _f32(T_thresh), ptr(grad_sigmas), ptr(grad_rgbs))
+        return grad_sigmas, grad_rgbs, None, None, None, None
+
+
+def composite_rays_train_norm(sigmas, rgbs, deltas, rays, rays_gt, T_thresh=1e-4):
+    """-> (weights_sum [N], depth [N], image [N, 3], rgb_norm [N]); see _composite_rays_train_norm."""
+    return _composite_rays_train_norm.apply(sigmas, rgbs, deltas, rays, rays_gt, T_thresh)
+
+
 class _composite_rays_flex_train(Function):
     """raymarching/raymarching.py:294-341"""
 

@@ -638,16 +638,23 @@ class NeRFRenderer(_OccupancyMaintenance, _RendererBase):
                                                                     force_all_rays, dt_gamma, max_steps)
             sigmas, rgbs = self(xyzs, dirs)
             sigmas = self.density_scale * sigmas
-            if rays_gt is not None:
-                gt_rgbs = torch.zeros_like(xyzs)
-                raymarching.spread_ray_to_sample(rays_gt, rays, gt_rgbs)
-                rgb_norm = ((gt_rgbs - rgbs) ** 2).sum(-1, keepdim=True).repeat(1, 3)
-            weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh)
-            if rays_gt is not None:
-                _, _, rgb_norm_map = raymarching.composite_rays_train(sigmas, rgb_norm, deltas, rays, T_thresh)
-                rgb_norm_map = rgb_norm_map.mean(dim=-1).view(*prefix)
-            else:   # the reference composites an all-zero rgb_norm here (nerf/renderer.py:304-309, 327): the map is exactly zero and so is its gradient
-                rgb_norm_map = torch.zeros(*prefix, dtype=image.dtype, device=image.device)
+            if rays_gt is not None and sigmas.is_cuda and rays_gt.is_cuda and getattr(self, "fused_train_norm", True):
+                # the rgb_norm regulariser as a fourth quantity of the ONE training composite (pnr_composite_rays_train_norm_*) instead of the
+                # reference's chain in the other branch (~20 launches with autograd's share, a second walk over every ray's samples); same
+                # weights_sum / depth / image bits.  fused_train_norm = False keeps the chain.
+                weights_sum, depth, image, rgb_norm_map = raymarching.composite_rays_train_norm(sigmas, rgbs, deltas, rays, rays_gt, T_thresh)
+                rgb_norm_map = rgb_norm_map.view(*prefix)
+            else:
+                if rays_gt is not None:
+                    gt_rgbs = torch.zeros_like(xyzs)
+                    raymarching.spread_ray_to_sample(rays_gt, rays, gt_rgbs)
+                    rgb_norm = ((gt_rgbs - rgbs) ** 2).sum(-1, keepdim=True).repeat(1, 3)
+                weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh)
+                if rays_gt is not None:
+                    _, _, rgb_norm_map = raymarching.composite_rays_train(sigmas, rgb_norm, deltas, rays, T_thresh)
+                    rgb_norm_map = rgb_norm_map.mean(dim=-1).view(*prefix)
+                else:   # the reference composites an all-zero rgb_norm here (nerf/renderer.py:304-309, 327): the map is exactly zero and so is its gradient
+                    rgb_norm_map = torch.zeros(*prefix, dtype=image.dtype, device=image.device)
             # image and depth (nerf/renderer.py:328-332: background blend, depth normalisation) are formed on first access; train_loss()
             # computes them, the loss and the gradients from results.raw in one launch each way instead
             results = TrainResults(RawTrain(weights_sum, depth, image, None, nears, fars, bg_color, tuple(prefix), 0, 0))

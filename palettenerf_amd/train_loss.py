@@ -158,13 +158,18 @@ class _train_loss(Function):
 
 
 def train_loss(results, gt_rgb, lambda_sparsity=0.0, lambda_offsets=0.0, lambda_view_dep=0.0, lambda_smooth=0.0, lambda_weight=0.0,
-               lambda_palette=0.0, gt_weights=None, gt_clip=None, basis_color=None, basis_color_origin=None, want_outputs=True):
+               lambda_palette=0.0, gt_weights=None, gt_clip=None, basis_color=None, basis_color_origin=None, want_outputs=True, lambda_sparse=0.0):
     """palette/utils.py:483-600 (`train_step` from `pred_rgb = outputs['image']` to `loss = loss.mean()`) on a TrainResults, MSE criterion:
     returns (loss, info) with info = {"terms": [10] tensor in TERM_NAMES order, "loss_ray": [N] per-ray colour error (the error map's input
     before the scalar terms), "image"/"depth"/"direct_rgb": detached renders for logging (None with want_outputs=False)}.
     gt_weights: the palette-weight guide (`get_palette_weight_with_hist`), gt_clip: feature targets (both optional; a clip term needs the model's
     pred_clip head).  basis_color + basis_color_origin add the palette anchor term.  A NeRF model's results (no all_map) give the colour term only
-    (nerf/utils.py:535); its `lambda_sparse` term stays with the caller."""
+    (nerf/utils.py:535).
+    lambda_sparse: the NeRF stage's rgb_norm regulariser (nerf/utils.py:535-571; the trainer's min(1, epoch / 50) ramp of the weight is the
+    caller's).  With a non-zero weight and `results["rgb_norm"]` present, loss becomes loss + lambda_sparse * rgb_norm.mean(), info["loss_ray"]
+    becomes loss_ray + lambda_sparse * rgb_norm (the per-ray value the reference's error map reads) and info["loss_sparse"] is the added
+    scalar; `terms` keeps its ten entries (terms[0] is the loss without this term).  These are a few [N]-sized torch launches on purpose:
+    folding the term into pnr_train_loss_* needs new fields in pnr_train_loss_args, i.e. an ABI bump.  With lambda_sparse == 0 nothing changes."""
     raw = getattr(results, "raw", results)
     if not isinstance(raw, RawTrain):
         raise RuntimeError("train_loss needs the TrainResults of a training-mode run_cuda (results.raw)")
@@ -178,4 +183,12 @@ def train_loss(results, gt_rgb, lambda_sparsity=0.0, lambda_offsets=0.0, lambda_
                want_outputs=want_outputs)
     loss, terms, loss_ray, image, depth, direct = _train_loss.apply(raw.weights_sum, raw.image_raw, raw.all_map, basis_color, cfg)
     shaped = lambda t, *tail: None if t is None else t.view(*raw.prefix, *tail)   # noqa: E731
-    return loss, {"terms": terms, "loss_ray": shaped(loss_ray), "image": shaped(image, 3), "depth": shaped(depth), "direct_rgb": shaped(direct, 3)}
+    info = {"terms": terms, "loss_ray": shaped(loss_ray), "image": shaped(image, 3), "depth": shaped(depth), "direct_rgb": shaped(direct, 3)}
+    rgb_norm = results.get("rgb_norm") if lambda_sparse != 0 and isinstance(results, dict) else None
+    if rgb_norm is not None:
+        rgb_norm = rgb_norm.float()
+        sparse = lambda_sparse * rgb_norm.mean()
+        loss = loss + sparse
+        info["loss_ray"] = info["loss_ray"] + lambda_sparse * rgb_norm.detach().view(*raw.prefix)
+        info["loss_sparse"] = sparse.detach()
+    return loss, info
