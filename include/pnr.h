@@ -756,7 +756,8 @@ int pnr_palette_heads_backward(const float* h, const float* w_offsets_radiance, 
  *   terms[0] = loss;  loss_ray [N] = mean_c (image - gt_rgb)^2 (what the reference's error map reads before the scalar terms are added)
  * all_map columns are those of pnr_palette_train_shade_forward's all_buffer after the flex composite; n_channel = 13 + clip_dim + num_basis,
  * or 0 with all_map NULL (the NeRF model: only the first term).  bg_mode 0: the constant bg_const; 1: bg_color [3]; 2: bg_color [N,3]
- * (no gradient reaches the background).  The sums are reduced in a fixed order (workgroup partials in `workspace`, combined by the last
+ * (pnr_train_loss_forward / _backward send no gradient to the background; a per-ray background that trains gets its own from
+ * pnr_train_loss_backward_bg).  The sums are reduced in a fixed order (workgroup partials in `workspace`, combined by the last
  * workgroup to finish), so the value is reproducible.  The backward multiplies by the device scalar *grad_loss and writes EVERY element of
  * grad_weights_sum [N], grad_image_raw [N,3], grad_all_map [N,n_channel] and (if not NULL) grad_basis_color [num_basis,3].
  * image / depth / direct_rgb / loss_ray may be NULL (not wanted); depth needs depth_raw, nears and fars. */
@@ -796,6 +797,11 @@ typedef struct pnr_train_loss_args {
 uint64_t pnr_train_loss_workspace_bytes(uint32_t N);
 int pnr_train_loss_forward(const pnr_train_loss_args* args, pnr_stream_t stream);
 int pnr_train_loss_backward(const pnr_train_loss_args* args, pnr_stream_t stream);
+/* The gradient of a per-ray background (bg_mode == 2: the background model of bg_radius > 0), one launch, every element written:
+ *   grad_bg_color[n,k] = (1 - weights_sum[n]) (d loss / d image[n,k] + d loss / d direct_rgb[n,k]) *grad_loss      (the second term with all_map only)
+ * Reads the forward's inputs and grad_loss from `args` (the grad_* outputs and the workspace are not touched).  Any other bg_mode is
+ * PNR_ERR_UNSUPPORTED; a missing grad_loss or grad_bg_color is PNR_ERR_INVALID; N = 0 is PNR_OK. */
+int pnr_train_loss_backward_bg(const pnr_train_loss_args* args, float* grad_bg_color /* [N,3] */, pnr_stream_t stream);
 
 /* replace rgb_to_hsv / hsv_to_rgb, palette/src/palette_func.h, palette.cu:135-149 */
 int pnr_rgb_to_hsv(uint32_t n, const float* input, float* output, pnr_stream_t stream);
@@ -840,6 +846,53 @@ typedef struct pnr_background_args {
 uint64_t pnr_background_packed_bytes(void);
 int pnr_background_pack(const float* w0, const float* w1, float* packed, pnr_stream_t stream);
 int pnr_background_forward(const pnr_background_args* args, pnr_stream_t stream);
+
+/* Training the background model (additive entries: the ABI version and pnr_background_args are unchanged).
+ *   pnr_background_train_forward: pnr_background_forward's arithmetic in the same order (the same bits) from the RAW weights -- w0 = bg_net.0.weight
+ *     [64, 24], w1 = bg_net.1.weight [3, 64], staged into LDS by the kernel, so no pack launch follows an optimiser step -- on the fp32 table.
+ *     Writes out [N,3] and ALWAYS coords_out [N,2] (the backward reads them as coords_in).
+ *   pnr_background_backward: from grad_rgb [N,3], the saved coordinates (coords_in, required), rays_d, the table and the raw weights: one ray per
+ *     lane, the hidden layer recomputed, the gradient taken through sigmoid and ReLU (a NaN stays a NaN).
+ *       grad_w0 [64, 24], grad_w1 [3, 64]: every workgroup leaves its rays' sums as one fp32 slab of `workspace`
+ *         (pnr_background_backward_workspace_bytes(N) bytes, 16-byte aligned, no initialisation needed) and a second small launch adds the slabs in a
+ *         fixed order and writes EVERY element: bitwise reproducible.
+ *       grad_table [table_rows, 2] fp32, ZEROED BY THE CALLER (NULL: not wanted): 4 levels x 4 corners x 2 features per ray by float atomics, the cells
+ *         of the forward; a ray whose coordinates fall outside [-1, 1] and a level that would reach beyond table_rows add nothing.
+ *     No gradient goes to the coordinates or the directions (the reference's rays carry none).
+ * Supported: the architecture of pnr_background_forward with an fp32 table (PNR_DTYPE_F32); anything else is PNR_ERR_UNSUPPORTED before anything is
+ * launched.  A null struct or a missing pointer is PNR_ERR_INVALID, a misaligned coordinate array, table or workspace PNR_ERR_ALIGNMENT, N = 0 PNR_OK. */
+typedef struct pnr_background_train_args {
+    uint32_t N;
+    const float* rays_o;           /* [N,3]; forward without coords_in only */
+    const float* rays_d;           /* [N,3] unit directions */
+    float radius;                  /* bg_radius; forward without coords_in only */
+    const float* coords_in;        /* forward: optional [N,2] (as pnr_background_args); backward: the forward's coords_out */
+    const void* embeddings;        /* encoder_bg table [table_rows, 2] fp32 */
+    int table_dtype;               /* PNR_DTYPE_F32 */
+    const int32_t* offsets;        /* device int32[num_levels + 1] */
+    uint32_t table_rows;
+    uint32_t num_levels, level_dim;
+    float S;                       /* log2(per_level_scale) */
+    uint32_t H;                    /* base_resolution */
+    uint32_t gridtype;             /* 0 hash, 1 tiled */
+    int align_corners;
+    uint32_t sh_degree, num_layers, hidden_dim;
+    const float* w0;               /* bg_net.0.weight [64, 24], row-major [out][in], device fp32 */
+    const float* w1;               /* bg_net.1.weight [3, 64] */
+    /* forward */
+    float* out;                    /* [N,3] fp32 */
+    float* coords_out;             /* [N,2] */
+    /* backward */
+    const float* grad_rgb;         /* [N,3] */
+    float* grad_w0;                /* [64, 24] */
+    float* grad_w1;                /* [3, 64] */
+    float* grad_table;             /* [table_rows, 2], zeroed by the caller; optional */
+    void* workspace;
+    uint64_t workspace_bytes;
+} pnr_background_train_args;
+int pnr_background_train_forward(const pnr_background_train_args* args, pnr_stream_t stream);
+uint64_t pnr_background_backward_workspace_bytes(uint32_t N);
+int pnr_background_backward(const pnr_background_train_args* args, pnr_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -114,11 +114,15 @@ SIGNATURES = {
     "pnr_background_packed_bytes": [],
     "pnr_background_pack": [_ptr, _ptr, _ptr, _ptr],
     "pnr_background_forward": [_ptr, _ptr],
+    "pnr_background_train_forward": [_ptr, _ptr],
+    "pnr_background_backward_workspace_bytes": [_u32],
+    "pnr_background_backward": [_ptr, _ptr],
+    "pnr_train_loss_backward_bg": [_ptr, _ptr, _ptr],
 }
 _RESTYPES = {"pnr_occupancy_workspace_bytes": _u64, "pnr_occupancy_samples": _u32, "pnr_adam_max_tensors": _u32, "pnr_error_string": ctypes.c_char_p, "pnr_scan_scratch_bytes": _u64, "pnr_nerf_field_packed_bytes": _u64, "pnr_occupancy_mip_bytes": _u64, "pnr_nerf_frame_workspace_bytes": _u64, "pnr_palette_field_packed_bytes": _u64, "pnr_palette_frame_workspace_bytes": _u64,
              "pnr_palette_aux_channels": _u32, "pnr_linear_wgrad_workspace_bytes": _u64, "pnr_grid_backward_binned_workspace_bytes": _u64,
              "pnr_palette_train_shade_workspace_bytes": _u64, "pnr_train_loss_workspace_bytes": _u64, "pnr_mlp_packed_bytes": _u64, "pnr_mlp_backward_workspace_bytes": _u64,
-             "pnr_background_packed_bytes": _u64}
+             "pnr_background_packed_bytes": _u64, "pnr_background_backward_workspace_bytes": _u64}
 
 class AdamTensor(ctypes.Structure):
     """Mirror of `pnr_adam_tensor` (include/pnr.h)."""
@@ -226,6 +230,15 @@ class BackgroundArgs(ctypes.Structure):
                 ("offsets", _ptr), ("table_rows", _u32), ("num_levels", _u32), ("level_dim", _u32), ("S", _f32), ("H", _u32), ("gridtype", _u32),
                 ("align_corners", _int), ("sh_degree", _u32), ("num_layers", _u32), ("hidden_dim", _u32), ("packed", _ptr), ("out", _ptr),
                 ("coords_out", _ptr)]
+
+
+class BackgroundTrainArgs(ctypes.Structure):
+    """Mirror of `pnr_background_train_args` (include/pnr.h)."""
+    _fields_ = [("N", _u32), ("rays_o", _ptr), ("rays_d", _ptr), ("radius", _f32), ("coords_in", _ptr), ("embeddings", _ptr), ("table_dtype", _int),
+                ("offsets", _ptr), ("table_rows", _u32), ("num_levels", _u32), ("level_dim", _u32), ("S", _f32), ("H", _u32), ("gridtype", _u32),
+                ("align_corners", _int), ("sh_degree", _u32), ("num_layers", _u32), ("hidden_dim", _u32), ("w0", _ptr), ("w1", _ptr), ("out", _ptr),
+                ("coords_out", _ptr), ("grad_rgb", _ptr), ("grad_w0", _ptr), ("grad_w1", _ptr), ("grad_table", _ptr), ("workspace", _ptr),
+                ("workspace_bytes", _u64)]
 
 
 _lib = None

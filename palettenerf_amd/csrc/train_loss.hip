@@ -8,6 +8,7 @@
 // LDS -> one partial row per workgroup, and the LAST workgroup to finish (an agent-scope acq_rel ticket) adds the partial rows in a fixed
 // order and writes the ten loss terms -- reproducible, no second launch.  Backward: one thread per gradient element; every element of
 // grad_weights_sum / grad_image_raw / grad_all_map is written (no zero fill by the caller), scaled by the incoming device scalar.
+// pnr_train_loss_backward_bg is a third, optional launch: the gradient of a per-ray background (bg_radius > 0), [N,3].
 // Latency-bound by construction (N = 4096 rays: 0.6 MB in, 16 workgroups); the point is the launches it replaces.
 #include "pnr_common.hpp"
 
@@ -170,6 +171,20 @@ __global__ void __launch_bounds__(256) k_train_loss_bwd(pnr_train_loss_args a) {
     a.grad_weights_sum[n] = -acc * g;
 }
 
+// d loss / d bg_color for a per-ray background (bg_mode 2): the background enters image and direct_rgb with the factor 1 - weights_sum, so this is
+// that factor times the colour gradients k_train_loss_bwd forms for grad_image_raw and for all_map's direct columns.  One thread per element.
+__global__ void __launch_bounds__(256) k_train_loss_bwd_bg(pnr_train_loss_args a, float* __restrict__ grad_bg) {
+    const uint32_t idx = blockIdx.x * 256 + threadIdx.x, C = a.n_channel;
+    if (idx >= a.N * 3) return;
+    const uint32_t n = idx / 3, k = idx - n * 3;
+    const float inv_3n = 1.0f / ((float)a.N * 3.0f);
+    const float om = 1.0f - a.weights_sum[n];
+    const float bg = a.bg_color[(size_t)n * 3 + k], gt = a.gt_rgb[(size_t)n * 3 + k];
+    float gk = 2.0f * ((a.image_raw[(size_t)n * 3 + k] + om * bg) - gt) * inv_3n;
+    if (a.all_map) gk += 2.0f * ((a.all_map[(size_t)n * C + 7 + k] + om * bg) - gt) * inv_3n;
+    grad_bg[idx] = om * gk * a.grad_loss[0];
+}
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -204,6 +219,15 @@ int pnr_train_loss_backward(const pnr_train_loss_args* a, pnr_stream_t stream) {
     if (a->N == 0) return PNR_OK;
     if (!a->grad_loss || !a->grad_weights_sum || !a->grad_image_raw || (a->all_map && !a->grad_all_map)) return PNR_ERR_INVALID;
     hipLaunchKernelGGL(k_train_loss_bwd, dim3(cdiv(a->N * (a->n_channel + 4), 256)), dim3(256), 0, as_stream(stream), *a);
+    return check_launch();
+}
+
+int pnr_train_loss_backward_bg(const pnr_train_loss_args* a, float* grad_bg_color, pnr_stream_t stream) {
+    if (const int rc = train_loss_check(a)) return rc;
+    if (a->bg_mode != 2) return PNR_ERR_UNSUPPORTED;      // a constant or [3] background takes no gradient here
+    if (a->N == 0) return PNR_OK;
+    if (!a->grad_loss || !grad_bg_color) return PNR_ERR_INVALID;
+    hipLaunchKernelGGL(k_train_loss_bwd_bg, dim3(cdiv(a->N * 3, 256)), dim3(256), 0, as_stream(stream), *a, grad_bg_color);
     return check_launch();
 }
 

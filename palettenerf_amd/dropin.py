@@ -58,7 +58,9 @@ def fuse_field(model, precision="f16x3", pair_lookup=False):
     version counters only: after writing the tables through `.data` (torch_ema's copy_to / restore around an evaluation) call
     invalidate_fused_caches(model), or the forward reads the old tables.  Default: the live tables, whatever wrote them.
     A model with a background (bg_radius > 0) also gets `background(x, d)` bound the same way: encoder_bg, SH, bg_net and the sigmoid as one launch
-    (pnr_background_forward over the coordinates the caller's sph_from_ray produced) for the same inference batches, the model's own method otherwise;
+    (pnr_background_forward over the coordinates the caller's sph_from_ray produced) for the same inference batches, one launch each way for training
+    batches (fp32 device inputs that need no gradient; pnr_background_train_forward / pnr_background_backward, `model.fused_train_background = False` turns
+    that off), the model's own method otherwise;
     a background that is not the reference's architecture (4 x 2 levels, SH degree 4, 24 -> 64 -> 3) keeps the model's own method."""
     import torch
     from .fused import NeRFFieldFused, PaletteFieldFused
@@ -214,7 +216,7 @@ def bind_background(model):
     binds a twin's again, over the twin's).  Nothing is bound without a background or for an architecture the launch does not support: the per-op
     formulation stays."""
     import torch
-    from .fused import background_fused
+    from .fused import background_fused, background_train_fused
     model.__dict__.pop("background", None)
     bg_fused = background_fused(model) if getattr(model, "bg_radius", 0) > 0 and getattr(model, "bg_net", None) is not None else None
     if bg_fused is None:
@@ -222,7 +224,10 @@ def bind_background(model):
     plain_bg = model.background
 
     def background(x, d):
-        if torch.is_grad_enabled() or torch.is_autocast_enabled() or not x.is_cuda:
+        if torch.is_grad_enabled():       # training batches: one launch each way, unless model.fused_train_background says no
+            train = background_train_fused(model, x, d, fused_kernels=True)     # the model's BackgroundFused as it is NOW, or None
+            return train.train_from_coords(x, d) if train is not None else plain_bg(x, d)
+        if torch.is_autocast_enabled() or not x.is_cuda:
             return plain_bg(x, d)
         return bg_fused.from_coords(x, d)
 

@@ -619,7 +619,8 @@ class BackgroundFused:
     `encoder_bg`, SH, bg_net, sigmoid), for inference batches.  Conventions of the field classes: the weight blob and, for the reference's -O mode,
     the half copy of the table are cached and rebuilt when torch's version counters move (_pkey) or invalidate_fused_caches(model) says so; a
     repack goes into a NEW tensor, so a launch already enqueued keeps reading what it was given; `state()` changes whenever a cached blob was
-    or has to be rebuilt, which is how a frame prepared before a weight change is recognised (renderer.render_launch)."""
+    or has to be rebuilt, which is how a frame prepared before a weight change is recognised (renderer.render_launch).
+    Training batches (train_from_rays / train_from_coords) use none of these caches: the launches read the parameters themselves."""
 
     def __init__(self, model):
         if not self.supported(model):
@@ -710,6 +711,102 @@ class BackgroundFused:
     def from_coords(self, x, d, half=None):
         """NeRFNetwork.background(x, d): x [N,2] the coordinates of sph_from_ray, d [N,3]."""
         return self._launch(None, d, x, False, half).view(*d.shape[:-1], 3)
+
+    def _train_args(self, N, rays_d, coords, table):
+        m, enc = self.model, self.model.encoder_bg
+        a = _lib.BackgroundTrainArgs()
+        a.N, a.rays_d, a.coords_in = N, rays_d.data_ptr(), ptr(coords)
+        a.embeddings, a.table_dtype, a.offsets, a.table_rows = table.data_ptr(), 0, require(enc.offsets, torch.int32, "offsets").data_ptr(), int(table.shape[0])
+        a.num_levels, a.level_dim, a.S, a.H = enc.num_levels, enc.level_dim, float(np.log2(enc.per_level_scale)), enc.base_resolution
+        a.gridtype, a.align_corners = enc.gridtype_id, int(enc.align_corners)
+        a.sh_degree, a.num_layers, a.hidden_dim = int(m.encoder_dir.degree), int(m.num_layers_bg), int(m.hidden_dim_bg)
+        return a
+
+    def _train(self, rays_o, rays_d, coords):
+        """The training form: pnr_background_train_forward / pnr_background_backward behind one autograd.Function.  The table and the two weights are
+        the model's parameters as they are at this call (no packed blob, no cache: an optimiser step or a write through `.data` is simply read)."""
+        ws = self._weights()
+        return _BackgroundTrain.apply(self, rays_o, rays_d, coords, self.model.encoder_bg.embeddings, ws[0], ws[1])
+
+    def train_from_rays(self, rays_o, rays_d, want_coords=False):
+        """from_rays with a gradient for encoder_bg.embeddings and bg_net's weights (none for the rays): rays [N,3] -> [N,3], fp32 also under autocast.
+        want_coords: and the sphere coordinates [N,2] the backward will read."""
+        out, coords = self._train(rays_o, rays_d, None)
+        return (out, coords) if want_coords else out
+
+    def train_from_coords(self, x, d):
+        """from_coords with a gradient for the parameters (none for x or d)."""
+        return self._train(None, d, x)[0].view(*d.shape[:-1], 3)
+
+
+class _BackgroundTrain(torch.autograd.Function):
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)   # under autocast: fp32 in, the fp32 table, fp32 out
+    def forward(ctx, owner, rays_o, rays_d, coords, embeddings, w0, w1):
+        f32 = torch.float32
+        rays_d = require(rays_d.detach().reshape(-1, 3).contiguous(), f32, "rays_d")
+        N, dev = rays_d.shape[0], rays_d.device
+        table = require(embeddings.detach(), f32, "encoder_bg.embeddings")
+        w0_, w1_ = (require(w.detach().contiguous(), f32, "bg_net weight") for w in (w0, w1))
+        if coords is not None:
+            coords = require(coords.detach().reshape(-1, 2).contiguous(), f32, "coords")
+            if coords.shape[0] != N:
+                raise RuntimeError("background: one coordinate pair per direction")
+        out = torch.empty(N, 3, dtype=f32, device=dev)
+        coords_out = torch.empty(N, 2, dtype=f32, device=dev)
+        a = owner._train_args(N, rays_d, coords, table)
+        if coords is None:
+            rays_o = require(rays_o.detach().reshape(-1, 3).contiguous(), f32, "rays_o")
+            if rays_o.shape[0] != N:
+                raise RuntimeError("background: one origin per direction")
+            a.rays_o, a.radius = rays_o.data_ptr(), float(owner.model.bg_radius)
+        a.w0, a.w1, a.out, a.coords_out = w0_.data_ptr(), w1_.data_ptr(), out.data_ptr(), coords_out.data_ptr()
+        call("pnr_background_train_forward", ctypes.byref(a), units=N)
+        ctx.owner = owner
+        ctx.save_for_backward(coords_out, rays_d, embeddings, w0, w1)
+        ctx.mark_non_differentiable(coords_out)
+        return out, coords_out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # no double backward: asking for one raises
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_rgb, _grad_coords):
+        coords, rays_d, embeddings, w0, w1 = ctx.saved_tensors
+        f32 = torch.float32
+        N, dev = rays_d.shape[0], rays_d.device
+        table = require(embeddings.detach(), f32, "encoder_bg.embeddings")
+        w0_, w1_ = (require(w.detach().contiguous(), f32, "bg_net weight") for w in (w0, w1))
+        g_w0, g_w1 = torch.empty_like(w0_), torch.empty_like(w1_)
+        g_table = torch.zeros_like(table) if ctx.needs_input_grad[4] else None
+        if N == 0:
+            return None, None, None, None, g_table, g_w0.zero_(), g_w1.zero_()
+        grad_rgb = require(grad_rgb.detach().reshape(-1, 3).float().contiguous(), f32, "grad_rgb")
+        nbytes = int(_lib.load().pnr_background_backward_workspace_bytes(N))
+        work = torch.empty(nbytes // 4, dtype=f32, device=dev)
+        a = ctx.owner._train_args(N, rays_d, coords, table)
+        a.w0, a.w1, a.grad_rgb, a.grad_w0, a.grad_w1, a.grad_table = w0_.data_ptr(), w1_.data_ptr(), grad_rgb.data_ptr(), g_w0.data_ptr(), g_w1.data_ptr(), ptr(g_table)
+        a.workspace, a.workspace_bytes = work.data_ptr(), nbytes
+        call("pnr_background_backward", ctypes.byref(a), units=N)
+        return None, None, None, None, g_table, g_w0, g_w1
+
+
+def background_train_fused(model, *inputs, fused_kernels=None):
+    """The model's BackgroundFused for a TRAINING batch (train_from_rays / train_from_coords), or None: the per-op formulation stays.  The batch
+    takes the fused path when gradients are enabled, the switch `model.fused_train_background` is on (the default), every input is an fp32 device
+    tensor that needs no gradient itself, the model asked for fused kernels (the condition of the inference launch) and its background is the
+    architecture the kernels support, with its parameters on the device.  fused_kernels: the caller's own answer to "asked for fused kernels"
+    (dropin.fuse_field's binding is one)."""
+    if not torch.is_grad_enabled() or not getattr(model, "fused_train_background", True):
+        return None
+    if fused_kernels is None:
+        fused_kernels = bool(getattr(model, "fused_field", False)) or getattr(model, "march_mode", None) == "native"
+    if not fused_kernels:
+        return None
+    for t in inputs:
+        if not t.is_cuda or t.dtype != torch.float32 or t.requires_grad:
+            return None
+    f = background_fused(model)
+    return f if f is not None and model.encoder_bg.embeddings.is_cuda else None
 
 
 def background_fused(model):

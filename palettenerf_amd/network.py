@@ -99,6 +99,11 @@ def _background(m, x, d):
     if _background_fused_ok(m, x, d):
         from .fused import background_fused
         return background_fused(m).from_coords(x, d)
+    if torch.is_grad_enabled() and x.shape[-1] == 2 and d.shape[-1] == 3:     # training batches: one launch each way (fused.BackgroundFused.train_from_coords)
+        from .fused import background_train_fused
+        fused = background_train_fused(m, x, d)
+        if fused is not None:
+            return fused.train_from_coords(x, d)
     h = m.encoder_bg(x)                                    # default bound = 1
     h = torch.cat([m.encoder_dir(d), h], dim=-1)           # the direction features come first
     for l in range(m.num_layers_bg):

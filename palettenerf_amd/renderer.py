@@ -274,8 +274,14 @@ class _RendererBase(nn.Module):
 
     def _background_of_rays(self, rays_o, rays_d):
         """bg_radius > 0: the per-ray background colour [N,3] (nerf/renderer.py:270-273).  Inference frames on the fused paths take one launch for
-        sph_from_ray + background() (fused.BackgroundFused.from_rays: the same coordinates, bit for bit); everything else the two calls."""
+        sph_from_ray + background() (fused.BackgroundFused.from_rays: the same coordinates, bit for bit), training batches one launch each way
+        (train_from_rays; `fused_train_background = False` keeps the per-op formulation); everything else the two calls."""
         bg = self.__dict__.get("background")       # an instance attribute (dropin.fuse_field) decides for itself
+        if bg is None and torch.is_grad_enabled():
+            from .fused import background_train_fused
+            fused = background_train_fused(self, rays_o, rays_d)
+            if fused is not None:
+                return fused.train_from_rays(rays_o, rays_d)
         if bg is None and not torch.is_grad_enabled() and rays_o.is_cuda and rays_o.dtype == torch.float32 and rays_d.dtype == torch.float32 \
                 and (bool(getattr(self, "fused_field", False)) or self.march_mode == "native"):
             from .fused import background_fused

@@ -6,6 +6,8 @@ the backward) are formed only when somebody reads them.  `train_loss(results, gt
 with the MSE criterion of main_palette.py:222; nerf/utils.py:534-556) computed straight from the raw composites `results.raw` -- blend, depth,
 every loss term, and in the backward every gradient of weights_sum / image / all_map -- without touching those lazy entries.  Same value as the
 torch formulation to rounding (sums are reduced in a fixed order of their own); any other criterion keeps using the dict entries.
+A per-ray background that needs a gradient (the background model of bg_radius > 0, [N,3]) gets it from one more launch in the backward
+(pnr_train_loss_backward_bg); a trainable background of any other shape raises.
 """
 import collections
 import ctypes
@@ -81,7 +83,7 @@ def _rows(t, n, width, name):
 class _train_loss(Function):
     @staticmethod
     @custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, weights_sum, image_raw, all_map, basis_color, cfg):
+    def forward(ctx, weights_sum, image_raw, all_map, basis_color, bg_color, cfg):
         dev, f32 = weights_sum.device, torch.float32
         N = weights_sum.shape[0]
         a = _lib.TrainLossArgs()
@@ -99,12 +101,18 @@ class _train_loss(Function):
         want = cfg["want_outputs"]
         depth_raw = _rows(cfg["depth_raw"], N, 0, "depth") if want else None
         a.depth_raw, a.nears, a.fars = P(depth_raw), P(_rows(cfg["nears"], N, 0, "nears")), P(_rows(cfg["fars"], N, 0, "fars"))
-        bg = cfg["bg_color"]
+        bg = bg_color if bg_color is not None else cfg["bg_color"]     # a tensor travels as an input (its gradient: backward), a number in cfg
+        ctx.bg_shape = None
         if torch.is_tensor(bg):
-            if bg.requires_grad:
-                raise RuntimeError("train_loss: a background that needs a gradient (bg_radius > 0) takes the torch formulation")
+            trains = bool(ctx.needs_input_grad[4])     # (the tensor itself may be a cast copy by now)
+            if trains and not (bg.ndim >= 2 and bg.shape[-1] == 3 and bg.numel() == 3 * N):
+                raise RuntimeError(f"train_loss: a background that needs a gradient must be per ray, [N,3] (the background model of bg_radius > 0); "
+                                   f"a trainable background of shape {tuple(bg.shape)} takes the torch formulation")
             bg = bg.detach().to(dev, f32)
-            if bg.numel() == 1:
+            if trains:
+                ctx.bg_shape = bg.shape
+                a.bg_mode, a.bg_color = 2, P(_rows(bg, N, 3, "bg_color"))
+            elif bg.numel() == 1:
                 a.bg_mode, a.bg_const = 0, float(bg)
             elif bg.numel() == 3:
                 a.bg_mode, a.bg_color = 1, P(bg.reshape(3).contiguous())
@@ -142,7 +150,7 @@ class _train_loss(Function):
     @custom_bwd(device_type="cuda")
     def backward(ctx, g_loss, *_):
         if g_loss is None:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         a = ctx.args
         dev, f32 = g_loss.device, torch.float32
         N, C = a.N, a.n_channel
@@ -153,8 +161,13 @@ class _train_loss(Function):
         g_bc = torch.empty(a.num_basis, 3, device=dev, dtype=f32) if ctx.shapes[3] is not None and ctx.needs_input_grad[3] else None
         a.grad_loss, a.grad_weights_sum, a.grad_image_raw, a.grad_all_map, a.grad_basis_color = ptr(g), ptr(g_ws), ptr(g_im), ptr(g_am), ptr(g_bc)
         _lib.call("pnr_train_loss_backward", ctypes.byref(a), stream_ptr())
+        g_bg = None
+        if ctx.bg_shape is not None and ctx.needs_input_grad[4]:      # the background model's colours: one more launch
+            g_bg = torch.empty(N, 3, device=dev, dtype=f32)
+            _lib.call("pnr_train_loss_backward_bg", ctypes.byref(a), ptr(g_bg), stream_ptr())
+            g_bg = g_bg.view(ctx.bg_shape)
         s = ctx.shapes
-        return (g_ws.view(s[0]), g_im.view(s[1]), None if g_am is None else g_am.view(s[2]), None if g_bc is None else g_bc.view(s[3]), None)
+        return (g_ws.view(s[0]), g_im.view(s[1]), None if g_am is None else g_am.view(s[2]), None if g_bc is None else g_bc.view(s[3]), g_bg, None)
 
 
 def train_loss(results, gt_rgb, lambda_sparsity=0.0, lambda_offsets=0.0, lambda_view_dep=0.0, lambda_smooth=0.0, lambda_weight=0.0,
@@ -181,7 +194,8 @@ def train_loss(results, gt_rgb, lambda_sparsity=0.0, lambda_offsets=0.0, lambda_
                gt_clip=gt_clip, gt_weights=gt_weights, basis_color_origin=basis_color_origin, lambda_sparsity=lambda_sparsity, lambda_offsets=lambda_offsets,
                lambda_view_dep=lambda_view_dep, lambda_smooth=lambda_smooth, lambda_weight=lambda_weight, lambda_palette=lambda_palette,
                want_outputs=want_outputs)
-    loss, terms, loss_ray, image, depth, direct = _train_loss.apply(raw.weights_sum, raw.image_raw, raw.all_map, basis_color, cfg)
+    loss, terms, loss_ray, image, depth, direct = _train_loss.apply(raw.weights_sum, raw.image_raw, raw.all_map, basis_color,
+                                                                    raw.bg_color if torch.is_tensor(raw.bg_color) else None, cfg)
     shaped = lambda t, *tail: None if t is None else t.view(*raw.prefix, *tail)   # noqa: E731
     info = {"terms": terms, "loss_ray": shaped(loss_ray), "image": shaped(image, 3), "depth": shaped(depth), "direct_rgb": shaped(direct, 3)}
     rgb_norm = results.get("rgb_norm") if lambda_sparse != 0 and isinstance(results, dict) else None
