@@ -66,7 +66,9 @@ int pnr_abi_version(void);
  * coarsest levels (tables of at most 16 384 rows) as LDS images instead of records; "cell_merge" (default 1): on its mid levels the samples of a ray that sit in
  * one cell are summed before their records are written; "scatter_staged" (default 1): its records are ordered by bucket in LDS and written coalesced
  * (0 = every lane writes its own records); "mlp_f16x3" (default 1): the training MLP launches use split-fp16 products; "train_coop" (default 1): pnr_march_rays_train*'s counting pass
- * marches four rays per wave cooperatively (same counts, same rows); "coop_march" also governs the cooperative tail of pnr_march_rays* */
+ * marches four rays per wave cooperatively (same counts, same rows); "coop_march" also governs the cooperative tail of pnr_march_rays*;
+ * "grid_lane_pairs" (default 1): the frame loops' lookup of one fp32 table puts the two x neighbours of a cell's corners into adjacent lanes of every gather
+ * of a workgroup row's finer level (0 = every lane loads its own eight corners); same encoder output, bit for bit */
 int pnr_set_option(const char* name, int value);
 
 /* ---------------------------------------------------------------- raymarching: utils ------- */
@@ -394,7 +396,7 @@ int pnr_nerf_render_frame(const pnr_nerf_frame_args* args, pnr_stream_t stream);
  * written through the pointers _submit was given.  One submitted frame per host thread and device (a second _submit is PNR_ERR_INVALID; a whole-frame call
  * drops a submitted frame that was never finished); no DEVICE buffer the frame reads or writes may be touched in between.  The frame likewise keeps the
  * pnr_set_option switches _submit saw (aux_fusion, composite_fusion, hosted_tail, march_budget, march_budget0, march_blocks, iteration_margin,
- * dynamic_tiles, block_skip, coop_march, palette_waves12): a pnr_set_option between the two calls applies from the next frame on.
+ * dynamic_tiles, block_skip, coop_march, palette_waves12, grid_lane_pairs): a pnr_set_option between the two calls applies from the next frame on.
  * pnr_nerf_render_frame == _submit + _finish.  (`noises` is read by the frame's first iteration, which _submit enqueues: it is one more input the caller
  * leaves alone until _finish.) */
 int pnr_nerf_render_frame_submit(const pnr_nerf_frame_args* args, pnr_stream_t stream);

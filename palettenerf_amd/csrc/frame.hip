@@ -688,6 +688,147 @@ __device__ __forceinline__ void grid_row(const GridArgs& g, const LevelCtx& lc, 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The lane-pair form of the level-major lookup (GK_SINGLE; pnr_set_option("grid_lane_pairs")).  Lanes 2k and 2k + 1 own rows b and
+// b + 1 as above -- position, weights, fmaf chain, store -- but split the LOADS by the corners' x bit instead of by row: lane parity p fetches the
+// four (x + p, y + j, z + k) corners of BOTH rows of its pair (grid_xside.hpp: x_side_rows), so in every one of the eight load instructions the two
+// lanes of a pair ask for (x, ..) and (x + 1, ..) of one cell: neighbouring table rows on a dense level, and on a hashed level too (x enters the hash
+// as itself: the two indices differ by an XOR with 2^k - 1), 15 times in 16 inside one 128-byte line.  The partner's cell travels over DPP
+// (quad_perm [1, 0, 3, 2]), and so do the four values of a lane's own row that the partner loaded; each lane then runs the reference's chain
+// idx = 0 .. 7 with its own weights: the output is grid_row's, bit for bit.  No LDS.
+// A row that is dead, flagged, out of range or outside [0, 1]^3 gets no loads from either lane (okA / okB: the pair's even / odd row is looked up).
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t dpp_swap_pair(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1 /* quad_perm [1, 0, 3, 2] */, 0xF, 0xF, true); }
+template <int KIND>
+__device__ __forceinline__ void grid_pair_level(const GridArgs& g, const LevelCtx& lc, uint32_t level, const void* __restrict__ table, float* __restrict__ enc0, uint32_t b,
+                                                const float (&in)[3], bool live, bool ok, bool odd, bool okA, bool okB) {
+    static_assert(KIND == GK_SINGLE, "the one-table fp32 layout");
+    constexpr int NW = 2;   // 32-bit words of a table row
+    typedef f32x2 RowT;
+    float pos[3];
+    uint32_t pg[3], ag[3], bg[3];
+#pragma unroll
+    for (int d = 0; d < 3; d++) {   // (a row that is not looked up arrives with in = 0)
+        pos[d] = fmaf(in[d], lc.scale, 0.5f);
+        const float fl = floorf(pos[d]);
+        pg[d] = (uint32_t)fl;
+        pos[d] -= (float)pg[d];
+        const uint32_t qg = dpp_swap_pair(pg[d]);
+        ag[d] = odd ? qg : pg[d];   // the cell of the pair's even row ...
+        bg[d] = odd ? pg[d] : qg;   // ... and of its odd row
+    }
+    uint32_t idxs[8];
+    x_side_rows<1>(lc.kind, g.gridtype, lc.hashmap_size, lc.resolution, ag, odd ? 1u : 0u, idxs);
+    x_side_rows<1>(lc.kind, g.gridtype, lc.hashmap_size, lc.resolution, bg, odd ? 1u : 0u, idxs + 4);
+    const RowT* tab = static_cast<const RowT*>(table) + lc.off0;
+    const RowT* p[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) p[i] = tab + idxs[i];
+    RowT v[8] = {};
+    if (okA && okB) load8_fresh(p, v);   // (the steady state: 99.7 % of a launch's rows are live)
+    else if (okA) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) v[i] = *(typename GlobalPtr<RowT>::type)(uintptr_t)p[i];
+    } else {
+#pragma unroll
+        for (int i = 4; i < 8; i++) v[i] = *(typename GlobalPtr<RowT>::type)(uintptr_t)p[i];
+    }
+    float ws[8];
+    grid_corner_weights(pos, ws);
+    // the eight corners of this lane's row in the reference's order: corner idx = xbit + 2 jk is this lane's load when xbit is its parity, else the partner's
+    uint32_t cw[8][NW];
+#pragma unroll
+    for (int jk = 0; jk < 4; jk++) {
+        uint32_t wa[NW], wb[NW];
+        __builtin_memcpy(wa, &v[jk], sizeof(wa));
+        __builtin_memcpy(wb, &v[4 + jk], sizeof(wb));
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            const uint32_t sa = dpp_swap_pair(wa[w]), sb = dpp_swap_pair(wb[w]);   // (every lane swaps both: a DPP read needs its source lane active)
+            cw[2 * jk][w] = odd ? sb : wa[w];
+            cw[2 * jk + 1][w] = odd ? wb[w] : sa;
+        }
+    }
+    const size_t o = ((size_t)level * g.level_stride + b) * 2;
+    float acc[2] = {0.0f, 0.0f};
+#pragma unroll
+    for (uint32_t idx = 0; idx < 8; idx++) {
+        acc[0] = fmaf(ws[idx], __builtin_bit_cast(float, cw[idx][0]), acc[0]);
+        acc[1] = fmaf(ws[idx], __builtin_bit_cast(float, cw[idx][1]), acc[1]);
+    }
+    const float2 out = make_float2(acc[0], acc[1]);
+    if (ok) *reinterpret_cast<float2*>(enc0 + o) = out;
+    else if (live) *reinterpret_cast<float2*>(enc0 + o) = make_float2(0.0f, 0.0f);   // outside [0, 1]^3: zeros, as grid_row writes them
+}
+// grid_row for a row whose position in [0, 1]^3 is already there (GK_SINGLE): the lane's own eight corners, as grid_row loads and sums them
+template <int KIND>
+__device__ __forceinline__ void grid_row_at(const GridArgs& g, const LevelCtx& lc, uint32_t level, const void* __restrict__ table, float* __restrict__ enc0, uint32_t b,
+                                            const float (&in)[3]) {
+    static_assert(KIND == GK_SINGLE, "the one-table fp32 layout");
+    float pos[3], ws[8];
+    uint32_t pg[3], idxs[8];
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        pos[d] = fmaf(in[d], lc.scale, 0.5f);
+        const float fl = floorf(pos[d]);
+        pg[d] = (uint32_t)fl;
+        pos[d] -= (float)pg[d];
+    }
+    corner_rows_by_kind<1>(lc.kind, g.gridtype, lc.hashmap_size, lc.resolution, pg, idxs);
+    f32x2 v[8];
+    gather8<f32x2, 1, true>(static_cast<const f32x2*>(table) + lc.off0, idxs, v);
+    grid_corner_weights(pos, ws);
+    float acc[2] = {0.0f, 0.0f};
+#pragma unroll
+    for (uint32_t idx = 0; idx < 8; idx++) { acc[0] = fmaf(ws[idx], v[idx].x, acc[0]); acc[1] = fmaf(ws[idx], v[idx].y, acc[1]); }
+    *reinterpret_cast<float2*>(enc0 + ((size_t)level * g.level_stride + b) * 2) = make_float2(acc[0], acc[1]);
+}
+// the row loop of a level-major workgroup in the lane-pair form: levels[0 .. NLV) for every row
+template <int KIND, uint32_t NLV>
+__device__ __forceinline__ void grid_pair_rows(const GridArgs& g, const LevelCtx (&lcs)[NLV], const uint32_t (&levels)[NLV], const void* __restrict__ table, float* __restrict__ enc0,
+                                               const uint8_t* __restrict__ rowflag, uint32_t first, uint32_t stride, uint32_t rows) {
+    const bool odd = (threadIdx.x & 1u) != 0;   // (first and stride are even: a lane's rows have its parity)
+    for (uint32_t b = first; (b & ~1u) < rows; b += stride) {   // a pair stays while either of its rows is in range
+        bool live = false, ok = false;
+        float in[3] = {0.0f, 0.0f, 0.0f};
+        if (b < rows) {
+            const float d0 = g.deltas[(size_t)b * 2];
+            const uint32_t fl = rowflag ? rowflag[b] : 0u;
+            live = d0 != 0.0f && !fl;
+        }
+        if (live) {
+            float xyz[3];
+#pragma unroll
+            for (int d = 0; d < 3; d++) xyz[d] = g.xyzs[(size_t)b * 3 + d];
+            asm volatile("" : "+v"(xyz[0]), "+v"(xyz[1]), "+v"(xyz[2]));   // (one 12-byte request: grid_corner_rows)
+            bool oob = false;
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                const float sft = xyz[d] + g.bound;
+                in[d] = g.inv_two_bound != 0.0f ? sft * g.inv_two_bound : sft / g.two_bound;
+                oob |= (in[d] < 0.0f) | (in[d] > 1.0f);
+            }
+            ok = !oob;
+            if (oob) { in[0] = 0.0f; in[1] = 0.0f; in[2] = 0.0f; }
+        }
+        const bool pok = dpp_swap_pair(ok ? 1u : 0u) != 0u;
+        const bool okA = odd ? pok : ok, okB = odd ? ok : pok;
+        if (!(okA || okB)) {   // (the same for both lanes of the pair: nothing to load)
+            if (live) {
+#pragma unroll
+                for (uint32_t l = 0; l < NLV; l++) *reinterpret_cast<float2*>(enc0 + ((size_t)levels[l] * g.level_stride + b) * 2) = make_float2(0.0f, 0.0f);
+            }
+            continue;
+        }
+        grid_pair_level<KIND>(g, lcs[0], levels[0], table, enc0, b, in, live, ok, odd, okA, okB);
+#pragma unroll
+        for (uint32_t l = 1; l < NLV; l++) {   // the workgroup row's coarse level: neighbouring lanes share its lines as it is, and the pair form's extra instructions only cost there
+            if (ok) grid_row_at<KIND>(g, lcs[l], levels[l], table, enc0, b, in);
+            else if (live) *reinterpret_cast<float2*>(enc0 + ((size_t)levels[l] * g.level_stride + b) * 2) = make_float2(0.0f, 0.0f);
+        }
+    }
+}
+
 #ifdef PNR_HOSTED_TIMING
 // instrumented builds only: wall-clock stamps (100 MHz) of ONE iteration's lookup launch.  [0..7]: launch-wide (earliest start, latest end of an
 // ordinary workgroup, latest end of a hosted one, rays queued); then 8 per hosted workgroup: start, mip staged, march done, lookups done, probes of its slowest lane
@@ -822,7 +963,10 @@ __device__ __forceinline__ void hosted_march_tail(const FrameCtl* ctl, const Gri
     }
 }
 
-template <int KIND>
+#ifndef PNR_LANE_PAIR_MIN_LEVEL
+#define PNR_LANE_PAIR_MIN_LEVEL 8u   // the lane-pair form from this level up: with two levels per workgroup row, the finer level of every row.  Measured 8 / 10 / 12 / 13: the lookup launch
+#endif                               // 61.8 / 63.2 / 64.8 / 65.2 us against 67.8 without (profiles/EXPERIMENTS.md); profiles/grid_line_sharing.py counts as many lines or more for the pair mapping below level 7
+template <int KIND, bool LANE_PAIRS = false>
 __device__ __forceinline__ void frame_grid_body(const FrameCtl* __restrict__ ctl, const GridArgs& g, const HostedArgs& h) {
     if (ctl->done) return;
     // GK_SINGLE with PNR_FRAME_LEVEL_PAIRS: a workgroup takes two levels, the y-th finest and the y-th coarsest, for each of its rows (8 instead of 16
@@ -857,6 +1001,24 @@ __device__ __forceinline__ void frame_grid_body(const FrameCtl* __restrict__ ctl
     [[maybe_unused]] const LevelCtx lc3 = level_ctx(g, kLv == 4 ? 11u - by : level), lc4 = level_ctx(g, kLv == 4 ? 4u + by : level);
     const void* table = g.table[KIND == GK_SINGLE ? bz : 0];
     float* enc0 = g.enc[KIND == GK_SINGLE ? bz : 0];
+    bool paired = false;
+    if constexpr (LANE_PAIRS) {
+        static_assert(kLv <= 2, "one or two levels per workgroup row");
+        // (block-uniform) the finest levels in the lane-pair form; below, a gather shares its lines between neighbouring lanes as it is and the pair form's extra instructions only cost
+        if (level >= PNR_LANE_PAIR_MIN_LEVEL) {
+            paired = true;
+            if constexpr (kPairs) {
+                const LevelCtx lcs[2] = {lc, lc2};
+                const uint32_t levels[2] = {level, by};
+                grid_pair_rows<KIND, 2>(g, lcs, levels, table, enc0, h.rowflag, bx * 256u + threadIdx.x, stride, rows);
+            } else {
+                const LevelCtx lcs[1] = {lc};
+                const uint32_t levels[1] = {level};
+                grid_pair_rows<KIND, 1>(g, lcs, levels, table, enc0, h.rowflag, bx * 256u + threadIdx.x, stride, rows);
+            }
+        }
+    }
+    if (!paired)
     for (uint32_t b = bx * 256u + threadIdx.x; b < rows; b += stride) {
         const float d0 = g.deltas[(size_t)b * 2];
         const uint32_t fl = h.rowflag ? h.rowflag[b] : 0u;
@@ -876,11 +1038,12 @@ __device__ __forceinline__ void frame_grid_body(const FrameCtl* __restrict__ ctl
 #ifndef PNR_GRID_WAVES_SINGLE
 #define PNR_GRID_WAVES_SINGLE 7   // the one-table kernel with its hosted tail: 72 registers (fewer spills in the tail) beat the eighth wave -- lego 3.80 -> 3.68 ms; the pair kernel is better off with eight (garden 13.3 against 13.6)
 #endif
-#define PNR_GRID_KERNEL(NAME, KIND, WAVES)                                                                                                   \
+#define PNR_GRID_KERNEL(NAME, KIND, WAVES, ...)                                                                                              \
     __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES))) NAME(const FrameCtl* __restrict__ ctl, GridArgs g, HostedArgs h) { \
-        frame_grid_body<KIND>(ctl, g, h);                                                                                                    \
+        frame_grid_body<KIND, ##__VA_ARGS__>(ctl, g, h);                                                                                     \
     }
 PNR_GRID_KERNEL(k_frame_grid, GK_SINGLE, PNR_GRID_WAVES_SINGLE)
+PNR_GRID_KERNEL(k_frame_grid_lp, GK_SINGLE, PNR_GRID_WAVES_SINGLE, true)   // the lane-pair form (grid_pair_level)
 PNR_GRID_KERNEL(k_frame_grid_pair, GK_PAIR, PNR_GRID_WAVES)
 PNR_GRID_KERNEL(k_frame_grid_triple, GK_TRIPLE, PNR_GRID_WAVES)
 PNR_GRID_KERNEL(k_frame_grid_h1, GK_HALF1, PNR_GRID_WAVES)
@@ -1204,11 +1367,11 @@ static FrameWorkspace carve(void* base, uint32_t N, uint32_t aux_stride = 0, boo
 // a second time, so the chunks it enqueues cannot run under another configuration than the chunks already in the stream.
 // FrameOpts: the pnr_set_option switches a frame's launches depend on, read once per frame with the rest.
 struct FrameOpts {
-    int aux_fusion, composite_fusion, hosted_tail, dynamic_tiles, march_budget, march_budget0, march_blocks, iteration_margin, block_skip, coop_march, palette_waves12;
+    int aux_fusion, composite_fusion, hosted_tail, dynamic_tiles, march_budget, march_budget0, march_blocks, iteration_margin, block_skip, coop_march, palette_waves12, grid_lane_pairs;
 };
 static FrameOpts frame_opts_now() {
     return FrameOpts{g_opt_aux_fusion, g_opt_composite_fusion, g_opt_hosted_tail, g_opt_dynamic_tiles, g_opt_march_budget, g_opt_march_budget0, g_opt_march_blocks,
-                     g_opt_iteration_margin, g_opt_block_skip, g_opt_coop_march, g_opt_palette_waves12};
+                     g_opt_iteration_margin, g_opt_block_skip, g_opt_coop_march, g_opt_palette_waves12, g_opt_grid_lane_pairs};
 }
 
 using UnsortKernel = decltype(&k_frame_unsort_outputs<4>);
@@ -1345,7 +1508,7 @@ static int make_frame_plan(const pnr_nerf_frame_args* a, const pnr_palette_frame
     else if (pal && p.with_clip && pal->embeddings_triple) { p.lookup = k_frame_grid_triple; ga.table[0] = pal->embeddings_triple; }
     else if (pal && !p.with_clip && pal->embeddings_pair) { p.lookup = k_frame_grid_pair; ga.table[0] = pal->embeddings_pair; p.lookup_y = PNR_FRAME_LEVEL_PAIRS_PAL ? 8 : 16; }
     else {
-        p.lookup = k_frame_grid; p.lookup_y = PNR_FRAME_LEVEL_PAIRS == 2 ? 4 : (PNR_FRAME_LEVEL_PAIRS ? 8 : 16); p.lookup_z = p.n_enc;
+        p.lookup = opt.grid_lane_pairs ? k_frame_grid_lp : k_frame_grid; p.lookup_y = PNR_FRAME_LEVEL_PAIRS == 2 ? 4 : (PNR_FRAME_LEVEL_PAIRS ? 8 : 16); p.lookup_z = p.n_enc;
         ga.table[0] = a->embeddings; ga.table[1] = pal ? pal->embeddings_palette : nullptr; ga.table[2] = p.with_clip ? pal->embeddings_clip : nullptr;
     }
 

@@ -1,6 +1,7 @@
 // grid_core.hpp -- hash-grid indexing / interpolation helpers shared by gridencoder.hip and frame.hip.
 #pragma once
 #include "pnr_common.hpp"
+#include "grid_xside.hpp"
 #include <math.h>
 
 namespace pnr {
@@ -39,19 +40,7 @@ __device__ __forceinline__ uint32_t grid_index(uint32_t gridtype, bool align_cor
 //   0 the reference's general form (stride test per dimension, hash or tiled, `%`); 1 dense: side^3 <= size, the index is below the size and the
 //   `%` is the identity; 2 hashed with a power-of-two size: a mask.  All three give grid_index's value (tests/test_gpu_ops.py: the D3C2 kernel and
 //   the frame loops against the generic kernel and the oracle, incl. sizes that are neither).  align_corners = false.
-#ifndef PNR_GRID_KIND
-#define PNR_GRID_KIND 1     // 0: every level through the general form (the A/B of the specialised index forms)
-#endif
-__device__ __forceinline__ uint32_t level_kind(uint32_t gridtype, uint32_t hashmap_size, uint32_t resolution) {
-    if (!PNR_GRID_KIND) return 0u;
-    const uint32_t side = resolution + 1u;
-    if ((uint64_t)side * side * side <= (uint64_t)hashmap_size) return 1u;
-    uint32_t stride = 1u;
-#pragma unroll
-    for (uint32_t d = 0; d < 3; d++)
-        if (stride <= hashmap_size) stride *= side;
-    return (gridtype == 0u && stride > hashmap_size && (hashmap_size & (hashmap_size - 1u)) == 0u) ? 2u : 0u;
-}
+// (level_kind itself: grid_xside.hpp, host + device)
 // the eight corner rows (x CMUL) of the cell whose lower corner is pg
 template <uint32_t CMUL>
 __device__ __forceinline__ void corner_rows_by_kind(uint32_t kind, uint32_t gridtype, uint32_t hashmap_size, uint32_t resolution, const uint32_t* pg /* [3] */,

@@ -114,6 +114,7 @@ __device__ __forceinline__ int wave_inclusive_scan(int v) {
 // Run-time switches for A/B measurements and tests (pnr_set_option; initialised from PNR_NO_BLOCK_SKIP / PNR_NO_AUX_FUSION).
 // Neither changes any result.
 extern int g_opt_block_skip;   // exact jumps over empty 4^3 / 8^3 / 16^3 blocks in the march
+extern int g_opt_grid_lane_pairs;   // frame loops: lane-pair form of the one-table level-major lookup (frame.hip: grid_pair_level)
 extern int g_opt_coop_march;   // frame loops: wave-cooperative march tail (frame.hip: march_coop_tail)
 extern int g_opt_hosted_tail;  // frame loops: rays a march launch has not finished within its probe budget are marched by the first workgroups of the lookup launch (frame.hip: hosted_march_tail)
 extern int g_opt_march_budget, g_opt_march_budget0;   // that budget in probe rounds: later launches / a frame's first launch (0 = the first launch keeps the in-wave cooperative tail)

@@ -556,6 +556,7 @@ int g_opt_composite_fusion = getenv("PNR_NO_COMPOSITE_FUSION") ? 0 : (getenv("PN
 int g_opt_iteration_margin = getenv("PNR_ITERATION_MARGIN") ? atoi(getenv("PNR_ITERATION_MARGIN")) : 0;   // measured 0 / 1 / 2 / 4 on the moving-camera bench: 4.239 / 4.247 / 4.277 / 4.265 ms -- a look costs less than a spare iteration
 int g_opt_palette_waves12 = getenv("PNR_PALETTE_WAVES8") ? 0 : 1;   // specialised PaletteNeRF field kernel: 12-wave workgroups (three waves per SIMD)
 int g_opt_dynamic_tiles = getenv("PNR_DYNAMIC_TILES") ? 1 : 0;   // measured: garden 14.6 -> 20.2 ms with it on (one contended counter, scattered tiles): off
+int g_opt_grid_lane_pairs = getenv("PNR_GRID_LANE_PAIRS") ? atoi(getenv("PNR_GRID_LANE_PAIRS")) != 0 : 1;   // frame loops, one fp32 table per lookup: the x pair of a cell's corners in adjacent lanes of every gather (frame.hip: grid_pair_level); same bits
 int g_opt_grid_fast = getenv("PNR_NO_GRID_FAST") ? 0 : 1;   // pnr_grid_encode_forward: the D = 3, C = 2 kernel (k_grid_fwd_d3c2) instead of the generic one (A/B; same bits)
 int g_opt_train_coop = getenv("PNR_NO_TRAIN_COOP") ? 0 : 1;   // training march: wave-cooperative counting pass (k_march_train_count_coop)
 int g_opt_mlp_f16x3 = getenv("PNR_MLP_FP32") ? 0 : 1;   // training MLP launches (mlp.hip): split-fp16 products on the fp16 matrix pipe (1) / exact fp32 MFMA (0)
@@ -584,6 +585,7 @@ int pnr_set_option(const char* name, int value) {
     if (!strcmp(name, "composite_fusion")) { g_opt_composite_fusion = value < 0 ? 0 : (value > 2 ? 2 : value); return PNR_OK; }
     if (!strcmp(name, "palette_waves12")) { g_opt_palette_waves12 = value != 0; return PNR_OK; }
     if (!strcmp(name, "dynamic_tiles")) { g_opt_dynamic_tiles = value != 0; return PNR_OK; }
+    if (!strcmp(name, "grid_lane_pairs")) { g_opt_grid_lane_pairs = value != 0; return PNR_OK; }
     if (!strcmp(name, "grid_fast")) { g_opt_grid_fast = value != 0; return PNR_OK; }
     if (!strcmp(name, "train_coop")) { g_opt_train_coop = value != 0; return PNR_OK; }
     if (!strcmp(name, "mlp_f16x3")) { g_opt_mlp_f16x3 = value != 0; return PNR_OK; }
