@@ -896,6 +896,17 @@ int pnr_background_train_forward(const pnr_background_train_args* args, pnr_stre
 uint64_t pnr_background_backward_workspace_bytes(uint32_t N);
 int pnr_background_backward(const pnr_background_train_args* args, pnr_stream_t stream);
 
+/* ---- launch geometry of the entries that cap their grid (host only; additive, ABI 10) ----
+ * These entries launch min(ceil(rows / rows_per_trip), cap) workgroups and let each walk tiles `for (t = blockIdx.x; t < ntiles; t += gridDim.x)`.
+ * pnr_launch_geometry reports, from the function the launcher itself forms its grid with, the workgroups the named entry launches for `rows`
+ * rows and the rows one workgroup handles per trip of its tile loop.  A workgroup takes a second trip iff rows > workgroups * rows_per_trip.
+ * Names: pnr_palette_heads_forward / _backward, pnr_palette_smooth_forward / _backward, pnr_palette_smooth_points,
+ * pnr_palette_train_shade_forward / _backward, pnr_nerf_field_forward, pnr_nerf_density_forward, pnr_mlp_forward, pnr_mlp_backward (the _lm
+ * forms launch as their plain twins).  `rows` is the entry's M or B, except for pnr_palette_smooth_points: there it counts what one lane handles
+ * per trip -- float4 groups, floor(3 M / 4), when xyzs, noise and xyzs_diff all start on a 16-byte boundary, else single elements, 3 M.
+ * PNR_ERR_INVALID for a name that has no capped grid, a null pointer, or more rows than the entry's own 32-bit count can express. */
+int pnr_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,7 @@ SIGNATURES = {
     "pnr_background_backward_workspace_bytes": [_u32],
     "pnr_background_backward": [_ptr, _ptr],
     "pnr_train_loss_backward_bg": [_ptr, _ptr, _ptr],
+    "pnr_launch_geometry": [ctypes.c_char_p, _u64, ctypes.POINTER(_u32), ctypes.POINTER(_u32)],
 }
 _RESTYPES = {"pnr_occupancy_workspace_bytes": _u64, "pnr_occupancy_samples": _u32, "pnr_adam_max_tensors": _u32, "pnr_error_string": ctypes.c_char_p, "pnr_scan_scratch_bytes": _u64, "pnr_nerf_field_packed_bytes": _u64, "pnr_occupancy_mip_bytes": _u64, "pnr_nerf_frame_workspace_bytes": _u64, "pnr_palette_field_packed_bytes": _u64, "pnr_palette_frame_workspace_bytes": _u64,
              "pnr_palette_aux_channels": _u32, "pnr_linear_wgrad_workspace_bytes": _u64, "pnr_grid_backward_binned_workspace_bytes": _u64,
@@ -282,3 +283,11 @@ def call(name, *args):
     rc = fn(*args)
     if rc:
         check(rc, name)
+
+
+def launch_geometry(entry, rows):
+    """(workgroups, rows_per_trip) of a capped-grid entry for `rows` rows (pnr_launch_geometry, host only): a workgroup takes a second trip through
+    its tile loop iff rows > workgroups * rows_per_trip."""
+    wg, rpt = _u32(0), _u32(0)
+    call("pnr_launch_geometry", entry.encode(), int(rows), ctypes.byref(wg), ctypes.byref(rpt))
+    return wg.value, rpt.value

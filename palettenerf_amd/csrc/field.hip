@@ -24,6 +24,7 @@
 // One wave = 32 samples; 192 MFMAs per wave-tile (18 688 useful + padding FLOP per sample).
 #include "pnr_common.hpp"
 #include "field_core.hpp"
+#include <string.h>
 
 namespace pnr {
 
@@ -133,6 +134,19 @@ __global__ void __launch_bounds__(kFieldThreads) k_nerf_density_fwd(const float*
     }
 }
 
+constexpr uint32_t kFieldRows = 256;   // samples of a workgroup tile (8 waves x 32)
+inline uint32_t field_blocks(uint32_t B) { const uint32_t ntiles = cdiv(B, kFieldRows); return ntiles < 512u ? ntiles : 512u; }        // 2 persistent workgroups per CU
+inline uint32_t density_blocks(uint32_t B) { const uint32_t ntiles = cdiv(B, kFieldRows); return ntiles < 1024u ? ntiles : 1024u; }
+
+int field_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip) {
+    const bool field = !strcmp(entry, "pnr_nerf_field_forward");
+    if (!field && strcmp(entry, "pnr_nerf_density_forward")) return PNR_ERR_INVALID;
+    if (rows > UINT32_MAX) return PNR_ERR_INVALID;
+    *workgroups = field ? field_blocks((uint32_t)rows) : density_blocks((uint32_t)rows);
+    *rows_per_trip = kFieldRows;
+    return PNR_OK;
+}
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -164,8 +178,7 @@ int pnr_nerf_field_forward(const float* enc, const float* dirs, const float* pac
     if (precision != PNR_FIELD_FP32 && precision != PNR_FIELD_F16X3 && precision != PNR_FIELD_F16X2) return PNR_ERR_UNSUPPORTED;
     if (B == 0) return PNR_OK;
     if (!enc || !dirs || !packed || !sigmas || !rgbs) return PNR_ERR_INVALID;
-    const uint32_t ntiles = cdiv(B, 256);
-    const uint32_t grid = ntiles < 512u ? ntiles : 512u;  // 2 persistent workgroups per CU
+    const uint32_t grid = field_blocks(B);
     if (precision == PNR_FIELD_FP32)
         hipLaunchKernelGGL(k_nerf_field_fwd<0>, dim3(grid), dim3(kFieldThreads), 0, as_stream(stream), enc, dirs, packed, B, sigmas, rgbs, enc_scale);
     else if (precision == PNR_FIELD_F16X2)
@@ -182,8 +195,7 @@ int pnr_nerf_density_forward(const float* enc, const float* packed, uint32_t B, 
     if (precision != PNR_FIELD_FP32 && precision != PNR_FIELD_F16X3) return PNR_ERR_UNSUPPORTED;
     if (B == 0) return PNR_OK;
     if (!enc || !packed || !sigmas) return PNR_ERR_INVALID;
-    const uint32_t ntiles = cdiv(B, 256);
-    const uint32_t grid = ntiles < 1024u ? ntiles : 1024u;
+    const uint32_t grid = density_blocks(B);
     if (precision == PNR_FIELD_FP32)
         hipLaunchKernelGGL(k_nerf_density_fwd<0>, dim3(grid), dim3(kFieldThreads), 0, as_stream(stream), enc, packed, B, scale, sigmas, geo_feat, enc_scale);
     else

@@ -15,6 +15,7 @@
 // products with per-tile power-of-two scaling on v_mfma_f32_32x32x16_f16 (k_mlp_fwd_h / k_mlp_bwd_h, further down); pnr_mlp_pack writes the weights in both.
 #include "field_core.hpp"
 #include <initializer_list>
+#include <string.h>
 
 namespace pnr {
 
@@ -1033,6 +1034,17 @@ static uint32_t mlp_blocks(uint32_t B) {
     const uint32_t t = cdiv(B, 32 * kMlpWaves);
     return t < kMlpMaxBlocks ? (t ? t : 1) : kMlpMaxBlocks;
 }
+// the forward: two workgroups per CU
+static uint32_t mlp_fwd_blocks(uint32_t B) { const uint32_t tiles = cdiv(B, 32 * kMlpWaves); return tiles < 2 * kMlpMaxBlocks ? tiles : 2 * kMlpMaxBlocks; }
+
+int mlp_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip) {
+    const bool fwd = !strcmp(entry, "pnr_mlp_forward");
+    if (!fwd && strcmp(entry, "pnr_mlp_backward")) return PNR_ERR_INVALID;
+    if (rows > UINT32_MAX) return PNR_ERR_INVALID;
+    *workgroups = fwd ? mlp_fwd_blocks((uint32_t)rows) : mlp_blocks((uint32_t)rows);
+    *rows_per_trip = 32 * kMlpWaves;
+    return PNR_OK;
+}
 
 }  // namespace pnr
 
@@ -1120,7 +1132,7 @@ static int mlp_forward_impl(const pnr_mlp_desc* desc, const float* packed, const
     if (lds > 160 * 1024) return PNR_ERR_UNSUPPORTED;
     if (!arrays_ok({x, x_tail, y}, B, p)) return PNR_ERR_ALIGNMENT;
     hipStream_t s = as_stream(stream);
-    const uint32_t tiles = cdiv(B, 32 * kMlpWaves), grid = tiles < 2 * kMlpMaxBlocks ? tiles : 2 * kMlpMaxBlocks;   // two workgroups per CU
+    const uint32_t grid = mlp_fwd_blocks(B);
     if (g_opt_mlp_f16x3) PNR_MLP_SWITCH(k_mlp_fwd_h, p, packed, x, x_tail, B, y);
     else PNR_MLP_SWITCH(k_mlp_fwd, p, packed, x, x_tail, B, y);
     return check_launch();

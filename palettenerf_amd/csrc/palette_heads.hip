@@ -8,6 +8,7 @@
 // dz = [d offsets_radiance | d omega_pre] which pnr_linear_wgrad / pnr_linear_bgrad reduce to the weight and bias gradients.
 // HBM-bound: forward (in + 4 nb + 1) * 4 B, backward (2 in + 2 (4 nb + 1)) * 4 B per sample (+ the dz re-read by the weight gradient).
 #include "pnr_common.hpp"
+#include <string.h>
 
 namespace pnr {
 
@@ -148,6 +149,17 @@ __global__ void __launch_bounds__(256) k_palette_heads_bwd(uint32_t M, uint32_t 
     }
 }
 
+constexpr uint32_t kHeadsRows = 256, kHeadsMaxBlocks = 2048;      // rows of a tile = lanes of a workgroup; the grid's cap (both kernels)
+inline uint32_t heads_blocks(uint32_t M) { const uint32_t want = cdiv(M, kHeadsRows); return want < kHeadsMaxBlocks ? want : kHeadsMaxBlocks; }
+
+int heads_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip) {
+    if (strcmp(entry, "pnr_palette_heads_forward") && strcmp(entry, "pnr_palette_heads_backward")) return PNR_ERR_INVALID;
+    if (rows > UINT32_MAX) return PNR_ERR_INVALID;
+    *workgroups = heads_blocks((uint32_t)rows);
+    *rows_per_trip = kHeadsRows;
+    return PNR_OK;
+}
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -159,8 +171,7 @@ int pnr_palette_heads_forward(const float* h, const float* w_offsets_radiance, c
     if (num_basis == 0 || num_basis > kHeadsMaxBasis || in_dim == 0 || in_dim > kHeadsIn) return PNR_ERR_UNSUPPORTED;
     if (M == 0) return PNR_OK;
     if (!h || !w_offsets_radiance || !b_offsets_radiance || !w_omega || !offsets_radiance || !omega) return PNR_ERR_INVALID;
-    const uint32_t blocks = cdiv(M, 256);
-    hipLaunchKernelGGL(k_palette_heads_fwd, dim3(blocks < 2048u ? blocks : 2048u), dim3(256), 0, as_stream(stream), M, num_basis, in_dim, h,
+    hipLaunchKernelGGL(k_palette_heads_fwd, dim3(heads_blocks(M)), dim3(256), 0, as_stream(stream), M, num_basis, in_dim, h,
                        w_offsets_radiance, b_offsets_radiance, w_omega, offsets_radiance, omega);
     return check_launch();
 }
@@ -171,8 +182,7 @@ int pnr_palette_heads_backward(const float* h, const float* w_offsets_radiance, 
     if (num_basis == 0 || num_basis > kHeadsMaxBasis || in_dim == 0 || in_dim > kHeadsIn) return PNR_ERR_UNSUPPORTED;
     if (M == 0) return PNR_OK;
     if (!h || !w_offsets_radiance || !w_omega || !grad_offsets_radiance || !grad_omega || !grad_pre) return PNR_ERR_INVALID;
-    const uint32_t blocks = cdiv(M, 256);
-    hipLaunchKernelGGL(k_palette_heads_bwd, dim3(blocks < 2048u ? blocks : 2048u), dim3(256), 0, as_stream(stream), M, num_basis, in_dim, h,
+    hipLaunchKernelGGL(k_palette_heads_bwd, dim3(heads_blocks(M)), dim3(256), 0, as_stream(stream), M, num_basis, in_dim, h,
                        w_offsets_radiance, w_omega, grad_offsets_radiance, grad_omega, grad_h, grad_pre);
     return check_launch();
 }

@@ -12,6 +12,7 @@
 // Backward: purely elementwise over the same spans, the row's 2 g w taken from LDS.  HBM-bound: (12 + 2 nb + 2 clip) * 4 B read and 8 B
 // written per sample forward, (2 + 2 nb + 2 clip) * 4 B read and (2 nb + 2 clip) * 4 B written backward.
 #include "pnr_common.hpp"
+#include <string.h>
 
 namespace pnr {
 
@@ -130,6 +131,22 @@ __global__ void __launch_bounds__(256) k_palette_smooth_bwd(uint32_t M, uint32_t
 
 inline uint32_t smooth_blocks(uint32_t M) { const uint32_t want = cdiv(M, kSmoothRows); return want < kSmoothMaxBlocks ? want : kSmoothMaxBlocks; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// k_palette_smooth_points: `items` = float4 groups when every array starts on a 16-byte boundary, single elements otherwise; one per lane and trip
+// (the up to three elements behind the groups are picked up by the grid stride)
+inline uint32_t smooth_points_blocks(uint64_t items) { const uint64_t want = (items + kSmoothRows - 1) / kSmoothRows; return (uint32_t)(want < kSmoothMaxBlocks ? want : kSmoothMaxBlocks); }
+
+int smooth_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip) {
+    if (!strcmp(entry, "pnr_palette_smooth_points")) {
+        if (rows > 3ull * UINT32_MAX) return PNR_ERR_INVALID;
+        *workgroups = smooth_points_blocks(rows);
+    } else if (!strcmp(entry, "pnr_palette_smooth_forward") || !strcmp(entry, "pnr_palette_smooth_backward")) {
+        if (rows > UINT32_MAX) return PNR_ERR_INVALID;
+        *workgroups = smooth_blocks((uint32_t)rows);
+    } else
+        return PNR_ERR_INVALID;
+    *rows_per_trip = kSmoothRows;
+    return PNR_OK;
+}
 
 }  // namespace pnr
 
@@ -141,8 +158,7 @@ int pnr_palette_smooth_points(const float* xyzs, const float* noise, float bound
     if (M == 0) return PNR_OK;
     if (!xyzs || !noise || !xyzs_diff) return PNR_ERR_INVALID;
     const uint64_t n = (uint64_t)M * 3, n4 = aligned16(xyzs) && aligned16(noise) && aligned16(xyzs_diff) ? n / 4 : 0;
-    const uint64_t want = ((n4 ? n4 : n) + 255) / 256;     // the up to three elements behind the groups are picked up by the grid stride
-    hipLaunchKernelGGL(k_palette_smooth_points, dim3((uint32_t)(want < kSmoothMaxBlocks ? want : kSmoothMaxBlocks)), dim3(256), 0, as_stream(stream), n4, n,
+    hipLaunchKernelGGL(k_palette_smooth_points, dim3(smooth_points_blocks(n4 ? n4 : n)), dim3(256), 0, as_stream(stream), n4, n,
                        xyzs, noise, bound, xyzs_diff);
     return check_launch();
 }

@@ -11,6 +11,7 @@
 // wave shuffle -> LDS -> one partial row per workgroup -> a second tiny launch sums the partials in a fixed order.
 // HBM-bound: (4 nb + 8 + clip) * 4 B read and (16 + clip + nb) * 4 B written per sample forward.
 #include "pnr_common.hpp"
+#include <string.h>
 
 namespace pnr {
 
@@ -193,6 +194,19 @@ __global__ void __launch_bounds__(1024) k_palette_train_shade_reduce(const float
     }
 }
 
+constexpr uint32_t kShadeRows = 256, kShadeFwdBlocks = 4096;      // rows of a tile = lanes of a workgroup; the forward's grid cap (the backward's is kShadeBlocks)
+inline uint32_t shade_fwd_blocks(uint32_t M) { const uint32_t want = cdiv(M, kShadeRows); return want < kShadeFwdBlocks ? want : kShadeFwdBlocks; }
+inline uint32_t shade_bwd_blocks(uint32_t M) { const uint32_t want = cdiv(M, kShadeRows); return want < kShadeBlocks ? want : kShadeBlocks; }
+
+int shade_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip) {
+    const bool fwd = !strcmp(entry, "pnr_palette_train_shade_forward");
+    if (!fwd && strcmp(entry, "pnr_palette_train_shade_backward")) return PNR_ERR_INVALID;
+    if (rows > UINT32_MAX) return PNR_ERR_INVALID;
+    *workgroups = fwd ? shade_fwd_blocks((uint32_t)rows) : shade_bwd_blocks((uint32_t)rows);
+    *rows_per_trip = kShadeRows;
+    return PNR_OK;
+}
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -207,8 +221,7 @@ int pnr_palette_train_shade_forward(uint32_t M, uint32_t num_basis, uint32_t cli
     if (num_basis == 0 || num_basis > kShadeMaxBasis) return PNR_ERR_UNSUPPORTED;
     if (M == 0) return PNR_OK;
     if (!omega || !offsets_radiance || !view_dep || !diffuse || !basis_color || !rgbs || !all_buffer) return PNR_ERR_INVALID;
-    const uint32_t blocks = cdiv(M, 256);
-    hipLaunchKernelGGL(k_palette_train_shade_fwd, dim3(blocks < 4096u ? blocks : 4096u), dim3(256), 0, as_stream(stream), M, num_basis, clip_dim,
+    hipLaunchKernelGGL(k_palette_train_shade_fwd, dim3(shade_fwd_blocks(M)), dim3(256), 0, as_stream(stream), M, num_basis, clip_dim,
                        omega, offsets_radiance, view_dep, diffuse, clip_feat, smooth_norm, basis_color, rgbs, all_buffer);
     return check_launch();
 }
@@ -228,7 +241,7 @@ int pnr_palette_train_shade_backward(uint32_t M, uint32_t num_basis, uint32_t cl
         !grad_diffuse)
         return PNR_ERR_INVALID;
     if (grad_basis_color && (!workspace || workspace_bytes < pnr_palette_train_shade_workspace_bytes(num_basis))) return PNR_ERR_INVALID;
-    const uint32_t want = cdiv(M, 256), blocks = want < kShadeBlocks ? want : kShadeBlocks;
+    const uint32_t blocks = shade_bwd_blocks(M);
     float* partial = grad_basis_color ? static_cast<float*>(workspace) : nullptr;
     hipLaunchKernelGGL(k_palette_train_shade_bwd, dim3(blocks), dim3(256), 0, s, M, num_basis, clip_dim, omega, offsets_radiance, view_dep, basis_color,
                        grad_rgbs, grad_all, grad_omega, grad_offsets_radiance, grad_view_dep, grad_diffuse, grad_clip_feat, grad_smooth_norm, partial);

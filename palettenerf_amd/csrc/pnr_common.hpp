@@ -20,6 +20,15 @@ inline int check_launch() {
 inline hipStream_t as_stream(pnr_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
+// pnr_launch_geometry (launch_geometry.hip): every translation unit whose entries launch a capped grid answers for them here, through the very
+// helper its launcher calls.  PNR_OK and both outputs written for one of the unit's entries, PNR_ERR_INVALID otherwise (not its name, or more
+// rows than the entry's 32-bit row count can express).
+int heads_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);    // palette_heads.hip
+int smooth_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);   // palette_smooth.hip
+int shade_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);    // palette_train.hip
+int field_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);    // field.hip
+int mlp_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);      // mlp.hip
+
 // One process may drive several GPUs: function attributes and events belong to a device, so one-time set-up is tracked per device id.
 constexpr int kMaxDevices = 64;
 inline int current_device() { int d = 0; if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) d = 0; return d; }

@@ -9,6 +9,7 @@ import torch
 
 import oracle
 from palettenerf_amd import gridencoder, palette_utils, raymarching, scene, shencoder
+from tests import float64_blocks as f64
 
 pytestmark = pytest.mark.gpu
 
@@ -1332,23 +1333,19 @@ def test_palette_heads_match_the_torch_formulas(cuda, nb, n_in, frozen_h):
     def leafs(dtype, device):
         return [t.to(device=device, dtype=dtype).requires_grad_(not (frozen_h and k == 0)) for k, t in enumerate((h, w_or, b_or, w_om))]
 
-    hh, a, b, c = leafs(torch.float64, "cpu")
-    offrad = F.linear(hh, a, b)
-    om = F.softplus(F.linear(hh, c)) + 0.05
-    om = om / om.sum(-1, keepdim=True)
-    ((offrad * w1.double()).sum() + (om * w2.double()).sum()).backward()
+    offrad, om, ref_grads, _ = f64.heads_block(h, w_or, b_or, w_om, w1, w2, torch.float64, "cpu", frozen_h)      # the reference arithmetic, float64 on the host
 
     h2, a2, b2, c2 = leafs(torch.float32, cuda)
     offrad2, om2 = palette_utils._palette_heads.apply(h2, a2, b2, c2)
-    np.testing.assert_allclose(offrad2.detach().cpu().numpy(), offrad.detach().numpy(), rtol=2e-6, atol=2e-5)
-    np.testing.assert_allclose(om2.detach().cpu().numpy(), om.detach().numpy(), rtol=2e-6, atol=2e-6)
+    np.testing.assert_allclose(offrad2.detach().cpu().numpy(), offrad.numpy(), rtol=2e-6, atol=2e-5)
+    np.testing.assert_allclose(om2.detach().cpu().numpy(), om.numpy(), rtol=2e-6, atol=2e-6)
     ((offrad2 * w1.to(cuda)).sum() + (om2 * w2.to(cuda)).sum()).backward()
-    for name, got, want in zip(("h", "w_offsets_radiance", "b_offsets_radiance", "w_omega"), (h2, a2, b2, c2), (hh, a, b, c)):
+    for name, got, want in zip(("h", "w_offsets_radiance", "b_offsets_radiance", "w_omega"), (h2, a2, b2, c2), ref_grads):
         if name == "h" and frozen_h:
             assert got.grad is None
             continue
-        scale = float(want.grad.abs().max()) + 1e-12
-        err = float((got.grad.cpu().double() - want.grad).abs().max())
+        scale = float(want.abs().max()) + 1e-12
+        err = float((got.grad.cpu().double() - want).abs().max())
         assert err <= 2e-5 * scale + 1e-7, (name, err, scale)
 
 
@@ -1409,28 +1406,15 @@ def test_palette_train_shade_matches_the_torch_formulas(cuda, nb, clip_dim, has_
         return [None if t is None else t.to(device=device, dtype=dtype).requires_grad_(True) for t in ts]
 
     # reference arithmetic, float64 on the host
-    o, r, vd, df, cf, sm, bc = leafs(torch.float64, "cpu")
-    off, rad = r[:, :-1].reshape(M, nb, 3), r[:, -1:].reshape(M, 1, 1)
-    bcc = bc[None].clamp(0, 1)
-    if frozen:
-        bcc = bcc.detach()
-    final = F.softplus(rad) * (bcc + off)
-    rgbs = (o[..., None] * final).sum(-2) + vd.detach()
-    sparsity = o.sum(-1, keepdim=True) / ((o ** 2).sum(-1, keepdim=True) + 1e-6) - 1
-    cols = [sparsity, (vd ** 2).sum(-1, keepdim=True), (off ** 2).sum(-1).sum(-1, keepdim=True), sm if sm is not None else torch.zeros(M, 1, dtype=torch.float64),
-            vd, df + vd, df, cf if cf is not None else torch.zeros(M, clip_dim, dtype=torch.float64), o]
-    all_ref = torch.cat(cols, -1)
-    ((rgbs * w_rgb.double()).sum() + (all_ref * w_all.double()).sum()).backward()
-    ref_grads = [None if t is None else t.grad for t in (o, r, vd, df, cf, sm, bc)]
+    rgbs, all_ref, ref_grads = f64.shade_block(omega, offrad, view_dep, diffuse, clip_feat, smooth, basis, w_rgb, w_all, clip_dim, torch.float64, "cpu", frozen)
 
     o2, r2, vd2, df2, cf2, sm2, bc2 = leafs(torch.float32, cuda)
     rg, ab = palette_utils.palette_train_shade(o2, r2, vd2, df2, cf2, sm2, bc2.detach() if frozen else bc2, clip_dim)
     assert ab.shape == (M, 13 + clip_dim + nb)
-    np.testing.assert_allclose(rg.detach().cpu().numpy(), rgbs.detach().numpy(), rtol=2e-6, atol=2e-6)
-    np.testing.assert_allclose(ab.detach().cpu().numpy(), all_ref.detach().numpy(), rtol=2e-6, atol=2e-6)
+    np.testing.assert_allclose(rg.detach().cpu().numpy(), rgbs.numpy(), rtol=2e-6, atol=2e-6)
+    np.testing.assert_allclose(ab.detach().cpu().numpy(), all_ref.numpy(), rtol=2e-6, atol=2e-6)
     ((rg * w_rgb.to(cuda)).sum() + (ab * w_all.to(cuda)).sum()).backward()
-    for name, got, want in zip(("omega", "offsets_radiance", "view_dep", "diffuse", "clip_feat", "smooth_norm", "basis_color"),
-                               (o2, r2, vd2, df2, cf2, sm2, bc2), ref_grads):
+    for name, got, want in zip(f64.SHADE_NAMES, (o2, r2, vd2, df2, cf2, sm2, bc2), ref_grads):
         if got is None:
             continue
         if name == "basis_color" and frozen:
@@ -1504,12 +1488,7 @@ def test_fused_mlp_forward_backward_match_float64(cuda, dims, act):
     # a hidden unit whose pre-activation is within rounding of 0 may sit on either side of the kink in fp32 and float64: such samples
     # (a handful in 5e4 x 128 units) get no output gradient, so that the derivative choice cannot matter
     with torch.no_grad():
-        hd, zmin = x.detach().double().cpu(), torch.full((B,), 1e9, dtype=torch.float64)
-        for i, l in enumerate(net[:-1]):
-            z = hd @ l.weight.detach().double().cpu().t()
-            zmin = torch.minimum(zmin, z.abs().min(dim=1).values)
-            hd = fact(z)
-        ambiguous = zmin < 2e-5     # (the split-fp16 products are good to ~2^-22 of the largest term of a sum: a few 1e-6 on a pre-activation of order 1)
+        ambiguous = f64.mlp_ambiguous(x, [l.weight for l in net], fact, "cpu", margin=2e-5)     # (the split-fp16 products are good to ~2^-22 of the largest term of a sum: a few 1e-6 on a pre-activation of order 1)
         assert int(ambiguous.sum()) < 2000
         wy[ambiguous.to(cuda)] = 0.0
     assert mlp.fusable(net, x, fact)
@@ -1518,20 +1497,10 @@ def test_fused_mlp_forward_backward_match_float64(cuda, dims, act):
     (y * wy).sum().backward()
     got = [x.grad.clone()] + [l.weight.grad.clone() for l in net]
     # float64 reference on the host
-    xd = x.detach().double().cpu().requires_grad_(True)
-    wd = [l.weight.detach().double().cpu().requires_grad_(True) for l in net]
-    h = xd
-    for i, w in enumerate(wd):
-        h = h @ w.t()
-        if i != len(wd) - 1:
-            h = fact(h)
-    if out is not None:
-        h = out(h)
-    (h * wy.double().cpu()).sum().backward()
-    want = [xd.grad] + [w.grad for w in wd]
+    h, want = f64.mlp_block(x, [l.weight for l in net], wy, fact, out, torch.float64, "cpu")
     scale = float(h.abs().max())
-    assert float((y.detach().double().cpu() - h.detach()).abs().max()) <= 2e-6 * scale
-    for name, a, b in zip(["dx"] + [f"dw{i}" for i in range(len(wd))], got, want):
+    assert float((y.detach().double().cpu() - h).abs().max()) <= 2e-6 * scale
+    for name, a, b in zip(["dx"] + [f"dw{i}" for i in range(len(want) - 1)], got, want):
         err, ref = float((a.double().cpu() - b).abs().max()), float(b.abs().max())
         assert err <= 2e-5 * ref, (name, err, ref)
     for l in net:

@@ -73,7 +73,15 @@ def case(M, nb, clip_name):
 
     ref64, ref32 = run(torch.float64), run(torch.float32)
     err32 = {k: float((ref32[k].double() - ref64[k]).abs().max()) for k in ref64}
-    return dict(inputs=inputs, g_norm=g_norm, bound=bound, sigma_clip=sigma_clip, same=same, ref=ref64, err32=err32)
+    return dict(inputs=inputs, g_norm=g_norm, bound=bound, sigma_clip=sigma_clip, same=same, ref=ref64, ref32=ref32, err32=err32)
+
+
+def rows_of(c, lo, hi):
+    """The case restricted to rows [lo, hi): its inputs, its float64 values and the fp32 torch block's largest error on those rows alone."""
+    cut = lambda v: None if v is None else v[lo:hi]      # noqa: E731
+    ref = {k: cut(v) for k, v in c["ref"].items()}
+    err32 = {k: float((cut(c["ref32"][k]).double() - ref[k]).abs().max()) for k in ref}
+    return dict(c, inputs={k: cut(v) for k, v in c["inputs"].items()}, g_norm=cut(c["g_norm"]), same=cut(c["same"]), ref=ref, ref32=None, err32=err32)
 
 
 def ulp32(v):
