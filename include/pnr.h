@@ -904,8 +904,69 @@ int pnr_background_backward(const pnr_background_train_args* args, pnr_stream_t 
  * pnr_palette_train_shade_forward / _backward, pnr_nerf_field_forward, pnr_nerf_density_forward, pnr_mlp_forward, pnr_mlp_backward (the _lm
  * forms launch as their plain twins).  `rows` is the entry's M or B, except for pnr_palette_smooth_points: there it counts what one lane handles
  * per trip -- float4 groups, floor(3 M / 4), when xyzs, noise and xyzs_diff all start on a 16-byte boundary, else single elements, 3 M.
+ * pnr_lattice_density (below) answers too: `rows` = the lattice points of one chunk, min(chunk, nx ny nz).
  * PNR_ERR_INVALID for a name that has no capped grid, a null pointer, or more rows than the entry's own 32-bit count can express. */
 int pnr_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);
+
+/* ---- mesh export: density lattice and marching cubes on the device (additive, ABI 10) ----
+ * What the reference's Trainer.save_mesh does on the host (nerf/utils.py:187-217, :633-653: extract_fields builds 128^3 blocks of points with
+ * linspace / meshgrid / cat and reads every block back, PyMCubes runs on the CPU over the volume) as device work: the lattice points, the
+ * density volume and the surface never leave the GPU; the host reads back two counts.
+ *
+ * Lattice (nerf/utils.py:187-217: torch.linspace per axis): coordinate i of n >= 2 on [min, max], step = (max - min) / (n - 1) in fp32,
+ *     i < n / 2:  min + step * i        otherwise:  max - step * (n - 1 - i)        (a product and a sum, each rounded: no contraction)
+ * -- the two-sided form torch.linspace documents; the last point is exactly max, so a lattice over the field's whole box never steps past
+ * `bound` (where the encoder would read zero).  Points are numbered in C order, z fastest: index = (x * ny + y) * nz + z.
+ *
+ * pnr_lattice_points   points first .. first + count of the lattice as [count, 3] fp32 (for a field evaluated by the caller).
+ *                      n[d] in 2 .. 512, first + count <= nx ny nz, null pointer: PNR_ERR_INVALID.  count = 0 is PNR_OK.
+ *                      The caller evaluates its field there (density()['sigma'], nerf/utils.py:642-648) and hands the volume to pnr_mesh_count.
+ * pnr_lattice_density  nerf/utils.py:187-217 with the query of :642-648 for the shipped field (16-level x 2 fp32 hash grid -> sigma_net 32 -> 64 -> 16,
+ *                      the field of pnr_occupancy_update): u[x, y, z] = exp(sigma_net(encoder(p))[0]) at every lattice point -- density()['sigma'], no
+ *                      density scale -- by the occupancy sweep's lookup kernel and its exact-fp32 matrix-core sigma_net, `chunk` points at a time
+ *                      through workspace = pnr_lattice_density_workspace_bytes(chunk) bytes (256-byte aligned; chunk >= 256, rounded up to a multiple
+ *                      of 256, at most 2^22 are used).  Another architecture is PNR_ERR_UNSUPPORTED; a null pointer, an n[d] outside 2 .. 512 or a
+ *                      workspace below 256 points PNR_ERR_INVALID -- before any launch. */
+int pnr_lattice_points(const float* box_min, const float* box_max, const uint32_t* n, uint64_t first, uint32_t count, float* points, pnr_stream_t stream);
+typedef struct pnr_lattice_density_args {
+    float box_min[3], box_max[3];
+    uint32_t n[3];
+    float bound;                       /* of the encoder: its inputs are (p + bound) / (2 bound) */
+    const float* embeddings;           /* fp32 hash table [rows, 2] */
+    const int32_t* offsets;
+    uint32_t num_levels;
+    float S;
+    uint32_t base_resolution, gridtype;
+    const float* packed_sigma_net;     /* a PNR_FIELD_FP32 blob of pnr_nerf_field_pack (its sigma_net part) */
+    void* workspace;
+    uint64_t workspace_bytes;
+    float* u;                          /* [nx, ny, nz] out */
+} pnr_lattice_density_args;
+uint64_t pnr_lattice_density_workspace_bytes(uint32_t chunk);
+int pnr_lattice_density(const pnr_lattice_density_args* args, pnr_stream_t stream);
+
+/* Marching cubes over a device volume u[nx, ny, nz] (replaces mcubes.marching_cubes, nerf/utils.py:211).  A lattice point is inside when
+ * u > threshold (strict; NaN is outside).  Case table: csrc/mc_tables.inc, generated by csrc/gen_mc_tables.py -- corner c = x + 2y + 4z,
+ * cube edge e = axis * 4 + (offsets of the other two axes, lower axis in bit 0), ambiguous faces cut off each inside corner on its own (the
+ * same way from both cells of a face: watertight for any field), triangles counter-clockwise seen from the low-density side.
+ *   vertices  one per lattice edge (p, axis) whose ends differ, shared by the cells around it, ascending by ((x ny + y) nz + z) * 3 + axis;
+ *             [nv, 3] fp32 in lattice-index coordinates: p, with p[axis] + t,  t = (threshold - u0) / (u1 - u0), 0.5 when that is not finite,
+ *             clamped to [0, 1]  (u0 = u[p], u1 = u[p + axis]).
+ *   triangles by cell in C order, then in table order; [nt, 3] int32 vertex indices.
+ * The order is part of the contract: the output is reproducible bit for bit.
+ *   pnr_mesh_case_triangles  host only: the triangles of a case (0 .. 5) and, when edges is not NULL, their 3 * n cube edges (255-padded);
+ *                            PNR_ERR_INVALID for case > 255.
+ *   pnr_mesh_count           classifies every lattice edge and cell, scans, leaves counts[0] = nv, counts[1] = nt (device int32[2]) and the
+ *                            per-point vertex ranks in the workspace (pnr_mesh_workspace_bytes(nx, ny, nz) bytes, 256-byte aligned).
+ *   pnr_mesh_emit            after pnr_mesh_count on the same u, threshold and workspace: writes the vertices and triangles; rows at or past
+ *                            cap_vertices / cap_triangles are not written (the caller sized the arrays from the counts).
+ * PNR_ERR_INVALID before any launch: a null pointer, an axis < 2 or > 512 (3 * 512^3 fits the 29-bit ranks), a short or misaligned workspace. */
+int pnr_mesh_case_triangles(uint32_t mc_case, uint8_t* edges /* [15] or NULL */);
+uint64_t pnr_mesh_workspace_bytes(uint32_t nx, uint32_t ny, uint32_t nz);
+int pnr_mesh_count(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, void* workspace, uint64_t workspace_bytes, int32_t* counts,
+                   pnr_stream_t stream);
+int pnr_mesh_emit(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, const void* workspace, uint64_t workspace_bytes,
+                  float* vertices, uint32_t cap_vertices, int32_t* triangles, uint32_t cap_triangles, pnr_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -119,8 +119,15 @@ SIGNATURES = {
     "pnr_background_backward": [_ptr, _ptr],
     "pnr_train_loss_backward_bg": [_ptr, _ptr, _ptr],
     "pnr_launch_geometry": [ctypes.c_char_p, _u64, ctypes.POINTER(_u32), ctypes.POINTER(_u32)],
+    "pnr_lattice_points": [_ptr, _ptr, _ptr, _u64, _u32, _ptr, _ptr],
+    "pnr_lattice_density_workspace_bytes": [_u32],
+    "pnr_lattice_density": [_ptr, _ptr],
+    "pnr_mesh_case_triangles": [_u32, _ptr],
+    "pnr_mesh_workspace_bytes": [_u32, _u32, _u32],
+    "pnr_mesh_count": [_ptr, _u32, _u32, _u32, _f32, _ptr, _u64, _ptr, _ptr],
+    "pnr_mesh_emit": [_ptr, _u32, _u32, _u32, _f32, _ptr, _u64, _ptr, _u32, _ptr, _u32, _ptr],
 }
-_RESTYPES = {"pnr_occupancy_workspace_bytes": _u64, "pnr_occupancy_samples": _u32, "pnr_adam_max_tensors": _u32, "pnr_error_string": ctypes.c_char_p, "pnr_scan_scratch_bytes": _u64, "pnr_nerf_field_packed_bytes": _u64, "pnr_occupancy_mip_bytes": _u64, "pnr_nerf_frame_workspace_bytes": _u64, "pnr_palette_field_packed_bytes": _u64, "pnr_palette_frame_workspace_bytes": _u64,
+_RESTYPES = {"pnr_mesh_workspace_bytes": _u64, "pnr_lattice_density_workspace_bytes": _u64, "pnr_occupancy_workspace_bytes": _u64, "pnr_occupancy_samples": _u32, "pnr_adam_max_tensors": _u32, "pnr_error_string": ctypes.c_char_p, "pnr_scan_scratch_bytes": _u64, "pnr_nerf_field_packed_bytes": _u64, "pnr_occupancy_mip_bytes": _u64, "pnr_nerf_frame_workspace_bytes": _u64, "pnr_palette_field_packed_bytes": _u64, "pnr_palette_frame_workspace_bytes": _u64,
              "pnr_palette_aux_channels": _u32, "pnr_linear_wgrad_workspace_bytes": _u64, "pnr_grid_backward_binned_workspace_bytes": _u64,
              "pnr_palette_train_shade_workspace_bytes": _u64, "pnr_train_loss_workspace_bytes": _u64, "pnr_mlp_packed_bytes": _u64, "pnr_mlp_backward_workspace_bytes": _u64,
              "pnr_background_packed_bytes": _u64, "pnr_background_backward_workspace_bytes": _u64}
@@ -157,6 +164,13 @@ class OccupancyArgs(ctypes.Structure):
                 ("decay", _f32), ("density_thresh", _f32), ("mode", _int), ("n_partial", _u32), ("noise", _ptr), ("coords", _ptr), ("occ_rand", _ptr),
                 ("embeddings", _ptr), ("offsets", _ptr), ("num_levels", _u32), ("S", _f32), ("base_resolution", _u32), ("gridtype", _u32),
                 ("packed_sigma_net", _ptr), ("workspace", _ptr), ("workspace_bytes", _u64), ("state", _ptr), ("points_out", _ptr)]
+
+
+class LatticeDensityArgs(ctypes.Structure):
+    """Mirror of `pnr_lattice_density_args` (include/pnr.h)."""
+    _fields_ = [("box_min", _f32 * 3), ("box_max", _f32 * 3), ("n", _u32 * 3), ("bound", _f32), ("embeddings", _ptr), ("offsets", _ptr),
+                ("num_levels", _u32), ("S", _f32), ("base_resolution", _u32), ("gridtype", _u32), ("packed_sigma_net", _ptr), ("workspace", _ptr),
+                ("workspace_bytes", _u64), ("u", _ptr)]
 
 
 class NerfFrameArgs(ctypes.Structure):

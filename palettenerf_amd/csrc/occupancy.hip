@@ -21,6 +21,8 @@
 #include "pnr_common.hpp"
 #include "grid_core.hpp"
 #include "field_core.hpp"
+#include "mesh_core.hpp"
+#include <string.h>
 
 extern "C" int pnr_build_occupancy_mip(const uint8_t* grid, uint32_t C, uint32_t H, float bound, void* mip, pnr_stream_t stream);
 
@@ -392,6 +394,41 @@ __global__ void __launch_bounds__(256) k_mark_untrained(OccGeom g, const float* 
     }
 }
 
+// ------------------------------------------------------------------------------------------ density lattice (mesh export)
+// pnr_lattice_density (nerf/utils.py:187-217, :642-648): the sample stage of the sweep on the points of a lattice instead of jittered cell points --
+// k_occ_lookup as it stands and nerf_density_tile<0>; only the points' origin and the destination differ.  Row w of a point = its lattice index.
+__global__ void __launch_bounds__(256) k_lat_points(LatticeGeom g, uint32_t first, uint32_t count, float4* __restrict__ pts) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    float p[3];
+    lattice_point(g, first + i, p);
+    pts[i] = make_float4(p[0], p[1], p[2], __int_as_float((int32_t)(first + i)));
+}
+// u = exp(logit): density()['sigma'] (nerf/network.py:137), no density scale
+__global__ void __launch_bounds__(512) k_lat_sigma(const float4* __restrict__ pts, uint32_t count, const float* __restrict__ enc, uint32_t level_stride,
+                                                   const float* __restrict__ packed, float* __restrict__ u) {
+    __shared__ float w[kC0];
+    for (int i = threadIdx.x * 4; i < kC0; i += 512 * 4) *reinterpret_cast<float4*>(&w[i]) = *reinterpret_cast<const float4*>(&packed[i]);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
+    const uint32_t ntiles = (count + 255) / 256;
+    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint32_t n = tile * 256 + wave * 32 + (lane & 31);
+        const bool valid = n < count;
+        const f32x16 g = nerf_density_tile<0>(w, lane, valid, enc, level_stride, valid ? n : 0u);
+        if (valid && h == 0) u[__float_as_int(pts[n].w)] = expf(g[0]);
+    }
+}
+constexpr uint32_t kLatRows = 256;     // points of a workgroup tile of k_lat_sigma (8 waves x 32)
+inline uint32_t lat_sigma_blocks(uint32_t count) { const uint32_t ntiles = cdiv(count, kLatRows); return ntiles < 1024u ? ntiles : 1024u; }
+
+int occupancy_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip) {
+    if (strcmp(entry, "pnr_lattice_density") || rows > UINT32_MAX) return PNR_ERR_INVALID;
+    *workgroups = lat_sigma_blocks((uint32_t)rows);
+    *rows_per_trip = kLatRows;
+    return PNR_OK;
+}
+
 static int launch_points(const pnr_occupancy_args* a, const OccGeom& g, const OccWorkspace& w, uint32_t first, uint32_t count, float* pts, hipStream_t s) {
     if (!a->noise || (g.mode == 1 && (!a->coords || !a->occ_rand))) return PNR_ERR_INVALID;
     hipLaunchKernelGGL(k_occ_points, dim3(cdiv(count, 256)), dim3(256), 0, s, g, first, count, a->noise, a->coords, a->occ_rand, w.occ_list, w.nnz,
@@ -490,6 +527,32 @@ int pnr_occupancy_update(const pnr_occupancy_args* a, pnr_stream_t stream) {
     rc = check_launch();
     if (rc != PNR_OK) return rc;
     return pnr_occupancy_commit(a, stream);
+}
+
+uint64_t pnr_lattice_density_workspace_bytes(uint32_t chunk) { return (uint64_t)((chunk + 255u) & ~255u) * kOccSampleBytes; }
+
+int pnr_lattice_density(const pnr_lattice_density_args* a, pnr_stream_t stream) {
+    LatticeGeom g;
+    if (!a || !make_lattice(a->box_min, a->box_max, a->n, &g)) return PNR_ERR_INVALID;
+    if (!a->embeddings || !a->offsets || !a->packed_sigma_net || !a->u || !a->workspace || (reinterpret_cast<uintptr_t>(a->workspace) & 255)) return PNR_ERR_INVALID;
+    if (a->num_levels != 16 || a->gridtype > 1 || !(a->bound > 0.0f)) return PNR_ERR_UNSUPPORTED;      // the fused sigma_net kernel is the shipped 16 x 2 -> 64 -> 16 stack
+    uint64_t chunk = (a->workspace_bytes / kOccSampleBytes) & ~(uint64_t)255;
+    if (chunk > (1u << 22)) chunk = 1u << 22;
+    if (chunk < 256) return PNR_ERR_INVALID;
+    float4* pts = static_cast<float4*>(a->workspace);
+    float* enc = reinterpret_cast<float*>(static_cast<unsigned char*>(a->workspace) + chunk * 16);
+    hipStream_t s = as_stream(stream);
+    const LevelParams lp = make_level_params(a->num_levels, a->S, a->base_resolution);
+    const uint32_t total = (uint32_t)lattice_total(g);
+    for (uint32_t first = 0; first < total; first += (uint32_t)chunk) {
+        const uint32_t count = total - first < chunk ? total - first : (uint32_t)chunk;
+        const uint32_t bx = cdiv(count, 256);
+        hipLaunchKernelGGL(k_lat_points, dim3(bx), dim3(256), 0, s, g, first, count, pts);
+        hipLaunchKernelGGL(k_occ_lookup, dim3(bx, a->num_levels), dim3(256), 0, s, pts, count, a->embeddings, a->offsets, lp, enc, (uint32_t)chunk, a->bound,
+                           2.0f * a->bound, exact_reciprocal_or_zero(2.0f * a->bound), a->gridtype);
+        hipLaunchKernelGGL(k_lat_sigma, dim3(lat_sigma_blocks(count)), dim3(512), 0, s, pts, count, enc, (uint32_t)chunk, a->packed_sigma_net, a->u);
+    }
+    return check_launch();
 }
 
 int pnr_mark_untrained_grid(const float* poses, uint32_t B, float fx, float fy, float cx, float cy, uint32_t C, uint32_t H, float bound, float min_near,
