@@ -1,5 +1,5 @@
 """Float64 statement of the multiresolution grid encoder for any D, C, gridtype and align_corners, with the error bounds the tests hold the oracle and
-the HIP kernels to.  TEST HELPER (imported by tests/test_oracle.py and tests/test_gpu_grid_variants.py); numpy only, no GPU.
+the HIP kernels to.  TEST HELPER (imported by tests/test_oracle.py, tests/test_gpu_grid_variants.py and tests/test_gpu_grid_binned.py); numpy only, no GPU.
 
 What is shared with the code under test are the kernels' INPUTS only: the per-level (scale, resolution) of oracle.grid_level_params and the fp32 cell
 position (one rounding of x * scale [+ 0.5], its floor, the fp32 fractional part).  Everything after that -- corner weights, sums, differences, scatter --
@@ -203,3 +203,179 @@ def variant_tables(D, C, case_index):
     rng = np.random.default_rng(5000 + 100 * D + 10 * C + case_index)
     rows = int(variant_cases(D)[case_index][1][-1])
     return (rng.random((rows, C)) - 0.5).astype(np.float32), rng.standard_normal((999, L * C)).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------ the binned table gradient's cases
+# csrc/grid_binned.hip (D = 3, C = 2, fp32 tables): the table in buckets of BIN_ROWS rows, gather jobs of at most BIN_CHUNK records, and per level one
+# of four treatments chosen by the host (binned_level_plan).  tests/test_gpu_grid_binned.py holds every one of them to table_grad_bound.
+#
+# No regime needs a bound of its own.  Per addend: D subtractions and D - 1 products for the weight, one product with the gradient = D + 3 roundings,
+# then the sum of the n addends of a row --
+#   records (COMBINE 0): the values are summed in fp64 (LDS), ONE rounding to fp32; a bucket split into j jobs adds j fp32 partials (the first onto an
+#     exact 0): 1 + (j - 1) roundings, and every partial that is not 0 holds at least one addend, so j <= n;
+#   merged records (COMBINE 1 / 2): a run of m addends is first summed by a segmented scan of depth ceil(log2 m) <= m - 1 in fp32, then as above;
+#   images: each of p <= min(n, workgroups) workgroup partials is rounded to fp32 once (u |partial|, in total <= u S), the reduce adds them in fp32 onto
+#     0: the partials that are 0 add exactly, p - 1 roundings remain -- p in all;
+# each of them at most n roundings of at most u S: (n + D + 3) u S holds for all.  An entry point that ADDS into a buffer holding p rounds once more:
+# u |p + gradient| (table_grad_accumulate_bound).
+BIN_ROWS, BIN_CHUNK = 8192, 131072
+BINNED_A = (8, 16, 1.5, 17)                                   # L, H, per_level_scale, log2_hashmap_size: scales 15 ... 272.4
+BINNED_B_SIZES = (8192, 8193, 16384, 16385, 24577, 70001)     # L = 6, H = 16, per_level_scale = 2; even total
+BINNED_CASES = ("A-hash", "A-hash-ac", "A-tiled", "A-tiled-ac", "B-hash", "B-tiled", "C")
+BINNED_LONG_RUNS = ((2048, 2064), (3010, 3023))               # lanes 0-15 and 2-14 of a row of 16; these samples stay alive on every level
+BINNED_RAYS = 4999                                            # 185 segments of 27 + 4 loose rows: ragged last workgroups at 1024 and 4096 samples each
+
+
+def binned_case(name):
+    """-> (L, H, per_level_scale, offsets, gridtype, align_corners)"""
+    gridtype = 1 if "tiled" in name else 0
+    if name[0] == "B":
+        return 6, 16, 2.0, np.concatenate([[0], np.cumsum(BINNED_B_SIZES)]).astype(np.int32), gridtype, False
+    L_, H_, pls, log2T = BINNED_A
+    ac = name.endswith("-ac")
+    return L_, H_, pls, oracle.grid_offsets(3, L_, pls, H_, log2T, align_corners=ac), gridtype, ac
+
+
+def binned_level_plan(L_, pls, H_, offsets, align_corners, coarse_image=True, cell_merge=True):
+    """The host's choice per level (pnr_grid_encode_backward_binned), recomputed: -> (sizes, buckets, kinds); kinds[l] is "image" (fp64 LDS images, no
+    records), 1 (records of runs of equal rows), 2 (records of runs of samples in one cell) or 0 (a record per sample and corner)."""
+    scale, res = oracle.grid_level_params(L_, pls, H_)
+    sizes = np.diff(np.asarray(offsets).astype(np.int64))
+    ni = jobs = 0
+    while coarse_image and ni < L_:
+        side = int(res[ni]) + (0 if align_corners else 1)
+        halves = -(-((side ** 3 + 7) // 8 * 8) // BIN_ROWS)
+        if halves > 2 or jobs + halves > 8:
+            break
+        jobs, ni = jobs + halves, ni + 1
+    nc = ni
+    while nc < L_ and scale[nc] <= 24.0:
+        nc += 1
+    nm = nc
+    while cell_merge and nm < L_ and scale[nm] <= 256.0:
+        nm += 1
+    return tuple(int(s) for s in sizes), tuple(int(-(-s // BIN_ROWS)) for s in sizes), ("image",) * ni + (1,) * (nc - ni) + (2,) * (nm - nc) + (0,) * (L_ - nm)
+
+
+def _frozen(a):
+    a.flags.writeable = False
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def _binned_rays():
+    """[4999, 3] float32, ray-ordered like variant_inputs' "rays" (runs of samples in one cell and of equal rows that start and end anywhere in a wave and
+    in a row of 16 lanes), with the same specials inside segments and one block of identical rows across the edge of a 1024-sample workgroup."""
+    rng = np.random.default_rng(4999)
+    start = rng.random((185, 1, 3)) * 0.9
+    step = (0.1 / 27) * (0.5 + 0.5 * rng.random((185, 1, 3)))
+    x = np.concatenate([(start + np.arange(27)[None, :, None] * step).reshape(4995, 3), rng.random((4, 3))]).astype(np.float32)
+    assert x.shape == (BINNED_RAYS, 3) and x.min() >= 0 and x.max() < 1
+    x[100] = 1.0e6                      # far outside, in the middle of segment 3
+    x[200, 2] = -0.25                   # one negative coordinate
+    x[300:310] = x[300]                 # ten identical rows
+    x[400] = 0.0
+    x[401] = 1.0
+    x[500, 0] = 1.0000001               # one ulp above 1: outside
+    x[600, 1] = -1e-7                   # just below 0: outside
+    x[1019:1029] = x[1019]              # ten identical rows across a workgroup's (and a wave's) edge
+    for lo, hi in BINNED_LONG_RUNS:     # identical rows that fill a row of 16 lanes / lie strictly inside one: the late steps of the segmented sums
+        x[lo:hi] = x[lo]
+    return _frozen(x)
+
+
+@functools.lru_cache(maxsize=None)
+def binned_inputs(name):
+    """[B, 3] float32, read-only.  A: the 4999 ray-ordered rows.  B: the same, plus for every level whose last bucket holds one row two points with a corner
+    on that row (found by search: a plain draw of 4999 touches such a row 0-2 times).  C: 40000 points uniform in a cube of 8 cells of level 2 from 0.40."""
+    if name == "C":
+        scale, _ = oracle.grid_level_params(BINNED_A[0], BINNED_A[2], BINNED_A[1])
+        return _frozen((0.40 + np.random.default_rng(2).random((40000, 3)) * (8.0 / float(scale[2]))).astype(np.float32))
+    if name[0] == "A":
+        return _binned_rays()
+    L_, H_, pls, offsets, gridtype, ac = binned_case(name)
+    rng = np.random.default_rng(70001 + gridtype)
+    want = {l: int(offsets[l + 1]) - 1 for l in range(L_) if int(offsets[l + 1] - offsets[l]) % BIN_ROWS == 1}
+    found = {l: [] for l in want}
+    for _ in range(40):
+        cand = rng.random((50000, 3)).astype(np.float32)
+        ref = GridReference(cand, offsets, pls, H_, gridtype, ac)
+        for l, row in want.items():
+            found[l] += list(cand[(ref.rows[l] == row).any(axis=0)][: 2 - len(found[l])])
+        if all(len(v) == 2 for v in found.values()):
+            break
+    assert all(len(v) == 2 for v in found.values()), "no point found on a one-row last bucket"
+    return _frozen(np.concatenate([_binned_rays()] + [np.stack(found[l]) for l in sorted(found)]).astype(np.float32))
+
+
+@functools.lru_cache(maxsize=None)
+def binned_grad(name):
+    """[B, L * 2] float32, read-only: the output gradient a training step hands the table gradient.  Standard normal, then on the ray-ordered rows every
+    seventh sample loses channel 0 only (it still contributes), ~5 % of the (sample, level) pairs are exactly zero, every segment is exactly zero on all
+    levels from a random sample on (what the composite's backward writes behind a ray's stopping sample), and a few entries are -0.0 -- alone (the sample
+    lives on) and as a pair (it is dead); the samples of BINNED_LONG_RUNS live on every level.  Rows appended to the rays (geometry B) and geometry C stay alive on every level."""
+    L_ = binned_case(name)[0]
+    B = binned_inputs(name).shape[0]
+    rng = np.random.default_rng(1234 + BINNED_CASES.index(name))
+    g = rng.standard_normal((B, L_, 2)).astype(np.float32)
+    g[::7, :, 0] = 0.0
+    if name != "C":
+        g[:BINNED_RAYS][rng.random((BINNED_RAYS, L_)) < 0.05] = 0.0
+        stop = rng.integers(1, 28, 185)                        # 27: the whole segment lives
+        seg = g[:4995].reshape(185, 27, L_, 2)
+        seg[np.arange(27)[None, :] >= stop[:, None]] = 0.0
+        for i in range(40, BINNED_RAYS, 97):
+            g[i, i % L_, 0] = -0.0                             # with channel 1 as it is
+        for i in range(55, BINNED_RAYS, 131):
+            g[i, i % L_] = -0.0                                # both channels: a dead sample
+        for lo, hi in BINNED_LONG_RUNS:
+            g[lo:hi] = rng.standard_normal((hi - lo, L_, 2)).astype(np.float32)
+    return _frozen(g.reshape(B, L_ * 2))
+
+
+@functools.lru_cache(maxsize=3)
+def binned_reference(name, rows=None):
+    """(GridReference, float64 table gradient, sum |w g|, addends per row) of a case, of its first `rows` samples if given; shared, not to be written"""
+    L_, H_, pls, offsets, gridtype, ac = binned_case(name)
+    x, g = binned_inputs(name), binned_grad(name)
+    if rows is not None:
+        x, g = x[:rows], g[:rows]
+    ref = GridReference(x, offsets, pls, H_, gridtype, ac)
+    return (ref,) + tuple(_frozen(a) for a in ref.table_grad(g))
+
+
+def table_grad_accumulate_bound(D, mag, n, want, before):
+    """The entry point added the gradient to `before` = p (fp32): one more rounding, of the sum: u |p + gradient|.  That is the whole statement for the
+    image reduce and for a gather job that owns its bucket (one add per element).  A bucket split into j jobs adds j times: the last add rounds
+    u |p + gradient| as before, each of the j - 1 earlier ones at most u (|p| + S) -- where table_grad_bound's derivation counted u S for it on a
+    buffer of zeros.  With |p| <= S those 2 (j - 1) u S fit into the n u S of the bound from n >= 2 j - 1 on, so a test keeps |p| <= S on the
+    rows that receive addends (and j <= 3 there)."""
+    return table_grad_bound(D, mag, n) + U32 * np.abs(np.asarray(before, np.float64) + want)
+
+
+def binned_live(ref, grad):
+    """[L, B] bool: the (level, sample) pairs that write records -- inside [0, 1]^3 and a gradient that is not exactly zero"""
+    g = np.asarray(grad).reshape(ref.B, ref.L, -1)
+    return ref.inr[None, :] & (g != 0).any(axis=2).T
+
+
+def binned_bucket_records(ref, grad, offsets, level):
+    """records per bucket of `level` before any merging: 8 per live sample, by the bucket of each corner's row"""
+    live = binned_live(ref, grad)[level]
+    local = ref.rows[level][:, live] - int(offsets[level])
+    return np.bincount((local // BIN_ROWS).reshape(-1), minlength=-(-int(offsets[level + 1] - offsets[level]) // BIN_ROWS))
+
+
+def deleted_sample_ratio(ref, grad, bound, level, sample):
+    """error / bound of a table gradient that lacks `sample`'s contribution on `level`: max over its eight rows of |w g| / bound (rows that two of its
+    corners share are summed)"""
+    g = np.asarray(grad, np.float64).reshape(ref.B, ref.L, -1)[sample, level]
+    w = ref._weights(level, np.arange(1 << ref.D))[:, sample]
+    rows = ref.rows[level, :, sample]
+    worst = 0.0
+    for r in np.unique(rows):
+        miss = np.abs(w[rows == r].sum() * g)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            q = np.where(miss == 0, 0.0, miss / bound[r])
+        worst = max(worst, float(q.max()))
+    return worst
