@@ -68,7 +68,13 @@ int pnr_abi_version(void);
  * (0 = every lane writes its own records); "mlp_f16x3" (default 1): the training MLP launches use split-fp16 products; "train_coop" (default 1): pnr_march_rays_train*'s counting pass
  * marches four rays per wave cooperatively (same counts, same rows); "coop_march" also governs the cooperative tail of pnr_march_rays*;
  * "grid_lane_pairs" (default 1): the frame loops' lookup of one fp32 table puts the two x neighbours of a cell's corners into adjacent lanes of every gather
- * of a workgroup row's finer level (0 = every lane loads its own eight corners); same encoder output, bit for bit */
+ * of a workgroup row's finer level (0 = every lane loads its own eight corners); same encoder output, bit for bit; "palette_waves12" (default 1): the
+ * 4-basis PaletteNeRF field without a clip head runs its wide kernels (0 = the 8-wave ones); "dynamic_tiles" (default 0): the frame loops' field kernels
+ * hand their wave tiles out through a device counter instead of a static schedule (measured slower); "grid_fast" (default 1): pnr_grid_encode_forward uses
+ * its D = 3, C = 2 kernel where it applies (0 = the generic one; same bits); "flex_coop" (default 1): pnr_composite_rays_flex with at most 8 samples per
+ * ray runs the workgroup-cooperative kernel (0 = one thread per ray; same bits); "grid_nt" (0..3, default 0): experiment, non-temporal stores (1) / input
+ * loads (2) in that D = 3, C = 2 kernel.  Values outside a switch's range are clamped (masked for "adam_variant" and "grid_nt"); an unknown name or NULL
+ * is PNR_ERR_INVALID.  The whole list, with each switch's range and environment variable, is palettenerf_amd/csrc/options.def. */
 int pnr_set_option(const char* name, int value);
 
 /* ---------------------------------------------------------------- raymarching: utils ------- */

@@ -39,14 +39,14 @@ def _deps_mtime():
     m = 0.0
     for root in (CSRC, os.path.join(HERE, "..", "include")):
         for f in os.listdir(root):
-            if f.endswith((".hip", ".hpp", ".h", ".inc")):
+            if f.endswith((".hip", ".hpp", ".h", ".inc", ".def")):
                 m = max(m, os.path.getmtime(os.path.join(root, f)))
     return m
 
 
 def _compile(src):
     obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
-    hdr_m = max(os.path.getmtime(os.path.join(CSRC, f)) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc")))
+    hdr_m = max(os.path.getmtime(os.path.join(CSRC, f)) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc", ".def")))
     hdr_m = max(hdr_m, os.path.getmtime(os.path.join(HERE, "..", "include", "pnr.h")))
     if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_m):
         return obj

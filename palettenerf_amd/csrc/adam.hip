@@ -54,7 +54,6 @@ __global__ void __launch_bounds__(kAdamThreads) k_adam(AdamTable tab, AdamScalar
 
 using namespace pnr;
 
-extern int g_opt_adam_variant;
 
 extern "C" {
 

@@ -27,12 +27,6 @@ uint64_t pnr_internal_edit_device_bytes();
 int pnr_internal_edit_upload(const pnr_palette_edit* edit, void* dst, hipStream_t s);
 int pnr_internal_palette_field_forward(const pnr_palette_field_args* a, pnr_stream_t stream, int waves12);
 
-#ifndef PNR_FRAME_LEVEL_PAIRS
-#define PNR_FRAME_LEVEL_PAIRS 1
-#endif
-#ifndef PNR_FRAME_LEVEL_PAIRS_PAL
-#define PNR_FRAME_LEVEL_PAIRS_PAL 0
-#endif
 namespace pnr {
 
 struct FrameCtl {  // 64 bytes, two copies ping-ponged by iteration parity
@@ -249,9 +243,6 @@ __device__ int g_march_timing_iter = 3;
 #define PNR_MARCH_WAVES 4     // waves per SIMD the march kernel WITH the in-wave cooperative tail is compiled for (register budget 512 / PNR_MARCH_WAVES): it needs 114 VGPRs;
                               // squeezed into 80 (6 waves, all chunks of a later iteration resident at once) it spills and the lego frame is 0.3 ms slower (4.38 vs 4.07 ms)
 #endif
-#ifndef PNR_MARCH2_JUMPS
-#define PNR_MARCH2_JUMPS true   // the budgeted march attempts the exact block jumps (false: plain cell steps only -- fewer registers; the rays that would have jumped end up in the queue)
-#endif
 #ifndef PNR_MARCH_WAVES_Q
 #define PNR_MARCH_WAVES_Q 5   // waves per SIMD of the budgeted march (MODE 2: no in-wave tail; 80 VGPRs spill 24 registers: 23 us per launch against 17.8 at 102)
 #endif
@@ -445,7 +436,7 @@ __global__ void __launch_bounds__(kRayBlock) __attribute__((amdgpu_waves_per_eu(
                 kinds[kind & 7]++;
                 if (!hit) empties++;
 #else
-                const bool hit = march_probe<MIP, POW2, (MODE != 2 || PNR_MARCH2_JUMPS)>(c, t, x, y, z, dt);
+                const bool hit = march_probe<MIP, POW2>(c, t, x, y, z, dt);   // (the budgeted march, MODE 2, attempts the exact block jumps too)
 #endif
                 if (hit) {
                     const size_t row = (size_t)n * n_step + step;
@@ -838,9 +829,6 @@ __device__ int g_hosted_timing_iter = 3;
 #ifndef PNR_HOSTED_MIN_GLOG
 #define PNR_HOSTED_MIN_GLOG 3u
 #endif
-#ifndef PNR_HOSTED_JUMPS
-#define PNR_HOSTED_JUMPS false
-#endif
 // The queue's consumer: rays_per_wave rays to a wave (8 when the queue is short -- the lookups that follow then spread over more waves --
 // up to 64), the march loop of k_frame_march from the recorded state, then the new rows' lookups, (row, level) pairs dealt to the lanes.
 template <int KIND>
@@ -905,7 +893,7 @@ __device__ __forceinline__ void hosted_march_tail(const FrameCtl* ctl, const Gri
 #ifdef PNR_HOSTED_TIMING
                 my_probes++;
 #endif
-                if (march_probe<true, true, PNR_HOSTED_JUMPS>(c, t, x, y, z, dt)) {
+                if (march_probe<true, true, false>(c, t, x, y, z, dt)) {   // (no block jumps: march_core.hpp, JUMPS)
                     const size_t row = (size_t)row0 + step;
                     float* px = h.xyzs + row * 3;
                     float* pd = h.dirs + row * 3;
@@ -969,18 +957,15 @@ __device__ __forceinline__ void hosted_march_tail(const FrameCtl* ctl, const Gri
 template <int KIND, bool LANE_PAIRS = false>
 __device__ __forceinline__ void frame_grid_body(const FrameCtl* __restrict__ ctl, const GridArgs& g, const HostedArgs& h) {
     if (ctl->done) return;
-    // GK_SINGLE with PNR_FRAME_LEVEL_PAIRS: a workgroup takes two levels, the y-th finest and the y-th coarsest, for each of its rows (8 instead of 16
+    // GK_SINGLE: a workgroup takes two levels, the y-th finest and the y-th coarsest, for each of its rows (8 instead of 16
     // workgroup rows per table): the row's position is read once, a scattered and a dense level share a thread
-    constexpr uint32_t kLv = KIND == GK_SINGLE ? (PNR_FRAME_LEVEL_PAIRS == 2 ? 4u : (PNR_FRAME_LEVEL_PAIRS ? 2u : 1u))
-                                               : ((KIND == GK_PAIR && PNR_FRAME_LEVEL_PAIRS_PAL) ? 2u : 1u);   // levels per workgroup row
+    constexpr uint32_t kLv = KIND == GK_SINGLE ? 2u : 1u;   // levels per workgroup row
     constexpr bool kPairs = kLv > 1;
     constexpr uint32_t kNY = 16u / kLv;
     uint32_t bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z, nbx = gridDim.x;
     if (h.blocks) {   // launch-uniform: a one-dimensional launch, the hosted workgroups first
         if (bx < h.blocks) {
-#ifndef PNR_NO_HOSTED_CODE
             hosted_march_tail<KIND>(ctl, g, h);
-#endif
             return;
         }
         const uint32_t id = bx - h.blocks, yz = id / h.gx;
@@ -998,12 +983,10 @@ __device__ __forceinline__ void frame_grid_body(const FrameCtl* __restrict__ ctl
 #endif
     const LevelCtx lc = level_ctx(g, level);
     [[maybe_unused]] const LevelCtx lc2 = level_ctx(g, kPairs ? by : level);
-    [[maybe_unused]] const LevelCtx lc3 = level_ctx(g, kLv == 4 ? 11u - by : level), lc4 = level_ctx(g, kLv == 4 ? 4u + by : level);
     const void* table = g.table[KIND == GK_SINGLE ? bz : 0];
     float* enc0 = g.enc[KIND == GK_SINGLE ? bz : 0];
     bool paired = false;
     if constexpr (LANE_PAIRS) {
-        static_assert(kLv <= 2, "one or two levels per workgroup row");
         // (block-uniform) the finest levels in the lane-pair form; below, a gather shares its lines between neighbouring lanes as it is and the pair form's extra instructions only cost
         if (level >= PNR_LANE_PAIR_MIN_LEVEL) {
             paired = true;
@@ -1024,7 +1007,6 @@ __device__ __forceinline__ void frame_grid_body(const FrameCtl* __restrict__ ctl
         const uint32_t fl = h.rowflag ? h.rowflag[b] : 0u;
         if (d0 == 0.0f || fl) continue;
         grid_row<KIND>(g, lc, level, table, enc0, b);
-        if constexpr (kLv == 4) { grid_row<KIND>(g, lc3, 11u - by, table, enc0, b); grid_row<KIND>(g, lc4, 4u + by, table, enc0, b); }
         if constexpr (kPairs) grid_row<KIND>(g, lc2, by, table, enc0, b);
     }
 #ifdef PNR_HOSTED_TIMING
@@ -1366,12 +1348,18 @@ static FrameWorkspace carve(void* base, uint32_t N, uint32_t aux_stride = 0, boo
 // keeps plan and progress in the host thread's per-device record; _finish checks that it is given that frame and waits on the KEPT plan -- it derives nothing
 // a second time, so the chunks it enqueues cannot run under another configuration than the chunks already in the stream.
 // FrameOpts: the pnr_set_option switches a frame's launches depend on, read once per frame with the rest.
+// (the PNR_FRAME_OPTION lines of options.def: the list include/pnr.h gives at pnr_nerf_render_frame_submit)
 struct FrameOpts {
-    int aux_fusion, composite_fusion, hosted_tail, dynamic_tiles, march_budget, march_budget0, march_blocks, iteration_margin, block_skip, coop_march, palette_waves12, grid_lane_pairs;
+#define PNR_OPTION(name, def, set, env, what)
+#define PNR_FRAME_OPTION(name, def, set, env, what) int name;
+#include "options.def"
 };
 static FrameOpts frame_opts_now() {
-    return FrameOpts{g_opt_aux_fusion, g_opt_composite_fusion, g_opt_hosted_tail, g_opt_dynamic_tiles, g_opt_march_budget, g_opt_march_budget0, g_opt_march_blocks,
-                     g_opt_iteration_margin, g_opt_block_skip, g_opt_coop_march, g_opt_palette_waves12, g_opt_grid_lane_pairs};
+    FrameOpts o;
+#define PNR_OPTION(name, def, set, env, what)
+#define PNR_FRAME_OPTION(name, def, set, env, what) o.name = g_opt_##name;
+#include "options.def"
+    return o;
 }
 
 using UnsortKernel = decltype(&k_frame_unsort_outputs<4>);
@@ -1506,9 +1494,9 @@ static int make_frame_plan(const pnr_nerf_frame_args* a, const pnr_palette_frame
     else if (p.half_tables && pal) { p.lookup = k_frame_grid_h2; ga.table[0] = pal->embeddings_pair; }
     else if (p.half_tables) { p.lookup = k_frame_grid_h1; ga.table[0] = a->embeddings; }
     else if (pal && p.with_clip && pal->embeddings_triple) { p.lookup = k_frame_grid_triple; ga.table[0] = pal->embeddings_triple; }
-    else if (pal && !p.with_clip && pal->embeddings_pair) { p.lookup = k_frame_grid_pair; ga.table[0] = pal->embeddings_pair; p.lookup_y = PNR_FRAME_LEVEL_PAIRS_PAL ? 8 : 16; }
+    else if (pal && !p.with_clip && pal->embeddings_pair) { p.lookup = k_frame_grid_pair; ga.table[0] = pal->embeddings_pair; p.lookup_y = 16; }
     else {
-        p.lookup = opt.grid_lane_pairs ? k_frame_grid_lp : k_frame_grid; p.lookup_y = PNR_FRAME_LEVEL_PAIRS == 2 ? 4 : (PNR_FRAME_LEVEL_PAIRS ? 8 : 16); p.lookup_z = p.n_enc;
+        p.lookup = opt.grid_lane_pairs ? k_frame_grid_lp : k_frame_grid; p.lookup_y = 8; p.lookup_z = p.n_enc;
         ga.table[0] = a->embeddings; ga.table[1] = pal ? pal->embeddings_palette : nullptr; ga.table[2] = p.with_clip ? pal->embeddings_clip : nullptr;
     }
 

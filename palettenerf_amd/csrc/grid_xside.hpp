@@ -19,11 +19,7 @@
 namespace pnr {
 
 // how a row index is formed on one level (grid_core.hpp describes the three forms)
-#ifndef PNR_GRID_KIND
-#define PNR_GRID_KIND 1     // 0: every level through the general form (the A/B of the specialised index forms)
-#endif
 PNR_HD uint32_t level_kind(uint32_t gridtype, uint32_t hashmap_size, uint32_t resolution) {
-    if (!PNR_GRID_KIND) return 0u;
     const uint32_t side = resolution + 1u;
     if ((uint64_t)side * side * side <= (uint64_t)hashmap_size) return 1u;
     uint32_t stride = 1u;

@@ -236,9 +236,6 @@ __device__ __forceinline__ int empty_block_log2(const RayCtx& c, uint32_t index)
 // one-cell step.
 // JUMPS = false compiles the block jumps out: every empty probe is the reference's own one-cell step (same results, since a jump is an
 // exact shortcut; fewer registers and a shorter chain for the hosted march tail, whose rays walk partly filled bricks where jumps rarely apply).
-#ifndef PNR_MARCH_NOJUMP_MEMO
-#define PNR_MARCH_NOJUMP_MEMO 1
-#endif
 template <bool MIP, bool POW2, bool JUMPS = true>
 __device__ __forceinline__ bool march_probe(const RayCtx& c, float& t, float& x, float& y, float& z, float& dt, int* kind = nullptr) {
     const float t0 = t;
@@ -272,9 +269,9 @@ __device__ __forceinline__ bool march_probe(const RayCtx& c, float& t, float& x,
     if constexpr (MIP && POW2 && JUMPS) {
         int sh = c.block_skip ? empty_block_log2(c, index) : 0;
         if (kind) *kind = sh == 0 ? 1 : 5;   // instrumented builds only: 0 emit, 1 cell step in a non-empty brick, 2/3/4 block jump, 5 block checks failed
-        [[maybe_unused]] const uint32_t jump_key = ((index >> (3 * sh)) << 3) | (uint32_t)sh;     // (level, aligned block of 2^sh cells a side in Morton order, sh)
+        const uint32_t jump_key = ((index >> (3 * sh)) << 3) | (uint32_t)sh;     // (level, aligned block of 2^sh cells a side in Morton order, sh)
         if (sh == 0) { if (cell_occupied<MIP>(c, index)) { if (kind) *kind = 0; return true; } }
-        else if (PNR_MARCH_NOJUMP_MEMO && jump_key == c.nojump_key) { if (kind) *kind = 7; }
+        else if (jump_key == c.nojump_key) { if (kind) *kind = 7; }
         else {
             const float s = (float)(1 << sh);
             const float lox = (float)((nx >> sh) << sh), loy = (float)((ny >> sh) << sh), loz = (float)((nz >> sh) << sh);
@@ -319,7 +316,7 @@ __device__ __forceinline__ bool march_probe(const RayCtx& c, float& t, float& x,
                     lattice_advance(t0, d, b, q, prev);
                     if (q - b > 2.0f * eps && b - prev > 2.0f * eps) { t = q; if (kind) *kind = 2; return false; }
                 }
-                if (PNR_MARCH_NOJUMP_MEMO) c.nojump_key = jump_key;     // the windows are taken (or the exit is a cell away): the same from the next cell of this block
+                c.nojump_key = jump_key;     // the windows are taken (or the exit is a cell away): the same from the next cell of this block
             }
         }
     } else {

@@ -198,16 +198,10 @@ struct EditParams {
 };
 
 constexpr int kPalThreads = 512;
-// Wide kernels: a request a tile used to wait for where it needed it is issued at the top of the tile --
-//   PNR_PAL_EARLY_RAY  a ray leader's slot -> ray id (and then its weights_sum) for the compositing step.
+// Wide kernels: a request a tile used to wait for where it needed it is issued at the top of the tile -- a ray leader's slot -> ray id (and then its
+// weights_sum) for the compositing step: garden 13.2 -> 13.0 ms (162 registers, no scratch).
 // (Round 4 also tried the second table's rows through global_load_lds into the then-idle staging slab, PNR_PAL_EARLY_PAL: slower, EXPERIMENTS.md; the slab
 // is gone since round 5 and that code with it.)
-#ifndef PNR_PAL_WAVE_MAJOR
-#define PNR_PAL_WAVE_MAJOR 1    // wave tiles dealt wave-major (see the tile loop); 0 = workgroup-major, for the A/B
-#endif
-#ifndef PNR_PAL_EARLY_RAY
-#define PNR_PAL_EARLY_RAY 1     // garden 13.2 -> 13.0 ms (162 registers, no scratch)
-#endif
 // Round 5.  What the parts of this kernel cost alone (profiles/r05_pal_parts.txt, stand-alone op, 1.09 M rows, timing-only PNR_PAL_FAKE builds): the matrix
 // phase 171 us of 213, everything behind it (scalar epilogue, staging, stores) ~40 us; and what they need: the matrix phase 118 registers, the old tail 157
 // plus a 4.6 KB staging slab per wave -- the tail, not the layers, held the kernel at three waves per SIMD.  The specialised 4-basis kernels ("wide":
@@ -216,23 +210,16 @@ constexpr int kPalThreads = 512;
 //     aux_map read-modify-write, nine 16-byte loads in flight at once; with 2 .. 8 samples per ray the ray's leader lane pulls the following lanes'
 //     rows through ds_bpermute and runs the same fmaf chain in the same order (bit-identical to the staged form either way);
 //   * the ray state (rays_t, depth, image) is requested when the matrix phase ends and used behind the scalar epilogue;
-//   * PNR_PAL_EARLY_ENC: the tile's encoder rows and directions are requested BEFORE the slot's `delta` has decided whether the row is alive (one trip
+//   * the tile's encoder rows and directions are requested BEFORE the slot's `delta` has decided whether the row is alive (one trip
 //     to memory instead of two dependent ones; a dead lane's loads are wasted), and the delta pair stays in two registers for the epilogue's alpha and
 //     the ray-state step (it was loaded three times).
 // LDS: the weights + 384 bytes per wave, so 16 waves (four per SIMD) fit where 12 slabs did not leave room for a thirteenth.
-#ifndef PNR_PAL_EARLY_ENC
-#define PNR_PAL_EARLY_ENC 1
-#endif
 #ifndef PNR_PAL_FAKE
 #define PNR_PAL_FAKE 0          // timing-only builds (WRONG results): 1 = no matrix phase (the loads stay), 2 = nothing behind the matrix phase (no epilogue, composite, stores), 4 = nothing behind it on every second tile
 #endif
 #ifndef PNR_PAL_WIDE_WAVES
 #define PNR_PAL_WIDE_WAVES 16   // waves per workgroup of the specialised 4-basis kernels ("wide": no clip head, rows of 36 floats, slabs in LDS).  Experiment builds: 8
 #endif
-#ifndef PNR_PAL_EARLY_ENC
-#define PNR_PAL_EARLY_ENC 1
-#endif
-
 
 // ctl == nullptr: rows = B (stand-alone op).  Otherwise rows = n_alive * n_step of the frame control block and
 // dead slots (delta == 0) are skipped.
@@ -262,13 +249,8 @@ struct PalArgs {
     uint32_t* tile_counter; RayState rs;
 };
 typedef const __attribute__((address_space(4))) PalArgs* PalArgsK;
-#ifndef PNR_PAL_KARGS
-#define PNR_PAL_KARGS 1     // 0: the loads are visible to the compiler again, which hoists them to the kernel's entry (the A/B of this change)
-#endif
 __device__ __forceinline__ PalArgsK launder(PalArgsK p) {
-#if PNR_PAL_KARGS
     asm volatile("" : "+s"(p));
-#endif
     return p;
 }
 
@@ -350,9 +332,8 @@ __global__ void __launch_bounds__(WAVES * 64) k_palette_field_fwd(PalArgs A_) {
             // wave-major: round `it` deals wave tile (it * WAVES + wave) * grid + b to wave `wave` of workgroup b, so the LAST, partial round of a
             // launch is spread one tile per workgroup (and, past `grid` tiles, one per SIMD: wave w sits on SIMD w % 4) instead of filling all
             // WAVES waves of its first few workgroups -- garden: 11.09 rounds cost 11 + 1/3 tile times instead of 12; an eighth of a frame:
-            // 1.4 rounds cost 1 + 2/3 instead of 2.  (Workgroup-major, rounds 1-3: (b + it * grid) * WAVES + wave.)
-            if constexpr (PNR_PAL_WAVE_MAJOR != 0) wt = (it * WAVES + (uint32_t)wave) * gridDim.x + blockIdx.x;
-            else wt = (blockIdx.x + it * gridDim.x) * WAVES + wave;
+            // 1.4 rounds cost 1 + 2/3 instead of 2.
+            wt = (it * WAVES + (uint32_t)wave) * gridDim.x + blockIdx.x;
         }
         if (wt >= nwt) break;
         // (the lane number goes through an opaque move once per tile: what is derived from it below -- row numbers, leader flags, LDS addresses, bit masks -- is
@@ -366,7 +347,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_palette_field_fwd(PalArgs A_) {
         // the slot's (delta_0, delta_1): delta_0 == 0 marks a dead slot; kept for the epilogue's alpha and the ray-state step's t advance
         f32x2 dl = {1.0f, 0.0f};
         if (deltas && mine) dl = *reinterpret_cast<const f32x2*>(deltas + (size_t)n * 2);
-        constexpr bool kEarlyEnc = PNR_PAL_EARLY_ENC != 0 && WAVES == PNR_PAL_WIDE_WAVES;
+        constexpr bool kEarlyEnc = WAVES == PNR_PAL_WIDE_WAVES;
         float xs[2][8], xp[2][8];
         float dx = 0.0f, dy = 0.0f, dz = 0.0f;
         if constexpr (kEarlyEnc) {   // requested before `dl` has arrived: rows of dead lanes are read too and replaced by zeros below
@@ -409,7 +390,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_palette_field_fwd(PalArgs A_) {
             if (valid) { dx = dirs[(size_t)row * 3]; dy = dirs[(size_t)row * 3 + 1]; dz = dirs[(size_t)row * 3 + 2]; }
         }
         // the compositing step's first dependent load (slot -> ray id), requested now; its second (the ray's weights_sum) once sigma_net is done
-        const bool early_ray = PNR_PAL_EARLY_RAY && WAVES == PNR_PAL_WIDE_WAVES && fuse_composite;
+        const bool early_ray = WAVES == PNR_PAL_WIDE_WAVES && fuse_composite;
         const uint32_t slot_t = wt * rays_pt + lane_q;      // the alive-list slot of this lane's ray
         const bool lead_lane = early_ray && (uint32_t)lane < rpw && lane_k_in_ray == 0 && slot_t < n_alive_k;
         int early_index = 0;

@@ -121,24 +121,5 @@ __device__ __forceinline__ int wave_inclusive_scan(int v) {
 
 }  // namespace pnr
 
-// Run-time switches for A/B measurements and tests (pnr_set_option; initialised from PNR_NO_BLOCK_SKIP / PNR_NO_AUX_FUSION).
-// Neither changes any result.
-extern int g_opt_block_skip;   // exact jumps over empty 4^3 / 8^3 / 16^3 blocks in the march
-extern int g_opt_grid_lane_pairs;   // frame loops: lane-pair form of the one-table level-major lookup (frame.hip: grid_pair_level)
-extern int g_opt_coop_march;   // frame loops: wave-cooperative march tail (frame.hip: march_coop_tail)
-extern int g_opt_hosted_tail;  // frame loops: rays a march launch has not finished within its probe budget are marched by the first workgroups of the lookup launch (frame.hip: hosted_march_tail)
-extern int g_opt_march_budget, g_opt_march_budget0;   // that budget in probe rounds: later launches / a frame's first launch (0 = the first launch keeps the in-wave cooperative tail)
-extern int g_opt_march_blocks;   // frame loops: workgroup cap of a budgeted march launch
-extern int g_opt_aux_fusion;   // PaletteNeRF frame loop: aux composite inside the field kernel
-extern int g_opt_composite_fusion;   // NeRF frame loop: 1 = n_step == 1 iterations composited inside the field kernel, 2 = every iteration (no composite launch)
-extern int g_opt_palette_waves12;    // PaletteNeRF field: the wide (PNR_PAL_WIDE_WAVES-wave) kernels for the shipped 4-basis shape (palette_field.hip)
-extern int g_opt_dynamic_tiles;      // frame loops: field kernels hand wave tiles out through a device counter instead of a static schedule
-extern int g_opt_grid_fast;          // stand-alone lookup op: k_grid_fwd_d3c2 for D = 3, C = 2 (gridencoder.hip)
-extern int g_opt_train_coop;  // training march: cooperative counting pass
-extern int g_opt_mlp_f16x3;  // training MLPs: split-fp16 matrix products (default) or exact fp32
-extern int g_opt_coarse_image;  // binned table gradient: LDS images for the coarsest levels
-extern int g_opt_scatter_staged;  // binned table gradient: LDS-ordered, coalesced record writes
-extern int g_opt_cell_merge;  // binned table gradient: cell-run merging on mid levels
-extern int g_opt_grid_nt;
-extern int g_opt_flex_coop;   // drop-in composite_rays_flex: workgroup-cooperative kernel (composite.hip)
-extern int g_opt_iteration_margin;   // frame loops: spare iterations enqueued beyond the previous frame's count before the first host look
+// Run-time switches for A/B measurements and tests (pnr_set_option): `extern int g_opt_<name>` for every line of options.def.  None changes any result.
+#include "options.hpp"

@@ -341,9 +341,6 @@ __global__ void __launch_bounds__(kBlock) k_spread_ray_to_sample(const float* __
 // ------------------------------------------------------------------------------------------
 // inference march (reference raymarching.cu:907-1011)
 // ------------------------------------------------------------------------------------------
-#ifndef PNR_OP_MARCH_COOP
-#define PNR_OP_MARCH_COOP 1   // 0: the plain SIMT loop (every lane walks its own ray to the end) -- the A/B of the cooperative tail in the drop-in kernel
-#endif
 // A launch lasts as long as its slowest ray (~1.3 us per probe of one lane while the other 63 idle).  Once at most kCoopRays rays of a wave
 // are still marching the whole wave works for them (march_coop_tail, march_core.hpp: the same march_probe() at the ray's next lattice
 // points, so every sample is bit for bit what the one-lane walk writes).  Lanes without a ray stay in the loop for that reason.
@@ -384,7 +381,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))
         for (;;) {
             const unsigned long long am = __ballot(active);
             if (am == 0ull) break;
-            if (PNR_OP_MARCH_COOP && p.coop && __popcll(am) <= kCoopRays) break;
+            if (p.coop && __popcll(am) <= kCoopRays) break;
             if (active) {
                 float x, y, z, dt;
                 if (march_probe<MIP, POW2>(c, t, x, y, z, dt)) {
@@ -402,7 +399,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4))
                 active = t < far && step < n_step;
             }
         }
-        if (PNR_OP_MARCH_COOP && p.coop && __ballot(active) != 0ull)
+        if (p.coop && __ballot(active) != 0ull)
             step = march_coop_tail<MIP, POW2>(coop[wave], p, grid, mip_lds, n_step, active, c, t, far, last_t, n, step, xyzs, dirs, deltas);
         if (fill_rows && keep)
             for (; step < n_step; step++) {
@@ -545,59 +542,11 @@ __global__ void __launch_bounds__(kBlock) k_get_rays(const float* __restrict__ p
 // ==========================================================================================
 // C ABI
 // ==========================================================================================
-int g_opt_block_skip = getenv("PNR_NO_BLOCK_SKIP") ? 0 : 1;
-int g_opt_coop_march = getenv("PNR_NO_COOP_MARCH") ? 0 : 1;
-int g_opt_hosted_tail = getenv("PNR_NO_HOSTED_TAIL") ? 0 : 1;   // frame loops: march stragglers finished inside the lookup launch (frame.hip: hosted_march_tail)
-int g_opt_march_budget = getenv("PNR_MARCH_BUDGET") ? atoi(getenv("PNR_MARCH_BUDGET")) : 2;     // probe rounds a later march launch spends on a ray before it hands it over
-int g_opt_march_budget0 = getenv("PNR_MARCH_BUDGET0") ? atoi(getenv("PNR_MARCH_BUDGET0")) : 0;  // the same for a frame's first launch; 0 = that launch keeps the in-wave cooperative tail
-int g_opt_march_blocks = getenv("PNR_MARCH_BLOCKS") ? atoi(getenv("PNR_MARCH_BLOCKS")) : 0;    // workgroup cap of a budgeted march launch; 0 (or 65536) = automatic: the 1 280 resident workgroups once a frame has twice as many chunks (frame.hip)
-int g_opt_aux_fusion = getenv("PNR_NO_AUX_FUSION") ? 0 : 1;
-int g_opt_composite_fusion = getenv("PNR_NO_COMPOSITE_FUSION") ? 0 : (getenv("PNR_COMPOSITE_FUSION") ? atoi(getenv("PNR_COMPOSITE_FUSION")) : 2);   // 2: the NeRF frame loop has no composite launch
-int g_opt_iteration_margin = getenv("PNR_ITERATION_MARGIN") ? atoi(getenv("PNR_ITERATION_MARGIN")) : 0;   // measured 0 / 1 / 2 / 4 on the moving-camera bench: 4.239 / 4.247 / 4.277 / 4.265 ms -- a look costs less than a spare iteration
-int g_opt_palette_waves12 = getenv("PNR_PALETTE_WAVES8") ? 0 : 1;   // specialised PaletteNeRF field kernel: 12-wave workgroups (three waves per SIMD)
-int g_opt_dynamic_tiles = getenv("PNR_DYNAMIC_TILES") ? 1 : 0;   // measured: garden 14.6 -> 20.2 ms with it on (one contended counter, scattered tiles): off
-int g_opt_grid_lane_pairs = getenv("PNR_GRID_LANE_PAIRS") ? atoi(getenv("PNR_GRID_LANE_PAIRS")) != 0 : 1;   // frame loops, one fp32 table per lookup: the x pair of a cell's corners in adjacent lanes of every gather (frame.hip: grid_pair_level); same bits
-int g_opt_grid_fast = getenv("PNR_NO_GRID_FAST") ? 0 : 1;   // pnr_grid_encode_forward: the D = 3, C = 2 kernel (k_grid_fwd_d3c2) instead of the generic one (A/B; same bits)
-int g_opt_train_coop = getenv("PNR_NO_TRAIN_COOP") ? 0 : 1;   // training march: wave-cooperative counting pass (k_march_train_count_coop)
-int g_opt_mlp_f16x3 = getenv("PNR_MLP_FP32") ? 0 : 1;   // training MLP launches (mlp.hip): split-fp16 products on the fp16 matrix pipe (1) / exact fp32 MFMA (0)
-int g_opt_coarse_image = getenv("PNR_NO_COARSE_IMAGE") ? 0 : 1;   // binned table gradient: the coarsest levels accumulated as LDS images (grid_binned.hip: k_coarse_image)
-int g_opt_scatter_staged = getenv("PNR_NO_SCATTER_STAGED") ? 0 : 1;   // binned table gradient: records ordered by bucket in LDS and written coalesced (grid_binned.hip: k_bin_scatter_staged)
-int g_opt_cell_merge = getenv("PNR_NO_CELL_MERGE") ? 0 : 1;   // binned table gradient: mid levels merge the samples of one cell before writing records
-int g_opt_flex_coop = getenv("PNR_NO_FLEX_COOP") ? 0 : 1;   // composite_rays_flex (n_step <= 8): the workgroup-cooperative kernel (coalesced rows) instead of one thread per ray; same bits
-int g_opt_grid_nt = getenv("PNR_GRID_NT") ? atoi(getenv("PNR_GRID_NT")) : 0;   // experiment: non-temporal stores (1) / input loads (2) in k_grid_fwd_d3c2
-int g_opt_adam_variant = 0;   // experiment switch of adam.hip (which multiply-adds are contracted); 0 = torch's kernels on this platform
-
 using namespace pnr;
 
 extern "C" {
 
 int pnr_abi_version(void) { return 10; }
-
-int pnr_set_option(const char* name, int value) {
-    if (!name) return PNR_ERR_INVALID;
-    if (!strcmp(name, "block_skip")) { g_opt_block_skip = value != 0; return PNR_OK; }
-    if (!strcmp(name, "coop_march")) { g_opt_coop_march = value != 0; return PNR_OK; }
-    if (!strcmp(name, "hosted_tail")) { g_opt_hosted_tail = value != 0; return PNR_OK; }
-    if (!strcmp(name, "march_budget")) { g_opt_march_budget = value < 1 ? 1 : (value > 1024 ? 1024 : value); return PNR_OK; }
-    if (!strcmp(name, "march_budget0")) { g_opt_march_budget0 = value < 0 ? 0 : (value > 1024 ? 1024 : value); return PNR_OK; }
-    if (!strcmp(name, "march_blocks")) { g_opt_march_blocks = value < 0 ? 0 : value; return PNR_OK; }
-    if (!strcmp(name, "aux_fusion")) { g_opt_aux_fusion = value != 0; return PNR_OK; }
-    if (!strcmp(name, "composite_fusion")) { g_opt_composite_fusion = value < 0 ? 0 : (value > 2 ? 2 : value); return PNR_OK; }
-    if (!strcmp(name, "palette_waves12")) { g_opt_palette_waves12 = value != 0; return PNR_OK; }
-    if (!strcmp(name, "dynamic_tiles")) { g_opt_dynamic_tiles = value != 0; return PNR_OK; }
-    if (!strcmp(name, "grid_lane_pairs")) { g_opt_grid_lane_pairs = value != 0; return PNR_OK; }
-    if (!strcmp(name, "grid_fast")) { g_opt_grid_fast = value != 0; return PNR_OK; }
-    if (!strcmp(name, "train_coop")) { g_opt_train_coop = value != 0; return PNR_OK; }
-    if (!strcmp(name, "mlp_f16x3")) { g_opt_mlp_f16x3 = value != 0; return PNR_OK; }
-    if (!strcmp(name, "coarse_image")) { g_opt_coarse_image = value != 0; return PNR_OK; }
-    if (!strcmp(name, "cell_merge")) { g_opt_cell_merge = value != 0; return PNR_OK; }
-    if (!strcmp(name, "scatter_staged")) { g_opt_scatter_staged = value != 0; return PNR_OK; }
-    if (!strcmp(name, "flex_coop")) { g_opt_flex_coop = value != 0; return PNR_OK; }
-    if (!strcmp(name, "grid_nt")) { g_opt_grid_nt = value & 3; return PNR_OK; }
-    if (!strcmp(name, "adam_variant")) { g_opt_adam_variant = value & 7; return PNR_OK; }
-    if (!strcmp(name, "iteration_margin")) { g_opt_iteration_margin = value < 0 ? 0 : (value > 64 ? 64 : value); return PNR_OK; }
-    return PNR_ERR_INVALID;
-}
 
 const char* pnr_error_string(int code) {
     switch (code) {

@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""Is the gfx950 device code of every csrc/*.hip the same at two revisions?  Each unit is compiled device-only to assembly text with the
+product's flags (build.FLAGS, the unit's UNIT_FLAGS) and the two texts are compared byte for byte.  No GPU is needed.
+usage: isa_identity.py [OLD [NEW]]   (git revisions; default HEAD~1 against the working tree).  Exit status 1 if any unit differs."""
+import concurrent.futures
+import io
+import os
+import subprocess
+import sys
+import tarfile
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from palettenerf_amd import build  # noqa: E402
+
+
+def checkout(rev, tmp):
+    """The tree whose units get compiled: ROOT itself for the working tree, else `rev`'s sources unpacked under tmp."""
+    if rev is None:
+        return ROOT
+    dst = os.path.join(tmp, "tree_" + rev.replace("/", "_"))
+    tar = subprocess.check_output(["git", "-C", ROOT, "archive", rev, "palettenerf_amd/csrc", "include"])
+    tarfile.open(fileobj=io.BytesIO(tar)).extractall(dst)
+    return dst
+
+
+def units(tree):
+    csrc = os.path.join(tree, "palettenerf_amd", "csrc")
+    return {f[:-4]: os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hip")}
+
+
+def assembly(src, out):
+    unit = os.path.basename(src)[:-4]
+    subprocess.check_call([build.hipcc(), *build.FLAGS, *build.UNIT_FLAGS.get(unit, []), "-fuse-cuid=none", "--cuda-device-only", "-S",
+                           "-Wno-unused-command-line-argument", src, "-o", out])
+    with open(out, "rb") as f:
+        return f.read()
+
+
+def first_difference(a, b):
+    la, lb = a.split(b"\n"), b.split(b"\n")
+    n = next((i for i, (x, y) in enumerate(zip(la, lb)) if x != y), min(len(la), len(lb)))
+    return f"line {n + 1}: {(la[n] if n < len(la) else b'<end of file>').decode(errors='replace').strip()!r} -> {(lb[n] if n < len(lb) else b'<end of file>').decode(errors='replace').strip()!r}"
+
+
+def main():
+    old_rev = sys.argv[1] if len(sys.argv) > 1 else "HEAD~1"
+    new_rev = sys.argv[2] if len(sys.argv) > 2 else None
+    with tempfile.TemporaryDirectory() as tmp:
+        old, new = units(checkout(old_rev, tmp)), units(checkout(new_rev, tmp))
+        with concurrent.futures.ThreadPoolExecutor(max_workers=16) as ex:
+            jobs = {(side, u): ex.submit(assembly, src, os.path.join(tmp, f"{side}_{u}.s"))
+                    for side, srcs in (("old", old), ("new", new)) for u, src in srcs.items()}
+            text = {k: j.result() for k, j in jobs.items()}
+    print(f"old: {old_rev}   new: {new_rev or 'working tree'}")
+    differ = 0
+    for u in sorted(set(old) | set(new)):
+        if u not in old or u not in new:
+            verdict = f"only in {'new' if u in new else 'old'}"
+        elif text["old", u] == text["new", u]:
+            verdict = "identical"
+        else:
+            verdict, differ = "differs: " + first_difference(text["old", u], text["new", u]), differ + 1
+        print(f"{u:16s} {verdict}")
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

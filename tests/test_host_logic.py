@@ -209,6 +209,20 @@ def test_frame_plan_rules_equal_the_expressions_they_replaced(tmp_path):
     assert p.returncode == 0, p.stderr
 
 
+def test_option_table_equals_the_chain_and_initialisers_it_replaced(tmp_path):
+    """tests/native/options_check.cpp: csrc/options.hpp (the table of options.def) against a transcription of pnr_set_option's chain of comparisons and of
+    the getenv initialisers it replaced: return code and stored value for every name (an unknown one and NULL too) over [-3, 1100], INT_MIN, INT_MAX and
+    65536; the starting values under every environment variable, alone and set to "", "0", "1", "2", "7", "5000", "-1", and under both of
+    composite_fusion's together (a stand-in lookup, not the process environment); distinct names, and the per-frame options being the twelve that pnr.h
+    lists at pnr_*_render_frame_submit.  A stand-alone program under the address and undefined-behaviour sanitizers, as above."""
+    import subprocess
+    exe = tmp_path / "options_check"
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "options_check.cpp")
+    subprocess.check_call(["g++", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover", "-o", str(exe), src])
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr
+
+
 def test_frame_workspace_sizes_are_pinned():
     """The frame workspace's layout (frame.hip: carve) is part of what callers allocate: its totals for a few frame sizes and model shapes, as literals."""
     import ctypes
