@@ -974,6 +974,98 @@ int pnr_mesh_count(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float 
 int pnr_mesh_emit(const float* u, uint32_t nx, uint32_t ny, uint32_t nz, float threshold, const void* workspace, uint64_t workspace_bytes,
                   float* vertices, uint32_t cap_vertices, int32_t* triangles, uint32_t cap_triangles, pnr_stream_t stream);
 
+/* ---- evaluate and test loops: palette sheets and meters on the device (additive, ABI 10; csrc/evaluate.hip) ----
+ * pnr_palette_sheets replaces the host half of PaletteTrainer.test, palette/utils.py:993-1038, and of the save_images block of
+ * evaluate_one_epoch, palette/utils.py:852-909 (nerf/utils.py:716-731 for a NeRF model: rgb and depth only): every `.cpu().numpy()` of an fp32
+ * map followed by `(x.clip(0, 1) * 255).astype(np.uint8)` and the np.concatenate(axis=1) of the per-basis images -- ONE launch, the frame leaves
+ * the device as bytes.  Inputs are fp32 maps of H*W rays, each with its own row stride in floats (>= its column count): columns of the frame
+ * call's aux_map are passed as they are.  A NULL input: that sheet is not written.  An output is written only when it is not NULL; an output
+ * given without its input is PNR_ERR_INVALID.  `image` and `depth` are required.
+ *   out_rgb [H,W,3]                   (uint8)(int)(clamp(s(image), 0, 1) * 255.0f), s = linear_to_srgb (nerf/utils.py:43-44, pnr_image_to_uint8's
+ *                                     expression) when asked, the identity otherwise                                    (palette/utils.py:993-999)
+ *   out_depth [H,W]                   (uint8)(int)(depth * 255.0f), no clamp                      (:1001-1002, as pnr_image_to_uint8 does)
+ *   out_view_dep, out_direct [H,W,3]  (uint8)(int)(clamp(v, 0, 1) * 255.0f)                                         (:1006-1008, :861-866)
+ *   out_basis_img, out_unscaled_basis_img [H, nb W, 3]   pixel (y, i W + x) = basis i of ray y W + x, columns 3i .. 3i + 2   (:1015-1024, :885-898)
+ *   out_basis_acc [H, nb W]           pixel (y, i W + x) = basis_acc[y W + x, i]                                        (:1017-1025)
+ *   out_weights_guide [H, nb W]       the same from gt_weights: gt_weights.transpose(0, 2, 1).reshape(H, -1)                 (:852-855)
+ *   out_basis_color [100, 100 nb, 3]  the palette swatches, basis_color [nb,3] clamped to [0, 1]                        (:1019-1026)
+ * Bytes are stored four at a time where the output's address allows, singly at ragged heads and tails (any base pointer works).
+ * H * W == 0 is PNR_OK; num_basis outside 1 .. PNR_SHEET_MAX_BASIS with a per-basis input, a stride below the column count or a NULL required
+ * pointer is PNR_ERR_INVALID; 3 nb H W >= 2^32 is PNR_ERR_UNSUPPORTED. */
+#define PNR_SHEET_MAX_BASIS 8
+typedef struct pnr_sheet_args {
+    uint32_t H, W, num_basis;
+    int linear_to_srgb;                 /* out_rgb only */
+    const float* image;                 /* [H W, 3] */
+    const float* depth;                 /* [H W] */
+    const float* view_dep_rgb;          /* [H W, 3]    optional */
+    const float* direct_rgb;            /* [H W, 3]    optional */
+    const float* basis_rgb;             /* [H W, 3 nb] optional */
+    const float* unscaled_basis_rgb;    /* [H W, 3 nb] optional */
+    const float* basis_acc;             /* [H W, nb]   optional */
+    const float* gt_weights;            /* [H W, nb]   optional */
+    const float* basis_color;           /* [nb, 3] contiguous, optional */
+    uint32_t image_stride, depth_stride, view_dep_stride, direct_stride, basis_rgb_stride, unscaled_stride, basis_acc_stride, gt_weights_stride;   /* floats per row */
+    uint8_t* out_rgb;
+    uint8_t* out_depth;
+    uint8_t* out_view_dep;
+    uint8_t* out_direct;
+    uint8_t* out_basis_img;
+    uint8_t* out_unscaled_basis_img;
+    uint8_t* out_basis_acc;
+    uint8_t* out_weights_guide;
+    uint8_t* out_basis_color;
+} pnr_sheet_args;
+int pnr_palette_sheets(const pnr_sheet_args* args, pnr_stream_t stream);
+
+/* pnr_frame_metrics replaces eval_step's ground truth and loss (palette/utils.py:610-638) and the meters' update() of evaluate_one_epoch
+ * (:825-830): PSNRMeter (nerf/utils.py:220-252), SSIMMeter (:297-330, kornia's ssim_loss(window_size=11)), SparsityMeter and TVMeter
+ * (palette/utils.py:52-114) of ONE H x W view in ONE launch, added to running totals on the device; nothing is read back per frame.
+ *   truth [H W, C], C = 3 or 4, fp32 in [0, 1]; with srgb_to_linear_truth its colour channels first go through nerf/utils.py:48-49 (:617-618);
+ *   gt = rgb a + 1 (1 - a) for C = 4 (:621-625), rgb otherwise; truth_rgb_out (optional, [H W, 3] contiguous) receives it as fp32.
+ *   mse       mean((pred - gt)^2) over the 3 H W values (the criterion of :636)           psnr  -10 log10(mse)  (nerf/utils.py:242)
+ *   sparsity  mean over pixels of sum_i w_i / (sum_i w_i^2 + 1e-6) - 1   (:69)
+ *   tv        100 (mean((w[:, :-1] - w[:, 1:])^2) + mean((w[:-1] - w[1:])^2)) over [H, W, nb]   (:101-104)
+ *   ssim      1 - 2 mean(clamp((1 - S) / 2, 0, 1)),  S = ((2 m1 m2 + C1)(2 s12 + C2)) / ((m1^2 + m2^2 + C1)(s1 + s2 + C2) + 1e-12) per channel
+ *             and pixel, m / E[.] from the 11 x 11 normalised Gaussian (sigma 1.5), border reflected without repeating the edge sample (pad 5,
+ *             "same" size), s1 = E[p^2] - m1^2, s2 = E[t^2] - m2^2, s12 = E[p t] - m1 m2, C1 = 0.01^2, C2 = 0.03^2  (nerf/utils.py:317-318).
+ *             This is kornia's ssim_loss(window_size=11) with its documented defaults as read from its documentation: kornia is not installed
+ *             where this library is developed, so nobody has run it against this statement; the float64 statement in tests/evaluate_reference.py
+ *             is the yardstick.
+ * One launch does all five (a second launch for SSIM alone was not needed: the meters other than SSIM ride on the tile load SSIM needs anyway).
+ * Arithmetic: fp32 inputs, everything after them -- the ground truth, the separable window sums, S, every sum -- in double, so E[p^2] - m^2
+ * keeps its bits on flat regions.  Reductions run in a fixed order (per-workgroup partials in double, the last workgroup, found by a ticket the
+ * kernel resets itself, adds them by index): two runs give the same bits; no atomics go into a result.
+ *   totals    device double[8], caller-owned, zero it to clear: [0] += 1 (frames), [1] += mse, [2] += psnr, [3] += ssim, [4] += sparsity, [5] += tv
+ *   frame_out optional device double[8]: this frame's values alone ([0] = 1)
+ *   workspace pnr_frame_metrics_workspace_bytes(H, W) bytes, 8-byte aligned, its first 64 bytes ZERO before the first call (the ticket)
+ * Values that `want` leaves out are 0 (PSNR implies MSE).  basis_acc == NULL: no palette meters (their bits are ignored).
+ * PNR_ERR_INVALID: a NULL pointer, C not 3 or 4, a stride below the column count, num_basis outside 1 .. PNR_MAX_BASIS with basis_acc,
+ * H or W < 6 with SSIM wanted, H or W < 2 with TV wanted, a workspace that is too small.  H * W == 0 is PNR_OK and touches nothing. */
+#define PNR_METRIC_MSE 1
+#define PNR_METRIC_PSNR 2
+#define PNR_METRIC_SSIM 4
+#define PNR_METRIC_SPARSITY 8
+#define PNR_METRIC_TV 16
+typedef struct pnr_metrics_args {
+    uint32_t H, W;
+    const float* pred;                  /* [H W, 3] rows of pred_stride floats */
+    uint32_t pred_stride;
+    const float* truth;                 /* [H W, C] contiguous */
+    uint32_t truth_channels;            /* 3 or 4 */
+    int srgb_to_linear_truth;
+    const float* basis_acc;             /* [H W, nb] rows of basis_acc_stride floats, or NULL */
+    uint32_t basis_acc_stride, num_basis;
+    uint32_t want;                      /* PNR_METRIC_* bits */
+    float* truth_rgb_out;               /* optional [H W, 3] */
+    double* totals;                     /* [8] in/out */
+    double* frame_out;                  /* optional [8] out */
+    void* workspace;
+    uint64_t workspace_bytes;
+} pnr_metrics_args;
+uint64_t pnr_frame_metrics_workspace_bytes(uint32_t H, uint32_t W);
+int pnr_frame_metrics(const pnr_metrics_args* args, pnr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,8 +126,11 @@ SIGNATURES = {
     "pnr_mesh_workspace_bytes": [_u32, _u32, _u32],
     "pnr_mesh_count": [_ptr, _u32, _u32, _u32, _f32, _ptr, _u64, _ptr, _ptr],
     "pnr_mesh_emit": [_ptr, _u32, _u32, _u32, _f32, _ptr, _u64, _ptr, _u32, _ptr, _u32, _ptr],
+    "pnr_palette_sheets": [_ptr, _ptr],
+    "pnr_frame_metrics_workspace_bytes": [_u32, _u32],
+    "pnr_frame_metrics": [_ptr, _ptr],
 }
-_RESTYPES = {"pnr_mesh_workspace_bytes": _u64, "pnr_lattice_density_workspace_bytes": _u64, "pnr_occupancy_workspace_bytes": _u64, "pnr_occupancy_samples": _u32, "pnr_adam_max_tensors": _u32, "pnr_error_string": ctypes.c_char_p, "pnr_scan_scratch_bytes": _u64, "pnr_nerf_field_packed_bytes": _u64, "pnr_occupancy_mip_bytes": _u64, "pnr_nerf_frame_workspace_bytes": _u64, "pnr_palette_field_packed_bytes": _u64, "pnr_palette_frame_workspace_bytes": _u64,
+_RESTYPES = {"pnr_frame_metrics_workspace_bytes": _u64, "pnr_mesh_workspace_bytes": _u64, "pnr_lattice_density_workspace_bytes": _u64, "pnr_occupancy_workspace_bytes": _u64, "pnr_occupancy_samples": _u32, "pnr_adam_max_tensors": _u32, "pnr_error_string": ctypes.c_char_p, "pnr_scan_scratch_bytes": _u64, "pnr_nerf_field_packed_bytes": _u64, "pnr_occupancy_mip_bytes": _u64, "pnr_nerf_frame_workspace_bytes": _u64, "pnr_palette_field_packed_bytes": _u64, "pnr_palette_frame_workspace_bytes": _u64,
              "pnr_palette_aux_channels": _u32, "pnr_linear_wgrad_workspace_bytes": _u64, "pnr_grid_backward_binned_workspace_bytes": _u64,
              "pnr_palette_train_shade_workspace_bytes": _u64, "pnr_train_loss_workspace_bytes": _u64, "pnr_mlp_packed_bytes": _u64, "pnr_mlp_backward_workspace_bytes": _u64,
              "pnr_background_packed_bytes": _u64, "pnr_background_backward_workspace_bytes": _u64}
@@ -254,6 +257,27 @@ class BackgroundTrainArgs(ctypes.Structure):
                 ("align_corners", _int), ("sh_degree", _u32), ("num_layers", _u32), ("hidden_dim", _u32), ("w0", _ptr), ("w1", _ptr), ("out", _ptr),
                 ("coords_out", _ptr), ("grad_rgb", _ptr), ("grad_w0", _ptr), ("grad_w1", _ptr), ("grad_table", _ptr), ("workspace", _ptr),
                 ("workspace_bytes", _u64)]
+
+
+SHEET_MAX_BASIS = 8   # PNR_SHEET_MAX_BASIS
+METRIC_MSE, METRIC_PSNR, METRIC_SSIM, METRIC_SPARSITY, METRIC_TV = 1, 2, 4, 8, 16   # PNR_METRIC_*
+
+
+class SheetArgs(ctypes.Structure):
+    """Mirror of `pnr_sheet_args` (include/pnr.h)."""
+    _fields_ = ([("H", _u32), ("W", _u32), ("num_basis", _u32), ("linear_to_srgb", _int)]
+                + [(n, _ptr) for n in ("image", "depth", "view_dep_rgb", "direct_rgb", "basis_rgb", "unscaled_basis_rgb", "basis_acc", "gt_weights", "basis_color")]
+                + [(n, _u32) for n in ("image_stride", "depth_stride", "view_dep_stride", "direct_stride", "basis_rgb_stride", "unscaled_stride",
+                                       "basis_acc_stride", "gt_weights_stride")]
+                + [(n, _ptr) for n in ("out_rgb", "out_depth", "out_view_dep", "out_direct", "out_basis_img", "out_unscaled_basis_img", "out_basis_acc",
+                                       "out_weights_guide", "out_basis_color")])
+
+
+class MetricsArgs(ctypes.Structure):
+    """Mirror of `pnr_metrics_args` (include/pnr.h)."""
+    _fields_ = [("H", _u32), ("W", _u32), ("pred", _ptr), ("pred_stride", _u32), ("truth", _ptr), ("truth_channels", _u32), ("srgb_to_linear_truth", _int),
+                ("basis_acc", _ptr), ("basis_acc_stride", _u32), ("num_basis", _u32), ("want", _u32), ("truth_rgb_out", _ptr), ("totals", _ptr),
+                ("frame_out", _ptr), ("workspace", _ptr), ("workspace_bytes", _u64)]
 
 
 _lib = None
