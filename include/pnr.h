@@ -1066,6 +1066,74 @@ typedef struct pnr_metrics_args {
 uint64_t pnr_frame_metrics_workspace_bytes(uint32_t H, uint32_t W);
 int pnr_frame_metrics(const pnr_metrics_args* args, pnr_stream_t stream);
 
+/* ---- training batches: gather, blend, weight guide, error map on the device (additive, ABI 10; csrc/train_batch.hip) ----
+ * pnr_train_batch replaces what a training step does in front of model.render: NeRFDataset.collate (palette/provider.py:356-410: the pose
+ * lookup, get_rays' ray arithmetic, the torch.gather of the pixels and of the feature pixels) and the head of PaletteTrainer.train_step
+ * (palette/utils.py:450-478; nerf/utils.py:507-525 likewise: srgb_to_linear, the alpha blend over the background, get_palette_weight_with_hist,
+ * palette/utils.py:117-124) -- ONE launch for B views of N rays each, one lane per ray; ray r = b N + n.  The random draws (pixel ids, the
+ * per-pixel background) stay torch's and come in as arrays; the view is chosen by an index ON THE DEVICE, nothing is read back to pick it.
+ *   images [V,H,W,C], C = 3 or 4, stored as image_format: fp32, fp16 (converted exactly) or uint8 (u / 255.0f, the loader's
+ *   astype(float32) / 255 for an 8-bit source); feat_images [V,H,W,D] fp32 or fp16 (the --pred_clip target); poses [V,4,4] fp32 row-major
+ *   cam2world with fx, fy, cx, cy as pnr_get_rays takes them; view_index [B], inds [B,N] int64 flat pixel ids; hist_weights [nb,Sr,Sg,Sb]
+ *   fp32 (the extraction's LUT without its leading 1: any sizes, r first), element (k, ir, ig, ib) at the dot product with hist_stride -- the
+ *   reference holds the table as a permuted view of an [R,G,B,nb] array, which is read where it lies, without a copy per step.
+ * Outputs, each optional by a NULL pointer, fp32:
+ *   rays_o, rays_d [B N,3]   pnr_get_rays' arithmetic on poses[view_index[b]], the same bits (both or neither)
+ *   pixels [B N,C]           the gathered pixel as fp32: collate's `images`
+ *   gt_rgb [B N,3]           c = srgb_to_linear ? (x < 0.04045 ? x / 12.92 : ((x + 0.055) / 1.055)^2.4) : x per colour channel (nerf/utils.py:48-49,
+ *                            the device library's powf), then for C = 4: c a + bg (1 - a) in fp32 as torch evaluates it -- two products, one
+ *                            difference, one sum, nothing fused; bg by bg_mode: 0 = bg_const, 1 = bg_color[3], 2 = bg_color[B N,3] (the
+ *                            trainer's rand_like draw).  C = 3: gt_rgb = c, bg is not read.
+ *   gt_weights [B N,nb]      sum over the 8 corners of hist[k, ir, ig, ib] w, read at x = gt_rgb (S - 1) per channel: i = floor(x), the corner
+ *                            weights (i + 1) - x and x - i, a corner with an index outside [0, S) counts as zero -- grid_sample(bilinear,
+ *                            padding_mode='zeros', align_corners=True) behind the reference's [2,1,0] swizzle; summed in grid_sample's corner order
+ *   gt_clip [B N,D]          the gathered feature pixel as fp32
+ * All addresses are formed in 64 bits (V H W C passes 2^32 on large sets).  A view index outside [0, V) or a pixel id outside [0, H W) is the
+ * caller's error; it is clamped into range, so nothing outside the stacks is read.
+ * B N == 0 is PNR_OK.  PNR_ERR_INVALID: a NULL required pointer, V, H or W of 0, C not 3 or 4 with a pixel output, rays_o without rays_d, fx or fy of
+ * 0 with rays, bg_mode outside 0..2 or without its array (C = 4 with a colour output), a table size of 0 or above 1024, D of 0 with gt_clip;
+ * PNR_ERR_UNSUPPORTED: an unknown format, num_basis outside 1 .. PNR_MAX_BASIS with gt_weights, H W >= 2^32. */
+#define PNR_IMAGE_FP32 0
+#define PNR_IMAGE_FP16 1
+#define PNR_IMAGE_UINT8 2
+typedef struct pnr_train_batch_args {
+    uint32_t V, H, W, C;
+    const void* images;                 /* [V,H,W,C] */
+    int image_format;                   /* PNR_IMAGE_* */
+    const void* feat_images;            /* [V,H,W,D] fp32 or fp16, optional */
+    int feat_format;                    /* PNR_IMAGE_FP32 or PNR_IMAGE_FP16 */
+    uint32_t D;
+    const float* poses;                 /* [V,4,4] */
+    float fx, fy, cx, cy;
+    const int64_t* view_index;          /* [B] on the device */
+    const int64_t* inds;                /* [B,N] */
+    uint32_t B, N;
+    int bg_mode;                        /* 0: bg_const, 1: bg_color [3], 2: bg_color [B N,3] */
+    float bg_const;
+    const float* bg_color;
+    const float* hist_weights;          /* [num_basis,Sr,Sg,Sb], optional */
+    uint32_t num_basis, Sr, Sg, Sb;
+    uint64_t hist_stride[4];            /* floats between neighbours along (basis, r, g, b); all 0 = contiguous in that order */
+    int srgb_to_linear;
+    float* rays_o;                      /* [B N,3] */
+    float* rays_d;                      /* [B N,3] */
+    float* pixels;                      /* [B N,C] */
+    float* gt_rgb;                      /* [B N,3] */
+    float* gt_weights;                  /* [B N,num_basis] */
+    float* gt_clip;                     /* [B N,D] */
+} pnr_train_batch_args;
+int pnr_train_batch(const pnr_train_batch_args* args, pnr_stream_t stream);
+
+/* The error map's update at the end of train_step (palette/utils.py:578-599, nerf/utils.py:556-580), in place on a device-resident map
+ * [V, cells] (cells = 128 * 128 in the reference) -- ONE launch, no copy of the rows out and back, no host synchronisation:
+ *   map[view_index[b], inds_coarse[b, n]] = 0.1f * map[...] + 0.9f * loss_ray[b, n]      (:595-596; two products and a sum, nothing fused)
+ * view_index [B], inds_coarse [B,N] int64 on the device, loss_ray [B,N] fp32.  The rows of inds_coarse come from multinomial(replacement=False)
+ * and are unique; duplicates within a view (or one view twice in view_index) give an unspecified winner, as torch's scatter_ does.
+ * A cell id outside [0, cells) is clamped; the number of views is not an argument, so view_index < V is the caller's to guarantee (a negative one
+ * is taken as 0).  B N == 0 is PNR_OK; a NULL pointer or cells of 0 is PNR_ERR_INVALID. */
+int pnr_error_map_update(float* error_map, uint32_t cells, const int64_t* view_index, const int64_t* inds_coarse, const float* loss_ray, uint32_t B,
+                         uint32_t N, pnr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

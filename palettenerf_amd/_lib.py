@@ -129,6 +129,8 @@ SIGNATURES = {
     "pnr_palette_sheets": [_ptr, _ptr],
     "pnr_frame_metrics_workspace_bytes": [_u32, _u32],
     "pnr_frame_metrics": [_ptr, _ptr],
+    "pnr_train_batch": [_ptr, _ptr],
+    "pnr_error_map_update": [_ptr, _u32, _ptr, _ptr, _ptr, _u32, _u32, _ptr],
 }
 _RESTYPES = {"pnr_frame_metrics_workspace_bytes": _u64, "pnr_mesh_workspace_bytes": _u64, "pnr_lattice_density_workspace_bytes": _u64, "pnr_occupancy_workspace_bytes": _u64, "pnr_occupancy_samples": _u32, "pnr_adam_max_tensors": _u32, "pnr_error_string": ctypes.c_char_p, "pnr_scan_scratch_bytes": _u64, "pnr_nerf_field_packed_bytes": _u64, "pnr_occupancy_mip_bytes": _u64, "pnr_nerf_frame_workspace_bytes": _u64, "pnr_palette_field_packed_bytes": _u64, "pnr_palette_frame_workspace_bytes": _u64,
              "pnr_palette_aux_channels": _u32, "pnr_linear_wgrad_workspace_bytes": _u64, "pnr_grid_backward_binned_workspace_bytes": _u64,
@@ -278,6 +280,20 @@ class MetricsArgs(ctypes.Structure):
     _fields_ = [("H", _u32), ("W", _u32), ("pred", _ptr), ("pred_stride", _u32), ("truth", _ptr), ("truth_channels", _u32), ("srgb_to_linear_truth", _int),
                 ("basis_acc", _ptr), ("basis_acc_stride", _u32), ("num_basis", _u32), ("want", _u32), ("truth_rgb_out", _ptr), ("totals", _ptr),
                 ("frame_out", _ptr), ("workspace", _ptr), ("workspace_bytes", _u64)]
+
+
+IMAGE_FP32, IMAGE_FP16, IMAGE_UINT8 = 0, 1, 2   # PNR_IMAGE_*
+
+
+class TrainBatchArgs(ctypes.Structure):
+    """Mirror of `pnr_train_batch_args` (include/pnr.h)."""
+    _fields_ = ([(n, _u32) for n in ("V", "H", "W", "C")]
+                + [("images", _ptr), ("image_format", _int), ("feat_images", _ptr), ("feat_format", _int), ("D", _u32), ("poses", _ptr)]
+                + [(n, _f32) for n in ("fx", "fy", "cx", "cy")]
+                + [("view_index", _ptr), ("inds", _ptr), ("B", _u32), ("N", _u32), ("bg_mode", _int), ("bg_const", _f32), ("bg_color", _ptr),
+                   ("hist_weights", _ptr)]
+                + [(n, _u32) for n in ("num_basis", "Sr", "Sg", "Sb")] + [("hist_stride", _u64 * 4), ("srgb_to_linear", _int)]
+                + [(n, _ptr) for n in ("rays_o", "rays_d", "pixels", "gt_rgb", "gt_weights", "gt_clip")])
 
 
 _lib = None

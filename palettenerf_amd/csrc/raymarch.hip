@@ -7,6 +7,7 @@
 #include "pnr_common.hpp"
 #include "march_core.hpp"
 #include "sph_core.hpp"
+#include "ray_core.hpp"
 
 namespace pnr {
 
@@ -523,18 +524,7 @@ __global__ void __launch_bounds__(kBlock) k_get_rays(const float* __restrict__ p
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x, b = blockIdx.y;
     if (n >= N) return;
     const uint32_t p = inds ? (uint32_t)inds[(size_t)b * N + n] : n;
-    const float xs = (((float)(p % W) + 0.5f) - cx) / fx;
-    const float ys = (((float)(p / W) + 0.5f) - cy) / fy;
-    const float nrm = sqrtf(fmaf(xs, xs, fmaf(ys, ys, 1.0f)));
-    const float d0 = xs / nrm, d1 = ys / nrm, d2 = 1.0f / nrm;
-    const float* P = poses + (size_t)b * 16;
-    float* o = rays_o + ((size_t)b * N + n) * 3;
-    float* d = rays_d + ((size_t)b * N + n) * 3;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        d[k] = fmaf(d2, P[k * 4 + 2], fmaf(d1, P[k * 4 + 1], d0 * P[k * 4 + 0]));
-        o[k] = P[k * 4 + 3];
-    }
+    pinhole_ray(poses, b, p, W, fx, fy, cx, cy, rays_o, rays_d, (size_t)b * N + n);   // ray_core.hpp
 }
 
 }  // namespace pnr

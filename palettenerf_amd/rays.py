@@ -49,6 +49,24 @@ def _pair_indices(H, W, count, reach, device):
     return torch.cat([y0 * W + x0, y1 * W + x1], dim=0)
 
 
+def draw_indices(H, W, N, error_map=None, patch_size=1, random_size=0, B=1, device=None):
+    """The pixel selection of nerf/utils.py:get_rays (:75-131) for N > 0 rays per view: (inds [B,N] int64, inds_coarse [B,N] or None).
+    error_map: the [B, 128 * 128] rows of the views in this batch, or None.  The torch RNG calls come in the reference's order, so the same
+    torch seed selects the same pixels; `get_rays` and `trainset.TrainSet` both draw here."""
+    if patch_size > 1:
+        return _patch_indices(H, W, N, patch_size, device).expand(B, -1), None
+    if random_size > 0:
+        return _pair_indices(H, W, N, random_size, device).expand(B, -1), None
+    if error_map is None:
+        return torch.randint(0, H * W, size=[N], device=device).expand(B, N), None
+    coarse = torch.multinomial(error_map.to(device), N, replacement=False)  # [B, N] cells of the 128 x 128 error grid
+    cy, cx = coarse // 128, coarse % 128
+    sy, sx = H / 128, W / 128
+    yy = (cy * sy + torch.rand(B, N, device=device) * sy).long().clamp(max=H - 1)
+    xx = (cx * sx + torch.rand(B, N, device=device) * sx).long().clamp(max=W - 1)
+    return yy * W + xx, coarse
+
+
 def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, patch_size=1, random_size=0):
     """Drop-in for nerf/utils.py:get_rays: returns {'rays_o', 'rays_d', 'inds'[, 'inds_coarse']} with [B,N,3] / [B,N] tensors.
     Random draws follow the reference's call order, so the same torch seed selects the same pixels."""
@@ -57,19 +75,8 @@ def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, patch_size=1, random
     out = {}
     if N > 0:
         N = min(N, H * W)
-        if patch_size > 1:
-            inds = _patch_indices(H, W, N, patch_size, device).expand(B, -1)
-        elif random_size > 0:
-            inds = _pair_indices(H, W, N, random_size, device).expand(B, -1)
-        elif error_map is None:
-            inds = torch.randint(0, H * W, size=[N], device=device).expand(B, N)
-        else:
-            coarse = torch.multinomial(error_map.to(device), N, replacement=False)  # [B, N] cells of the 128 x 128 error grid
-            cy, cx = coarse // 128, coarse % 128
-            sy, sx = H / 128, W / 128
-            yy = (cy * sy + torch.rand(B, N, device=device) * sy).long().clamp(max=H - 1)
-            xx = (cx * sx + torch.rand(B, N, device=device) * sx).long().clamp(max=W - 1)
-            inds = yy * W + xx
+        inds, coarse = draw_indices(H, W, N, error_map, patch_size, random_size, B, device)
+        if coarse is not None:
             out["inds_coarse"] = coarse
         rays_o, rays_d = rays_from_indices(poses, intrinsics, H, W, inds)
     else:
