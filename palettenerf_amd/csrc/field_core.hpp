@@ -261,28 +261,33 @@ struct FieldOut { float sigma_logit, o0, o1, o2; };
 // features (hash tables at the reference's initialisation scale U(-1e-4, 1e-4), gridencoder/grid.py:107) out of the fp16 subnormal range.
 // the 8 encoder rows of a lane (levels 4h..4h+3 and 8+4h..8+4h+3; 32 samples x 2 channels = 256 contiguous bytes per level and half-wave),
 // issued together into fresh registers (load8_fresh, pnr_common.hpp).  `row` is a row that exists (callers clamp it); dead lanes get zeros.
-__device__ __forceinline__ void load_enc_rows8(const float* __restrict__ enc, size_t level_stride, uint32_t row, bool valid, int h, float x[2][8]) {
+// (in two steps for a caller that requests the rows before it knows `valid`: the request, and the registers as the k-blocks' elements)
+__device__ __forceinline__ void load_enc_raw8(const float* __restrict__ enc, size_t level_stride, uint32_t row, int h, f32x2 (&v)[8]) {
     const f32x2* p[8];
-    f32x2 v[8];
 #pragma unroll
     for (int kb = 0; kb < 2; kb++)
 #pragma unroll
         for (int q = 0; q < 4; q++) p[4 * kb + q] = reinterpret_cast<const f32x2*>(enc + ((size_t)(8 * kb + 4 * h + q) * level_stride + row) * 2);
     load8_fresh(p, v);
+}
+__device__ __forceinline__ void enc_rows8_of(const f32x2 (&v)[8], bool valid, float x[2][8]) {
 #pragma unroll
     for (int kb = 0; kb < 2; kb++)
 #pragma unroll
         for (int q = 0; q < 4; q++) { x[kb][2 * q] = valid ? v[4 * kb + q].x : 0.0f; x[kb][2 * q + 1] = valid ? v[4 * kb + q].y : 0.0f; }
 }
+__device__ __forceinline__ void load_enc_rows8(const float* __restrict__ enc, size_t level_stride, uint32_t row, bool valid, int h, float x[2][8]) {
+    f32x2 v[8];
+    load_enc_raw8(enc, level_stride, row, h, v);
+    enc_rows8_of(v, valid, x);
+}
+// x: the lane's encoder rows (load_enc_rows8: zeros in dead lanes)
 template <bool CHECK, bool LO = true>
-__device__ __forceinline__ FieldOut nerf_field_tile_f16x3(const unsigned char* __restrict__ w, int lane, bool valid, const float* __restrict__ enc,
-                                                          size_t level_stride, uint32_t row, float dx, float dy, float dz, float enc_scale,
-                                                          SplitWatch<CHECK>& sw) {
+__device__ __forceinline__ FieldOut nerf_field_tile_f16x3_rows(const unsigned char* __restrict__ w, int lane, float x[2][8], float dx, float dy, float dz,
+                                                               float enc_scale, SplitWatch<CHECK>& sw) {
     const int h = lane >> 5;
     h8 bh[2], bl[2];
     {   // sigma_net[0] inputs: k-block kb, element j  <-  encoder feature 16 kb + 8 h + j  = (level 8 kb + 4 h + j/2, channel j&1)
-        float x[2][8];
-        load_enc_rows8(enc, level_stride, row, valid, h, x);
         if (enc_scale != 1.0f) {
 #pragma unroll
             for (int j = 0; j < 8; j++) { x[0][j] *= enc_scale; x[1][j] *= enc_scale; }
@@ -351,6 +356,14 @@ __device__ __forceinline__ FieldOut nerf_field_tile_f16x3(const unsigned char* _
     head3_valu(w + 20 * kF16BlockBytes + (uint32_t)h * kVecHeadHalfBytes, d0, d1, o);
     out.o0 = o[0]; out.o1 = o[1]; out.o2 = o[2];
     return out;
+}
+template <bool CHECK, bool LO = true>
+__device__ __forceinline__ FieldOut nerf_field_tile_f16x3(const unsigned char* __restrict__ w, int lane, bool valid, const float* __restrict__ enc,
+                                                          size_t level_stride, uint32_t row, float dx, float dy, float dz, float enc_scale,
+                                                          SplitWatch<CHECK>& sw) {
+    float x[2][8];
+    load_enc_rows8(enc, level_stride, row, valid, lane >> 5, x);
+    return nerf_field_tile_f16x3_rows<CHECK, LO>(w, lane, x, dx, dy, dz, enc_scale, sw);
 }
 
 // One wave-tile of the NeRF field, exact-fp32 matrix path.  w: the 48 KiB fp32 blob in LDS.

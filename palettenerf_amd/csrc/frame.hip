@@ -1065,15 +1065,18 @@ __global__ void __launch_bounds__(256) k_interleave_tables3_half(const float2* _
 constexpr int kFieldThreads = 512;
 // The compositing step of the iteration is done right here by the lanes that hold the samples' sigma and rgb: same operations in the same
 // order as k_frame_composite's phase 2 on the same values (what it would re-read from sigmas / rgbs), including the per-chunk survivor
-// counts of the compaction.  fuse_mode 1: iterations with one sample per ray only (27 of the 29 of the benchmark frame; a 256-sample tile
-// IS chunk `tile` of the alive list, one plain store per tile) -- k_frame_composite returns at once on such iterations; fuse_mode 2
+// counts of the compaction.  fuse_mode 1: iterations with one sample per ray only (27 of the 29 of the benchmark frame; a 32-sample wave
+// tile lies inside one chunk of the alive list, one atomic add per wave tile that keeps a ray) -- k_frame_composite returns at once on such iterations; fuse_mode 2
 // (default): every iteration, and the frame loop has no composite launch.  With n_step samples per ray a wave tile holds
 // floor(32 / n_step) whole rays (30 or 28 of its 32 rows for n_step = 3, 5, 6, 7); the lane of a ray's first row walks the ray's rows
 // through wave shuffles; survivors are added to their chunk's count with at most two atomics per wave (the count arrays alternate between
 // iterations and the march launch clears the one its iteration fills).
 // CHECK (split-fp16 only): watch the split operands for magnitudes beyond fp16's range and raise scratch[1] (SplitWatch, field_core.hpp)
 template <int PREC, bool CHECK>
-__global__ void __launch_bounds__(kFieldThreads) k_frame_field(const FrameCtl* __restrict__ ctl, const float* __restrict__ enc, uint32_t level_stride,
+// (the unwatched split-fp16 forms hold their early loads in the 128 registers of four waves per SIMD -- two workgroups per CU, the whole launch resident --
+// without scratch; the exact-fp32 and the watching forms keep the registers they had and load where they always did)
+__global__ void __launch_bounds__(kFieldThreads) __attribute__((amdgpu_waves_per_eu((PREC != 0 && !CHECK) ? 4 : 2)))
+k_frame_field(const FrameCtl* __restrict__ ctl, const float* __restrict__ enc, uint32_t level_stride,
                                                                const float* __restrict__ dirs, const float* __restrict__ deltas,
                                                                const float* __restrict__ packed, float density_scale, float enc_scale, float* __restrict__ sigmas,
                                                                float* __restrict__ rgbs, int fuse_mode, float T_thresh, int32_t* __restrict__ rays_alive,
@@ -1085,28 +1088,59 @@ __global__ void __launch_bounds__(kFieldThreads) k_frame_field(const FrameCtl* _
     const bool fuse = fuse_mode && n_step == 1;
     const bool fuse_rays = fuse_mode == 2 && n_step > 1;
     const uint32_t rpw = fuse_rays ? (32u / n_step) * n_step : 32u;   // rows of a wave tile: whole rays
-    const uint32_t rpt = rpw * (kFieldThreads / PNR_WAVE);
-    const uint32_t ntiles = (B + rpt - 1) / rpt;
-    if (blockIdx.x >= ntiles) return;
+    const uint32_t nwt = (B + rpw - 1) / rpw;   // wave tiles of this launch
+    constexpr uint32_t kWaves = kFieldThreads / PNR_WAVE;
+    if (field_wave_tile(0, 0, blockIdx.x, gridDim.x, kWaves) >= nwt) return;   // (a workgroup's first wave tile is its wave 0's: nothing at all for this one)
     __shared__ float w[kPackedFloats];
-    __shared__ int wsum[kFieldThreads / PNR_WAVE];
     for (int i = threadIdx.x * 4; i < kPackedFloats; i += kFieldThreads * 4) lds_copy16(&packed[i], &w[i]);
-    bool weights_ready = false;   // the wait for the weights sits behind the first tile's own loads (every wave passes it exactly once: here or after the loop)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
+    const int lane = threadIdx.x & 63, h = lane >> 5;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t l = (uint32_t)lane & 31u;
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint32_t n = tile * rpt + wave * rpw + l;
-        const bool mine = l < rpw && n < B;
-        const float dl0 = mine ? deltas[(size_t)n * 2] : 0.0f;
+    // Every wave walks its own wave tiles (frame_plan.hpp: field_wave_tile); wave tile wt holds rows wt * rpw + l, the rows that wave wt % 8 of the
+    // 256-row tile wt / 8 held when tiles were dealt by the workgroup, so every lane computes what it always did.  The waves of a workgroup meet once,
+    // for the weights in LDS.
+    for (uint32_t it = 0;; it++) {
+        const uint32_t wt = field_wave_tile(it, wave, blockIdx.x, gridDim.x, kWaves);
+        const bool have = wt < nwt;
+        if (it != 0 && !have) break;
+        const uint32_t n = wt * rpw + l;
+        const bool mine = have && l < rpw && n < B;
+        // Everything the tile reads by its row number is requested here, in one trip: the slot's (delta_0, delta_1) as one pair, for the one-sample
+        // composite its ray and -- the unwatched split-fp16 forms -- the encoder rows and the direction, before `dl` has said which lanes are dead
+        // (row nc exists; a dead lane's values become zeros below, as they always were)
+        f32x2 dl = {0.0f, 0.0f};
+        if (mine) dl = *reinterpret_cast<const f32x2*>(deltas + (size_t)n * 2);
+        int index_early = 0;
+        if (fuse && mine && h == 0) index_early = rays_alive[n];
+        const float dl0 = dl.x;
         const bool valid = mine && dl0 != 0.0f;
         FieldOut o = {0.0f, 0.0f, 0.0f, 0.0f};
         const uint32_t nc = n < B ? n : (B - 1);
         float dx = 0.0f, dy = 0.0f, dz = 0.0f;
-        if (valid) { dx = dirs[(size_t)nc * 3]; dy = dirs[(size_t)nc * 3 + 1]; dz = dirs[(size_t)nc * 3 + 2]; }
-        if (!weights_ready) { lds_copy_wait(); __syncthreads(); weights_ready = true; }   // (tile loop trip counts are block-uniform: all waves of a block are here together)
+        constexpr bool kEarlyEnc = PREC != 0 && !CHECK;
+        [[maybe_unused]] f32x2 ev[8];
+        if constexpr (kEarlyEnc) {
+            if (have) {
+                load_enc_raw8(enc, level_stride, nc, h, ev);
+                dx = dirs[(size_t)nc * 3]; dy = dirs[(size_t)nc * 3 + 1]; dz = dirs[(size_t)nc * 3 + 2];
+            }
+            dx = valid ? dx : 0.0f; dy = valid ? dy : 0.0f; dz = valid ? dz : 0.0f;
+        } else {
+            if (valid) { dx = dirs[(size_t)nc * 3]; dy = dirs[(size_t)nc * 3 + 1]; dz = dirs[(size_t)nc * 3 + 2]; }
+        }
+        // the wait for the weights sits behind the first tile's own loads.  Every wave passes it exactly once, in its round 0 -- a wave without a
+        // tile too: it has its share of the lds_copy16 traffic in flight and its partners count on it at the barrier
+        if (it == 0) { lds_copy_wait(); __syncthreads(); }
+        if (!have) break;
         if (__any(valid)) {   // wave-uniform: otherwise all 32 slots of this wave are dead or out of range
             SplitWatch<CHECK> sw;
-            o = nerf_field_tile<PREC, CHECK>(w, lane, valid, enc, level_stride, nc, dx, dy, dz, enc_scale, sw);
+            if constexpr (kEarlyEnc) {
+                float x[2][8];
+                enc_rows8_of(ev, valid, x);
+                o = nerf_field_tile_f16x3_rows<CHECK, PREC == 1>(reinterpret_cast<const unsigned char*>(w), lane, x, dx, dy, dz, enc_scale, sw);
+            } else {
+                o = nerf_field_tile<PREC, CHECK>(w, lane, valid, enc, level_stride, nc, dx, dy, dz, enc_scale, sw);
+            }
             if constexpr (CHECK) { if (sw.overflowed()) scratch[1] = 1; }
         }
         float sigma = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
@@ -1120,10 +1154,10 @@ __global__ void __launch_bounds__(kFieldThreads) k_frame_field(const FrameCtl* _
                 rgbs[(size_t)n * 3] = cr; rgbs[(size_t)n * 3 + 1] = cg; rgbs[(size_t)n * 3 + 2] = cb;
             }
         }
-        if (fuse) {   // block-uniform
+        if (fuse) {   // launch-uniform
             int keep = 0;
             if (h == 0 && n < B) {   // slot n of the alive list: k_frame_composite phase 2 with n_step == 1
-                const int index = rays_alive[n];
+                const int index = index_early;
                 float ws = weights_sum[index], t = rays_t[index], d = depth[index];
                 float r = image[index * 3], g = image[index * 3 + 1], b = image[index * 3 + 2];
                 bool stepped = false;
@@ -1132,7 +1166,7 @@ __global__ void __launch_bounds__(kFieldThreads) k_frame_field(const FrameCtl* _
                     const float T = 1.0f - ws;
                     const float wgt = alpha * T;
                     ws += wgt;
-                    t += deltas[(size_t)n * 2 + 1];
+                    t += dl.y;
                     d = fmaf(wgt, t, d);
                     r = fmaf(wgt, cr, r); g = fmaf(wgt, cg, g); b = fmaf(wgt, cb, b);
                     stepped = !(T < T_thresh);
@@ -1141,17 +1175,11 @@ __global__ void __launch_bounds__(kFieldThreads) k_frame_field(const FrameCtl* _
                 weights_sum[index] = ws; depth[index] = d;
                 image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
             }
+            // the wave tile's 32 slots lie inside chunk wt / 8 of the alive list, whose count the iteration's march launch has cleared (integer adds commute)
             const unsigned long long m = __ballot(keep);
-            if (lane == 0) wsum[wave] = __popcll(m);
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                int tot = 0;
-                for (int wv = 0; wv < kFieldThreads / (int)PNR_WAVE; wv++) tot += wsum[wv];
-                counts_cur[tile] = tot;
-            }
-            __syncthreads();
-        } else if (fuse_rays) {   // block-uniform: k_frame_composite phase 2 for rays of n_step rows, all inside this wave's lower half
-            const float dl1 = (valid && h == 0) ? deltas[(size_t)n * 2 + 1] : 0.0f;
+            if (m != 0ull && lane == 0) atomicAdd(&counts_cur[wt >> 3], __popcll(m));
+        } else if (fuse_rays) {   // launch-uniform: k_frame_composite phase 2 for rays of n_step rows, all inside this wave's lower half
+            const float dl1 = (valid && h == 0) ? dl.y : 0.0f;
             const bool leader = h == 0 && mine && (l % n_step) == 0;
             const uint32_t slot = n / n_step;
             int index = 0;
@@ -1189,7 +1217,7 @@ __global__ void __launch_bounds__(kFieldThreads) k_frame_field(const FrameCtl* _
             }
             const unsigned long long km = __ballot(keep);
             if (km != 0ull) {   // the wave's rays are consecutive slots: at most two chunks
-                const uint32_t c0 = ((tile * rpt + wave * rpw) / n_step) >> 8;
+                const uint32_t c0 = ((wt * rpw) / n_step) >> 8;
                 const unsigned long long k0 = __ballot(keep && (slot >> 8) == c0);
                 if (lane == 0) {
                     if (k0) atomicAdd(&counts_cur[c0], __popcll(k0));

@@ -38,6 +38,15 @@ inline uint32_t rows_upper_bound(uint32_t alive_ub, uint32_t N) { return (uint64
 inline uint32_t lookup_blocks(uint32_t rows_ub) { return plan_cdiv(rows_ub, 256); }
 inline uint32_t lookup_blocks_capped(uint32_t rows_ub) { return plan_min(lookup_blocks(rows_ub), 1024u); }
 inline uint32_t field_blocks(uint32_t rows_ub) { return plan_min(lookup_blocks(rows_ub), 512u); }
+// The NeRF field launch deals 32-row wave tiles to its waves statically, SIMD-major: of a round's grid * waves tiles, four consecutive ones go to
+// waves 0..3 of a workgroup (one per SIMD: wave w sits on SIMD w % 4), workgroup after workgroup, then four each to waves 4..7.  A launch's last,
+// partial round so gives the first workgroups one tile per SIMD before any SIMD gets a second one (dealt by the workgroup, eight waves of the first
+// few workgroups took it; dealt wave-major as the PaletteNeRF field does it, (it * waves + wave) * grid + block, the same waves of ALL workgroups,
+// the last ones to start included: profiles/EXPERIMENTS.md).  A wave's tiles ascend with `it`: it stops at its first tile beyond the launch's
+// count; a workgroup's first tile is its wave 0's.  `waves` is a multiple of four.  constexpr: the kernel calls it too.
+constexpr uint32_t field_wave_tile(uint32_t it, uint32_t wave, uint32_t block, uint32_t grid, uint32_t waves) {
+    return it * grid * waves + (wave / 4u) * (grid * 4u) + block * 4u + (wave % 4u);
+}
 // hosted tail (MODE 2): the march gives every ray `budget` sample-less probes and queues the rest for the lookup launch's first workgroups
 inline uint32_t march_budget(bool hosted, int iter, int budget_first, int budget_later) { return hosted ? (uint32_t)(iter == 0 ? budget_first : budget_later) : 0u; }
 inline int march_mode(uint32_t budget) { return budget ? 2 : 1; }
