@@ -63,33 +63,11 @@ __device__ __forceinline__ bool bg_level_corners(const BgParams& p, uint32_t lev
     const uint32_t resolution = p.resolution[level];
     float pos[2];
     uint32_t pg[2];
+    grid_cell<2>(in, scale, p.align_corners, pg, pos);
 #pragma unroll
-    for (uint32_t d = 0; d < 2; d++) {
-        pos[d] = fmaf(in[d], scale, p.align_corners ? 0.0f : 0.5f);
-        const float fl = floorf(pos[d]);
-        pg[d] = (uint32_t)fl;
-        pos[d] -= (float)pg[d];
-        pg[d] = pg[d] < resolution ? pg[d] : resolution - 1u;   // the identity for inputs in [0, 1] (pg <= scale + 0.5 < resolution); keeps any other cell inside the level
-    }
-    // get_grid_index (gridencoder.cu:49-72) by kind of level, decided by the running stride as grid_index does; wave-uniform
-    const uint32_t side = p.align_corners ? resolution : resolution + 1u;
-    const bool dense = !p.align_corners && (uint64_t)side * side <= (uint64_t)hashmap_size;      // index < side^2 <= size: the `%` is the identity
-    uint32_t stride = 1u;
-#pragma unroll
-    for (uint32_t d = 0; d < 2; d++)
-        if (stride <= hashmap_size) stride *= side;
-    const bool hashed_pow2 = !dense && p.gridtype == 0u && stride > hashmap_size && (hashmap_size & (hashmap_size - 1u)) == 0u;
-#pragma unroll
-    for (uint32_t idx = 0; idx < 4; idx++) {
-        const uint32_t pl[2] = {pg[0] + (idx & 1u), pg[1] + ((idx >> 1) & 1u)};
-        float w = 1.0f;
-        w *= (idx & 1u) ? pos[0] : 1.0f - pos[0];
-        w *= (idx & 2u) ? pos[1] : 1.0f - pos[1];
-        ws[idx] = w;
-        if (dense) idxs[idx] = pl[0] + pl[1] * side;
-        else if (hashed_pow2) idxs[idx] = (pl[0] ^ (pl[1] * 2654435761u)) & (hashmap_size - 1u);
-        else idxs[idx] = grid_index<2, 1>(p.gridtype, p.align_corners, hashmap_size, resolution, pl);
-    }
+    for (uint32_t d = 0; d < 2; d++) pg[d] = pg[d] < resolution ? pg[d] : resolution - 1u;   // the identity for inputs in [0, 1] (pg <= scale + 0.5 < resolution); keeps any other cell inside the level
+    corner_weights<2>(pos, ws);
+    corner_rows<2, 1>(level_kind<2>(p.gridtype, hashmap_size, resolution, p.align_corners), p.gridtype, p.align_corners, hashmap_size, resolution, pg, idxs);   // (wave-uniform kind)
     return true;
 }
 

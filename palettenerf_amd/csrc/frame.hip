@@ -528,9 +528,7 @@ struct GridArgs {
     const int32_t* offsets; LevelParams lp;
     uint32_t level_stride; float bound, two_bound, inv_two_bound /* exact reciprocal when 2 * bound is a power of two, else 0 */; uint32_t gridtype;
 };
-// kind: how a row index is formed on this level (gridencoder.cu:49-72 evaluated once per level instead of once per corner) --
-//   0 the reference's general form (stride test per dimension, hash or tiled, `%`); 1 dense: side^3 <= size, the index is below the size and the
-//   `%` is the identity; 2 hashed with a power-of-two size: a mask.  All three give the same index (tests: every table layout against k_grid_fwd).
+// kind: how a row index is formed on this level (grid_xside.hpp: level_kind)
 struct LevelCtx { uint32_t off0, hashmap_size, resolution; float scale; uint32_t kind; };
 __device__ __forceinline__ LevelCtx level_ctx(const GridArgs& g, uint32_t level) {
     LevelCtx lc;
@@ -538,14 +536,12 @@ __device__ __forceinline__ LevelCtx level_ctx(const GridArgs& g, uint32_t level)
     lc.hashmap_size = (uint32_t)g.offsets[level + 1] - lc.off0;
     lc.scale = g.lp.scale[level];
     lc.resolution = g.lp.resolution[level];
-    lc.kind = level_kind(g.gridtype, lc.hashmap_size, lc.resolution);
+    lc.kind = level_kind<3>(g.gridtype, lc.hashmap_size, lc.resolution);
     return lc;
 }
 // the eight corners of row b's cell on one level: row indices (x CMUL) and the fractional position the weights come from; false = the point is outside [0, 1]^3
 template <uint32_t CMUL>
 __device__ __forceinline__ bool grid_corner_rows(const GridArgs& g, const LevelCtx& lc, uint32_t b, uint32_t idxs[8], float pos[3]) {
-    float in[3];
-    bool oob = false;
     // the row's three coordinates requested together (one 12-byte load): left alone the compiler sinks each 4-byte load to its use and waits for it there -- three
     // memory round trips in a row in front of the eight gathers.  One empty asm statement that names all three pins the point where they must have arrived.
     // (Frame times did not move -- the launch has seven waves per SIMD to cover the trips -- but the hosted tail's spills did: k_frame_grid 44 -> 0 B of scratch
@@ -554,95 +550,34 @@ __device__ __forceinline__ bool grid_corner_rows(const GridArgs& g, const LevelC
 #pragma unroll
     for (int d = 0; d < 3; d++) xyz[d] = g.xyzs[(size_t)b * 3 + d];
     asm volatile("" : "+v"(xyz[0]), "+v"(xyz[1]), "+v"(xyz[2]));
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        // GridEncoder.forward's (x + bound) / (2 bound) (gridencoder/grid.py:142).  With 2 * bound a power of two -- every shipped scene -- the division
-        // is an exact scaling and so is the multiplication by the exact reciprocal: same bits, one v_mul instead of the ~10-instruction IEEE
-        // division (three per (sample, level): an eighth of this kernel's vector instructions).  Any other bound divides.
-        const float sft = xyz[d] + g.bound;
-        in[d] = g.inv_two_bound != 0.0f ? sft * g.inv_two_bound : sft / g.two_bound;
-        oob |= (in[d] < 0.0f) | (in[d] > 1.0f);
-    }
-    if (oob) return false;
+    float in[3];
+    if (!unit_cube_of(xyz, g.bound, g.two_bound, g.inv_two_bound, in)) return false;
     uint32_t pg[3];
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        pos[d] = fmaf(in[d], lc.scale, 0.5f);
-        const float fl = floorf(pos[d]);
-        pg[d] = (uint32_t)fl;
-        pos[d] -= (float)pg[d];
-    }
-    corner_rows_by_kind<CMUL>(lc.kind, g.gridtype, lc.hashmap_size, lc.resolution, pg, idxs);   // (kind is wave-uniform in the level-major workgroups; 0 in the hosted tail)
+    grid_cell<3>(in, lc.scale, false, pg, pos);
+    corner_rows<3, CMUL>(lc.kind, g.gridtype, false, lc.hashmap_size, lc.resolution, pg, idxs);   // (kind is wave-uniform in the level-major workgroups; 0 in the hosted tail)
     return true;
 }
-// trilinear weights in the reference's order of multiplications (gridencoder.cu:150-163)
-__device__ __forceinline__ void grid_corner_weights(const float pos[3], float ws[8]) {
-#pragma unroll
-    for (uint32_t idx = 0; idx < 8; idx++) {
-        float w = 1.0f;
-#pragma unroll
-        for (uint32_t d = 0; d < 3; d++) w *= (idx & (1u << d)) ? pos[d] : 1.0f - pos[d];
-        ws[idx] = w;
-    }
-}
-// The eight gathers of a row go out first, back to back, and the weights are formed while they are in flight: every address exists before
-// the first load (one empty asm statement with all of them as operands pins that point) and nothing is scheduled across the end of the
-// group.  Left to itself the compiler does this too -- until it is asked to keep the kernel within a register budget
-// (amdgpu_waves_per_eu, which the hosted tail needs): then it forms the weights first and threads the loads between the address
-// arithmetic, and the lego launch takes 76 instead of 66 us with the very same instructions (profiles/scratch/prof_ref.sh).
-// ORDERED = false (the hosted tail's own few rows; GK_TRIPLE, whose 16 addresses + 48 values do not fit the budget): the compiler's order.
-template <typename T, uint32_t MUL, bool ORDERED>
-__device__ __forceinline__ void gather8(const T* tab, const uint32_t (&idxs)[8], T (&v)[8]) {
-    const T* p[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) p[i] = tab + (size_t)idxs[i] * MUL;
-    if constexpr (!ORDERED) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) v[i] = *p[i];
-        return;
-    }
-    load8_fresh(p, v);
-}
+// One row on one level, through grid_core.hpp's cell_interp for every layout of one gather per corner.  ORDERED = false: the hosted tail's own few
+// rows.  GK_TRIPLE, whose 16 addresses + 48 values do not fit the register budget, keeps its two gathers per corner in the compiler's order.
 // (table / enc0: the table and first output of this call -- GK_SINGLE picks them per blockIdx.z; resolved by the caller, outside its row loop)
 template <int KIND, bool ORDERED = true>
 __device__ __forceinline__ void grid_row(const GridArgs& g, const LevelCtx& lc, uint32_t level, const void* __restrict__ table, float* __restrict__ enc0, uint32_t b) {
     uint32_t idxs[8];
-    float pos[3], ws[8];
+    float pos[3];
     const size_t o = ((size_t)level * g.level_stride + b) * 2;
-    if constexpr (KIND == GK_SINGLE) {
-        float acc[2] = {0.0f, 0.0f};
-        if (grid_corner_rows<1>(g, lc, b, idxs, pos)) {
-            f32x2 v[8];
-            gather8<f32x2, 1, ORDERED>(static_cast<const f32x2*>(table) + lc.off0, idxs, v);
-            grid_corner_weights(pos, ws);
-#pragma unroll
-            for (uint32_t idx = 0; idx < 8; idx++) { acc[0] = fmaf(ws[idx], v[idx].x, acc[0]); acc[1] = fmaf(ws[idx], v[idx].y, acc[1]); }
-        }
-        *reinterpret_cast<float2*>(enc0 + o) = make_float2(acc[0], acc[1]);
-    } else if constexpr (KIND == GK_PAIR) {
-        float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (grid_corner_rows<1>(g, lc, b, idxs, pos)) {
-            f32x4 v[8];
-            gather8<f32x4, 1, ORDERED>(static_cast<const f32x4*>(table) + lc.off0, idxs, v);
-            grid_corner_weights(pos, ws);
-#pragma unroll
-            for (uint32_t idx = 0; idx < 8; idx++) {
-                out.x = fmaf(ws[idx], v[idx].x, out.x); out.y = fmaf(ws[idx], v[idx].y, out.y);
-                out.z = fmaf(ws[idx], v[idx].z, out.z); out.w = fmaf(ws[idx], v[idx].w, out.w);
-            }
-        }
-        *reinterpret_cast<float2*>(enc0 + o) = make_float2(out.x, out.y);
-        *reinterpret_cast<float2*>(g.enc[1] + o) = make_float2(out.z, out.w);
-    } else if constexpr (KIND == GK_TRIPLE) {
+    if constexpr (KIND == GK_TRIPLE) {
         float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         float2 outc = make_float2(0.0f, 0.0f);
         if (grid_corner_rows<1>(g, lc, b, idxs, pos)) {
             f32x4 v[8];
             f32x2 vc[8];
+            float ws[8];
             const f32x4* tab = static_cast<const f32x4*>(table) + (size_t)lc.off0 * 2;
-            gather8<f32x4, 2, false>(tab, idxs, v);
-            gather8<f32x2, 4, false>(reinterpret_cast<const f32x2*>(tab + 1), idxs, vc);
-            grid_corner_weights(pos, ws);
+#pragma unroll
+            for (int i = 0; i < 8; i++) v[i] = tab[(size_t)idxs[i] * 2];
+#pragma unroll
+            for (int i = 0; i < 8; i++) vc[i] = reinterpret_cast<const f32x2*>(tab + 1)[(size_t)idxs[i] * 4];
+            corner_weights<3>(pos, ws);
 #pragma unroll
             for (uint32_t idx = 0; idx < 8; idx++) {
                 out.x = fmaf(ws[idx], v[idx].x, out.x); out.y = fmaf(ws[idx], v[idx].y, out.y);
@@ -654,28 +589,19 @@ __device__ __forceinline__ void grid_row(const GridArgs& g, const LevelCtx& lc, 
         *reinterpret_cast<float2*>(g.enc[1] + o) = make_float2(out.z, out.w);
         *reinterpret_cast<float2*>(g.enc[2] + o) = outc;
     } else {
-        constexpr int NT = KIND == GK_HALF3 ? 3 : (KIND == GK_HALF2 ? 2 : 1);
-        constexpr int NW = NT == 3 ? 4 : NT;   // (GK_HALF3: 3 x half2 + one pad word = 16 bytes)
-        typedef uint32_t RowT __attribute__((ext_vector_type(NW)));   // NT x half2
-        __half acc[2 * NT];
+        // tables in the row: 1 (GK_SINGLE, GK_HALF1), 2 (GK_PAIR, GK_HALF2) or 3 (GK_HALF3: 3 x half2 + one pad word = 16 bytes)
+        constexpr bool HALF = KIND == GK_HALF1 || KIND == GK_HALF2 || KIND == GK_HALF3;
+        constexpr int NT = KIND == GK_HALF3 ? 3 : ((KIND == GK_HALF2 || KIND == GK_PAIR) ? 2 : 1);
+        constexpr int NW = HALF ? (NT == 3 ? 4 : NT) : 2 * NT;
+        typedef uint32_t RowT __attribute__((ext_vector_type(NW)));
+        typedef typename std::conditional<HALF, __half, float>::type AccT;   // (fp16 tables: the half accumulator is handed on as fp32, exact)
+        AccT out[HALF ? 2 * NW : NW];
 #pragma unroll
-        for (int ch = 0; ch < 2 * NT; ch++) acc[ch] = __float2half(0.0f);
-        if (grid_corner_rows<1>(g, lc, b, idxs, pos)) {
-            RowT v[8];
-            gather8<RowT, 1, ORDERED>(static_cast<const RowT*>(table) + lc.off0, idxs, v);
-            grid_corner_weights(pos, ws);
-#pragma unroll
-            for (uint32_t idx = 0; idx < 8; idx++) {
-                __half hv[2 * NT];
-                __builtin_memcpy(hv, &v[idx], sizeof(hv));
-#pragma unroll
-                for (int ch = 0; ch < 2 * NT; ch++)   // the reference's half accumulator: addend and sum rounded to fp16 (corner_accumulate<__half>)
-                    acc[ch] = __float2half(__half2float(acc[ch]) + __half2float(__float2half(ws[idx] * __half2float(hv[ch]))));
-            }
-        }
-        *reinterpret_cast<float2*>(enc0 + o) = make_float2(__half2float(acc[0]), __half2float(acc[1]));
-        if constexpr (NT >= 2) *reinterpret_cast<float2*>(g.enc[1] + o) = make_float2(__half2float(acc[2]), __half2float(acc[3]));
-        if constexpr (NT == 3) *reinterpret_cast<float2*>(g.enc[2] + o) = make_float2(__half2float(acc[4]), __half2float(acc[5]));
+        for (int ch = 0; ch < 2 * NT; ch++) out[ch] = AccT(0.0f);
+        if (grid_corner_rows<1>(g, lc, b, idxs, pos)) cell_interp<RowT, HALF, ORDERED>(static_cast<const RowT*>(table) + lc.off0, idxs, pos, out);
+        *reinterpret_cast<float2*>(enc0 + o) = make_float2(to_f32(out[0]), to_f32(out[1]));
+        if constexpr (NT >= 2) *reinterpret_cast<float2*>(g.enc[1] + o) = make_float2(to_f32(out[2]), to_f32(out[3]));
+        if constexpr (NT == 3) *reinterpret_cast<float2*>(g.enc[2] + o) = make_float2(to_f32(out[4]), to_f32(out[5]));
     }
 }
 
@@ -698,12 +624,9 @@ __device__ __forceinline__ void grid_pair_level(const GridArgs& g, const LevelCt
     typedef f32x2 RowT;
     float pos[3];
     uint32_t pg[3], ag[3], bg[3];
+    grid_cell<3>(in, lc.scale, false, pg, pos);   // (a row that is not looked up arrives with in = 0)
 #pragma unroll
-    for (int d = 0; d < 3; d++) {   // (a row that is not looked up arrives with in = 0)
-        pos[d] = fmaf(in[d], lc.scale, 0.5f);
-        const float fl = floorf(pos[d]);
-        pg[d] = (uint32_t)fl;
-        pos[d] -= (float)pg[d];
+    for (int d = 0; d < 3; d++) {
         const uint32_t qg = dpp_swap_pair(pg[d]);
         ag[d] = odd ? qg : pg[d];   // the cell of the pair's even row ...
         bg[d] = odd ? pg[d] : qg;   // ... and of its odd row
@@ -725,9 +648,9 @@ __device__ __forceinline__ void grid_pair_level(const GridArgs& g, const LevelCt
         for (int i = 4; i < 8; i++) v[i] = *(typename GlobalPtr<RowT>::type)(uintptr_t)p[i];
     }
     float ws[8];
-    grid_corner_weights(pos, ws);
+    corner_weights<3>(pos, ws);
     // the eight corners of this lane's row in the reference's order: corner idx = xbit + 2 jk is this lane's load when xbit is its parity, else the partner's
-    uint32_t cw[8][NW];
+    RowT cw[8];
 #pragma unroll
     for (int jk = 0; jk < 4; jk++) {
         uint32_t wa[NW], wb[NW];
@@ -736,17 +659,13 @@ __device__ __forceinline__ void grid_pair_level(const GridArgs& g, const LevelCt
 #pragma unroll
         for (int w = 0; w < NW; w++) {
             const uint32_t sa = dpp_swap_pair(wa[w]), sb = dpp_swap_pair(wb[w]);   // (every lane swaps both: a DPP read needs its source lane active)
-            cw[2 * jk][w] = odd ? sb : wa[w];
-            cw[2 * jk + 1][w] = odd ? wb[w] : sa;
+            cw[2 * jk][w] = __builtin_bit_cast(float, odd ? sb : wa[w]);
+            cw[2 * jk + 1][w] = __builtin_bit_cast(float, odd ? wb[w] : sa);
         }
     }
     const size_t o = ((size_t)level * g.level_stride + b) * 2;
-    float acc[2] = {0.0f, 0.0f};
-#pragma unroll
-    for (uint32_t idx = 0; idx < 8; idx++) {
-        acc[0] = fmaf(ws[idx], __builtin_bit_cast(float, cw[idx][0]), acc[0]);
-        acc[1] = fmaf(ws[idx], __builtin_bit_cast(float, cw[idx][1]), acc[1]);
-    }
+    float acc[NW];
+    cell_chain<RowT, false>(cw, ws, acc);
     const float2 out = make_float2(acc[0], acc[1]);
     if (ok) *reinterpret_cast<float2*>(enc0 + o) = out;
     else if (live) *reinterpret_cast<float2*>(enc0 + o) = make_float2(0.0f, 0.0f);   // outside [0, 1]^3: zeros, as grid_row writes them
@@ -756,22 +675,11 @@ template <int KIND>
 __device__ __forceinline__ void grid_row_at(const GridArgs& g, const LevelCtx& lc, uint32_t level, const void* __restrict__ table, float* __restrict__ enc0, uint32_t b,
                                             const float (&in)[3]) {
     static_assert(KIND == GK_SINGLE, "the one-table fp32 layout");
-    float pos[3], ws[8];
+    float pos[3], acc[2];
     uint32_t pg[3], idxs[8];
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        pos[d] = fmaf(in[d], lc.scale, 0.5f);
-        const float fl = floorf(pos[d]);
-        pg[d] = (uint32_t)fl;
-        pos[d] -= (float)pg[d];
-    }
-    corner_rows_by_kind<1>(lc.kind, g.gridtype, lc.hashmap_size, lc.resolution, pg, idxs);
-    f32x2 v[8];
-    gather8<f32x2, 1, true>(static_cast<const f32x2*>(table) + lc.off0, idxs, v);
-    grid_corner_weights(pos, ws);
-    float acc[2] = {0.0f, 0.0f};
-#pragma unroll
-    for (uint32_t idx = 0; idx < 8; idx++) { acc[0] = fmaf(ws[idx], v[idx].x, acc[0]); acc[1] = fmaf(ws[idx], v[idx].y, acc[1]); }
+    grid_cell<3>(in, lc.scale, false, pg, pos);
+    corner_rows<3, 1>(lc.kind, g.gridtype, false, lc.hashmap_size, lc.resolution, pg, idxs);
+    cell_interp<f32x2, false, true>(static_cast<const f32x2*>(table) + lc.off0, idxs, pos, acc);
     *reinterpret_cast<float2*>(enc0 + ((size_t)level * g.level_stride + b) * 2) = make_float2(acc[0], acc[1]);
 }
 // the row loop of a level-major workgroup in the lane-pair form: levels[0 .. NLV) for every row
@@ -792,15 +700,8 @@ __device__ __forceinline__ void grid_pair_rows(const GridArgs& g, const LevelCtx
 #pragma unroll
             for (int d = 0; d < 3; d++) xyz[d] = g.xyzs[(size_t)b * 3 + d];
             asm volatile("" : "+v"(xyz[0]), "+v"(xyz[1]), "+v"(xyz[2]));   // (one 12-byte request: grid_corner_rows)
-            bool oob = false;
-#pragma unroll
-            for (int d = 0; d < 3; d++) {
-                const float sft = xyz[d] + g.bound;
-                in[d] = g.inv_two_bound != 0.0f ? sft * g.inv_two_bound : sft / g.two_bound;
-                oob |= (in[d] < 0.0f) | (in[d] > 1.0f);
-            }
-            ok = !oob;
-            if (oob) { in[0] = 0.0f; in[1] = 0.0f; in[2] = 0.0f; }
+            ok = unit_cube_of(xyz, g.bound, g.two_bound, g.inv_two_bound, in);
+            if (!ok) { in[0] = 0.0f; in[1] = 0.0f; in[2] = 0.0f; }
         }
         const bool pok = dpp_swap_pair(ok ? 1u : 0u) != 0u;
         const bool okA = odd ? pok : ok, okB = odd ? ok : pok;

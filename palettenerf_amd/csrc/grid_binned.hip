@@ -59,33 +59,18 @@ __device__ __forceinline__ Corners corners_of(const float* __restrict__ inputs, 
                                               uint32_t hashmap_size, uint32_t gridtype, bool align_corners) {
     Corners c;
     c.active = b < B;
-    float pos[3];
+    float in[3], pos[3];
     uint32_t pg[3];
 #pragma unroll
     for (uint32_t d = 0; d < 3; d++) {
-        const float v = c.active ? inputs[(size_t)b * 3 + d] : 0.0f;
-        if (v < 0.0f || v > 1.0f) c.active = false;
-        pos[d] = fmaf(v, scale, align_corners ? 0.0f : 0.5f);
-        const float fl = floorf(pos[d]);
-        pg[d] = (uint32_t)fl;
-        pos[d] -= (float)pg[d];
+        in[d] = c.active ? inputs[(size_t)b * 3 + d] : 0.0f;   // (an inactive lane reads 0)
+        if (in[d] < 0.0f || in[d] > 1.0f) c.active = false;
     }
-#pragma unroll
-    for (uint32_t idx = 0; idx < 8; idx++) {
-        float w = 1.0f;
-        uint32_t pl[3];
-#pragma unroll
-        for (uint32_t d = 0; d < 3; d++) {
-            if ((idx & (1u << d)) == 0) { w *= 1.0f - pos[d]; pl[d] = pg[d]; }
-            else { w *= pos[d]; pl[d] = pg[d] + 1; }
-        }
-        c.w[idx] = w;
-        if (align_corners) c.row[idx] = grid_index<3, 1>(gridtype, true, hashmap_size, resolution, pl);
-    }
+    grid_cell<3>(in, scale, align_corners, pg, pos);
+    corner_weights<3>(pos, c.w);
     c.cell = c.active ? (pg[0] | (pg[1] << 10) | (pg[2] << 20)) : 0xFFFFFFFFu;
-    // the row index per kind of level (grid_core.hpp: dense levels need no `%`, hashed levels with a power-of-two size a mask): the general form's
-    // 32-bit modulo is ~25 instructions per corner, eight corners, in each of the three sweeps
-    if (!align_corners) corner_rows_by_kind<1>(level_kind(gridtype, hashmap_size, resolution), gridtype, hashmap_size, resolution, pg, c.row);
+    // (the row index per kind of level: the general form's modulo in each of the three sweeps is what level_kind spares)
+    corner_rows<3, 1>(level_kind<3>(gridtype, hashmap_size, resolution, align_corners), gridtype, align_corners, hashmap_size, resolution, pg, c.row);
     return c;
 }
 

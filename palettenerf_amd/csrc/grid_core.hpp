@@ -1,4 +1,7 @@
-// grid_core.hpp -- hash-grid indexing / interpolation helpers shared by gridencoder.hip and frame.hip.
+// grid_core.hpp -- the hash-grid lookup's shared pieces: level constants, the corner accumulators of the generic kernels, the eight gathers and the
+// interpolation chain of the D = 3 lookups.  The arithmetic in front of them (unit cube, cell and fraction, row indices, weights) is grid_xside.hpp's.
+// Users: gridencoder.hip (the generic kernels, k_grid_fwd_d3c2 and its pair form), grid_binned.hip (corners_of), frame.hip (grid_row, the lane-pair
+// lookup), occupancy.hip (k_occ_lookup), background.hip (the D = 2 lookup and its gradient).
 #pragma once
 #include "pnr_common.hpp"
 #include "grid_xside.hpp"
@@ -14,57 +17,6 @@ struct LevelParams {
 
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(__half v) { return __half2float(v); }
-
-// reference gridencoder.cu:35-72 (fast_hash + get_grid_index with ch = 0)
-template <uint32_t D, uint32_t C>
-__device__ __forceinline__ uint32_t grid_index(uint32_t gridtype, bool align_corners, uint32_t hashmap_size, uint32_t resolution,
-                                               const uint32_t pg[D]) {
-    constexpr uint32_t primes[7] = {1u, 2654435761u, 805459861u, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
-    uint32_t stride = 1, index = 0;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        if (stride <= hashmap_size) {
-            index += pg[d] * stride;
-            stride *= align_corners ? resolution : (resolution + 1);
-        }
-    }
-    if (gridtype == 0 && stride > hashmap_size) {
-        index = 0;
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) index ^= pg[d] * primes[d];
-    }
-    return (index % hashmap_size) * C;
-}
-
-// How a row index is formed on one level of a D = 3 grid (gridencoder.cu:49-72 evaluated once per level instead of once per corner):
-//   0 the reference's general form (stride test per dimension, hash or tiled, `%`); 1 dense: side^3 <= size, the index is below the size and the
-//   `%` is the identity; 2 hashed with a power-of-two size: a mask.  All three give grid_index's value (tests/test_gpu_ops.py: the D3C2 kernel and
-//   the frame loops against the generic kernel and the oracle, incl. sizes that are neither).  align_corners = false.
-// (level_kind itself: grid_xside.hpp, host + device)
-// the eight corner rows (x CMUL) of the cell whose lower corner is pg
-template <uint32_t CMUL>
-__device__ __forceinline__ void corner_rows_by_kind(uint32_t kind, uint32_t gridtype, uint32_t hashmap_size, uint32_t resolution, const uint32_t* pg /* [3] */,
-                                                    uint32_t* idxs /* [8] */) {
-    if (kind == 1u) {
-        const uint32_t side = resolution + 1u;
-#pragma unroll
-        for (uint32_t idx = 0; idx < 8; idx++)
-            idxs[idx] = ((pg[0] + (idx & 1u)) + (pg[1] + ((idx >> 1) & 1u)) * side + (pg[2] + ((idx >> 2) & 1u)) * side * side) * CMUL;
-    } else if (kind == 2u) {
-        const uint32_t mask = hashmap_size - 1u;
-#pragma unroll
-        for (uint32_t idx = 0; idx < 8; idx++)
-            idxs[idx] = (((pg[0] + (idx & 1u)) ^ ((pg[1] + ((idx >> 1) & 1u)) * 2654435761u) ^ ((pg[2] + ((idx >> 2) & 1u)) * 805459861u)) & mask) * CMUL;
-    } else {
-#pragma unroll
-        for (uint32_t idx = 0; idx < 8; idx++) {
-            uint32_t pl[3];
-#pragma unroll
-            for (uint32_t d = 0; d < 3; d++) pl[d] = pg[d] + ((idx >> d) & 1u);
-            idxs[idx] = grid_index<3, CMUL>(gridtype, false, hashmap_size, resolution, pl);
-        }
-    }
-}
 
 // accumulate one corner: fp32 table -> fmaf chain; fp16 table -> half accumulator with the
 // reference's two roundings (gridencoder.cu:142,165 with scalar_t = at::Half)
@@ -106,6 +58,69 @@ __device__ __forceinline__ void corner_accumulate(__half acc[C], float w, const 
 #pragma unroll
     for (uint32_t ch = 0; ch < C; ch++)
         acc[ch] = __float2half(__half2float(acc[ch]) + __half2float(half_of_product(w, v[ch])));
+}
+
+// The interpolation of one D = 3 cell from its eight rows v, corners in the reference's order 0 .. 7.  A row (RowT) is NW 32-bit words.
+//   !HALF: every word is a float; out[NW] gets the reference's fmaf chains (gridencoder.cu:142,165 with scalar_t = float).
+//   HALF:  every word is a half2; out[2 NW] gets the reference's half accumulator per channel -- every addend and every partial sum rounded to fp16
+//          (scalar_t = at::Half).  The chain is the plain expression, not half_of_product(): here the compiler turns it into v_cvt_pk_f16_f32 +
+//          v_pk_add_f16, which keeps the product's rounding to fp16 a step of its own -- the reference's two roundings -- while the empty statement
+//          of half_of_product() would cost the packed forms (k_grid_fwd_d3c2<__half>: 584 -> 602 instructions).
+//   OutT:  float (a half accumulator is upcast once, exact); a HALF caller that stores or merges halves may take the accumulator as it is (__half).
+template <typename RowT, bool HALF, typename OutT>
+__device__ __forceinline__ void cell_chain(const RowT (&v)[8], const float (&ws)[8], OutT* out /* [HALF ? 2 * NW : NW] */) {
+    constexpr uint32_t NW = sizeof(RowT) / 4;
+    if constexpr (!HALF) {
+#pragma unroll
+        for (uint32_t w = 0; w < NW; w++) out[w] = 0.0f;
+#pragma unroll
+        for (uint32_t idx = 0; idx < 8; idx++) {
+            float fv[NW];
+            __builtin_memcpy(fv, &v[idx], sizeof(fv));
+#pragma unroll
+            for (uint32_t w = 0; w < NW; w++) out[w] = fmaf(ws[idx], fv[w], out[w]);
+        }
+    } else {
+        __half acc[2 * NW];
+#pragma unroll
+        for (uint32_t ch = 0; ch < 2 * NW; ch++) acc[ch] = __float2half(0.0f);
+#pragma unroll
+        for (uint32_t idx = 0; idx < 8; idx++) {
+            __half hv[2 * NW];
+            __builtin_memcpy(hv, &v[idx], sizeof(hv));
+#pragma unroll
+            for (uint32_t ch = 0; ch < 2 * NW; ch++)
+                acc[ch] = __float2half(__half2float(acc[ch]) + __half2float(__float2half(ws[idx] * __half2float(hv[ch]))));
+        }
+#pragma unroll
+        for (uint32_t ch = 0; ch < 2 * NW; ch++) {
+            if constexpr (sizeof(OutT) == 2) out[ch] = acc[ch]; else out[ch] = __half2float(acc[ch]);
+        }
+    }
+}
+
+// One D = 3 cell: the eight gathers, the weights, the chain.  RowT = one table row (NW words: f32x2, f32x4 or NW x uint32 of half2), tab = the
+// level's first row, idxs = corner_rows' indices, frac = grid_cell's fraction.
+// The eight gathers go out first, back to back, and the weights are formed while they are in flight: every address exists before the first load
+// and every load returns into registers of its own (load8_fresh, pnr_common.hpp), and nothing is scheduled across the end of the group.  Left to
+// itself the compiler does this too -- until it is asked to keep the kernel within a register budget (amdgpu_waves_per_eu, which the frame loop's
+// hosted tail needs): then it forms the weights first and threads the loads between the address arithmetic, and the frame loop's lego lookup
+// launch takes 76 instead of 66 us with the very same instructions.  ORDERED = false (the hosted tail's own few rows): the compiler's order.
+template <typename RowT, bool HALF, bool ORDERED, typename OutT>
+__device__ __forceinline__ void cell_interp(const RowT* tab, const uint32_t (&idxs)[8], const float (&frac)[3], OutT* out /* [HALF ? 2 * NW : NW] */) {
+    const RowT* p[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) p[i] = tab + idxs[i];
+    RowT v[8];
+    if constexpr (ORDERED) {
+        load8_fresh(p, v);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++) v[i] = *p[i];
+    }
+    float ws[8];
+    corner_weights<3>(frac, ws);
+    cell_chain<RowT, HALF>(v, ws, out);
 }
 
 // 1 / v when v is a power of two (then x / v == x * (1 / v) bit for bit for every finite x that does not end subnormal), else 0: "divide"

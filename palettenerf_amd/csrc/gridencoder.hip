@@ -51,28 +51,16 @@ __global__ void __launch_bounds__(256) k_grid_fwd(const float* __restrict__ inpu
 
     float pos[D];
     uint32_t pg[D];
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        pos[d] = fmaf(in[d], scale, align_corners ? 0.0f : 0.5f);
-        const float fl = floorf(pos[d]);
-        pg[d] = (uint32_t)fl;
-        pos[d] -= (float)pg[d];
-    }
+    grid_cell<D>(in, scale, align_corners, pg, pos);
 
     // issue all 2^D gathers first (independent loads in flight), then reduce in the reference's order
     uint32_t idxs[1u << D];
     float ws[1u << D];
 #pragma unroll
     for (uint32_t idx = 0; idx < (1u << D); idx++) {
-        float w = 1.0f;
         uint32_t pl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            if ((idx & (1u << d)) == 0) { w *= 1.0f - pos[d]; pl[d] = pg[d]; }
-            else { w *= pos[d]; pl[d] = pg[d] + 1; }
-        }
-        ws[idx] = w;
-        idxs[idx] = grid_index<D, C>(gridtype, align_corners, hashmap_size, resolution, pl);
+        ws[idx] = corner_point<D>(pg, pos, idx, pl);
+        idxs[idx] = grid_index<D, C>(gridtype, align_corners, hashmap_size, resolution, pl);   // (any D: the general form)
     }
     T acc[C];
 #pragma unroll
@@ -126,7 +114,9 @@ __global__ void __launch_bounds__(256) k_grid_fwd(const float* __restrict__ inpu
 }
 
 // The lookup every shipped configuration issues (D = 3, C = 2, no dy_dx; fp32 or fp16 table): the same cell, corner order and fmaf / half
-// chains as k_grid_fwd<T, 3, 2> above -- bit for bit -- with what the frame loop's lookup (frame.hip: grid_row / gather8) found:
+// chains as k_grid_fwd<T, 3, 2> above -- bit for bit -- with what the frame loop's lookup (frame.hip: grid_row; grid_core.hpp: cell_interp) found.
+// (This kernel and its pair form below keep their own text of the cell path: through the shared helpers the fp32 lookup of 2^20 points took 368.5
+// instead of 366.7 us and the pair lookup 626.2 instead of 625.2 us, outside the run-to-run spread; profiles/isa_identity/README.md.)
 //   * all eight row addresses exist before the first load and every load returns into registers of its own (load8_fresh);
 //   * the finest levels -- scattered rows, five times the time of a dense level -- are dispatched first (blockIdx.y = 0 is level L-1),
 //     the dense ones fill the launch's tail;
@@ -277,7 +267,7 @@ k_grid_fwd_d3c2_pair(const float* __restrict__ inputs, const f32x4* __restrict__
             idxs[i] = grid_index<3, 1>(gridtype, true, hashmap_size, resolution, pl);
         }
     } else {
-        corner_rows_by_kind<1>(level_kind(gridtype, hashmap_size, resolution), gridtype, hashmap_size, resolution, pg, idxs);
+        corner_rows<3, 1>(level_kind<3>(gridtype, hashmap_size, resolution), gridtype, false, hashmap_size, resolution, pg, idxs);
     }
     const f32x4* p[8];
 #pragma unroll
@@ -324,12 +314,9 @@ __global__ void __launch_bounds__(256) k_grid_bwd(const T* __restrict__ grad, co
     uint32_t pg[D];
 #pragma unroll
     for (uint32_t d = 0; d < D; d++) {
-        const float v = active ? inputs[(size_t)b * D + d] : 0.0f;
+        const float v = active ? inputs[(size_t)b * D + d] : 0.0f;   // (an inactive lane reads 0)
         if (v < 0.0f || v > 1.0f) active = false;  // grad_grid is zero-initialised by the caller
-        pos[d] = fmaf(v, scale, align_corners ? 0.0f : 0.5f);
-        const float fl = floorf(pos[d]);
-        pg[d] = (uint32_t)fl;
-        pos[d] -= (float)pg[d];
+        grid_cell<1>(&v, scale, align_corners, pg + d, pos + d);
     }
     if (!COMBINE && !active) return;
     T g[C];
@@ -342,7 +329,7 @@ __global__ void __launch_bounds__(256) k_grid_bwd(const T* __restrict__ grad, co
         float w = 1.0f;
         uint32_t pl[D];
 #pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
+        for (uint32_t d = 0; d < D; d++) {   // (corner_point's loop, written out: through the helper five instantiations take one vector register more)
             if ((idx & (1u << d)) == 0) { w *= 1.0f - pos[d]; pl[d] = pg[d]; }
             else { w *= pos[d]; pl[d] = pg[d] + 1; }
         }

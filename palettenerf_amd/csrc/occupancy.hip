@@ -206,9 +206,8 @@ __global__ void __launch_bounds__(256) k_occ_points(OccGeom g, uint32_t first, u
 }
 
 // gridencoder.cu:75-175 for D = 3, C = 2, fp32 with GridEncoder.forward's (x + bound) / (2 bound) folded in (gridencoder/grid.py:142):
-// the loop of k_frame_grid over the sweep's points.  grid = (blocks, levels): a block column works on one level.
-// (round 4: what the frame lookup and the D3C2 op learnt -- finest levels dispatched first, the row index formed per kind of level, all eight
-// addresses before the first load and fresh destination registers, the exact reciprocal for power-of-two bounds; same bits as before.)
+// the loop of k_frame_grid over the sweep's points, through the same cell path (grid_core.hpp).  grid = (blocks, levels): a block column works on
+// one level, the finest levels dispatched first.
 __global__ void __launch_bounds__(256) k_occ_lookup(const float4* __restrict__ pts, uint32_t count, const float* __restrict__ table,
                                                     const int32_t* __restrict__ offsets, LevelParams lp, float* __restrict__ enc, uint32_t level_stride,
                                                     float bound, float two_bound, float inv_two_bound, uint32_t gridtype) {
@@ -218,48 +217,20 @@ __global__ void __launch_bounds__(256) k_occ_lookup(const float4* __restrict__ p
     const f32x2* g = reinterpret_cast<const f32x2*>(table) + off0;
     const float scale = lp.scale[level];
     const uint32_t resolution = lp.resolution[level];
-    const uint32_t kind = level_kind(gridtype, hashmap_size, resolution);
+    const uint32_t kind = level_kind<3>(gridtype, hashmap_size, resolution);
     for (uint32_t b = blockIdx.x * 256 + threadIdx.x; b < count; b += gridDim.x * 256) {
         const float4 p = pts[b];
         if (__float_as_int(p.w) < 0) continue;
         const float x[3] = {p.x, p.y, p.z};
-        float in[3];
-        bool oob = false;
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const float sft = x[d] + bound;
-            in[d] = inv_two_bound != 0.0f ? sft * inv_two_bound : sft / two_bound;
-            oob |= (in[d] < 0.0f) | (in[d] > 1.0f);
-        }
-        float2 out = make_float2(0.0f, 0.0f);
-        if (!oob) {
+        float in[3], acc[2] = {0.0f, 0.0f};
+        if (unit_cube_of(x, bound, two_bound, inv_two_bound, in)) {
             float pos[3];
-            uint32_t pg[3];
-#pragma unroll
-            for (int d = 0; d < 3; d++) {
-                pos[d] = fmaf(in[d], scale, 0.5f);
-                const float fl = floorf(pos[d]);
-                pg[d] = (uint32_t)fl;
-                pos[d] -= (float)pg[d];
-            }
-            uint32_t idxs[8];
-            corner_rows_by_kind<1>(kind, gridtype, hashmap_size, resolution, pg, idxs);
-            const f32x2* ptr8[8];
-#pragma unroll
-            for (int i = 0; i < 8; i++) ptr8[i] = g + idxs[i];
-            f32x2 v[8];
-            load8_fresh(ptr8, v);
-            float acc[2] = {0.0f, 0.0f};
-#pragma unroll
-            for (uint32_t idx = 0; idx < 8; idx++) {
-                float w = 1.0f;
-#pragma unroll
-                for (uint32_t d = 0; d < 3; d++) w *= (idx & (1u << d)) ? pos[d] : 1.0f - pos[d];
-                acc[0] = fmaf(w, v[idx].x, acc[0]); acc[1] = fmaf(w, v[idx].y, acc[1]);
-            }
-            out = make_float2(acc[0], acc[1]);
+            uint32_t pg[3], idxs[8];
+            grid_cell<3>(in, scale, false, pg, pos);
+            corner_rows<3, 1>(kind, gridtype, false, hashmap_size, resolution, pg, idxs);
+            cell_interp<f32x2, false, true>(g, idxs, pos, acc);
         }
-        *reinterpret_cast<float2*>(enc + ((size_t)level * level_stride + b) * 2) = out;
+        *reinterpret_cast<float2*>(enc + ((size_t)level * level_stride + b) * 2) = make_float2(acc[0], acc[1]);
     }
 }
 

@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Is the gfx950 device code of every csrc/*.hip the same at two revisions?  Each unit is compiled device-only to assembly text with the
-product's flags (build.FLAGS, the unit's UNIT_FLAGS) and the two texts are compared byte for byte.  No GPU is needed.
+product's flags (build.FLAGS, the unit's UNIT_FLAGS) and the two texts are compared byte for byte.  A unit whose text differs gets a per-kernel
+summary of what decides occupancy -- vector registers, scratch, LDS -- and of the instruction count, old against new.  No GPU is needed.
 usage: isa_identity.py [OLD [NEW]]   (git revisions; default HEAD~1 against the working tree).  Exit status 1 if any unit differs."""
 import concurrent.futures
 import io
 import os
+import re
+import shutil
 import subprocess
 import sys
 import tarfile
@@ -44,6 +47,50 @@ def first_difference(a, b):
     return f"line {n + 1}: {(la[n] if n < len(la) else b'<end of file>').decode(errors='replace').strip()!r} -> {(lb[n] if n < len(lb) else b'<end of file>').decode(errors='replace').strip()!r}"
 
 
+FIELDS = ("next_free_vgpr", "private_segment_fixed_size", "group_segment_fixed_size")
+
+
+def kernels(text):
+    """{kernel: (VGPRs, scratch bytes, LDS bytes, instructions)} of one unit's assembly text: the three .amdhsa_ fields of the kernel's
+    descriptor block and the instruction lines between the kernel's label and that block."""
+    lines = text.decode(errors="replace").split("\n")
+    label = {m.group(1): i for i, ln in enumerate(lines) if (m := re.match(r"(\w+):\s", ln))}
+    out = {}
+    for i, ln in enumerate(lines):
+        m = re.match(r"\s*\.amdhsa_kernel (\w+)", ln)
+        if not m or m.group(1) not in label:
+            continue
+        end = next(j for j in range(i, len(lines)) if lines[j].strip() == ".end_amdhsa_kernel")
+        desc = dict(ln.split()[:2] for ln in lines[i + 1:end] if len(ln.split()) >= 2)
+        body = sum(1 for ln in lines[label[m.group(1)] + 1:i] if re.match(r"\s+[a-z]\w*(\s|$)", ln))
+        out[m.group(1)] = tuple(int(desc[".amdhsa_" + f]) for f in FIELDS) + (body,)
+    return out
+
+
+def demangled(names):
+    filt = shutil.which("c++filt") or shutil.which("llvm-cxxfilt")
+    if not filt or not names:
+        return {n: n for n in names}
+    plain = subprocess.run([filt], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+    return dict(zip(names, plain))
+
+
+def summary(old_text, new_text):
+    """One line per kernel whose resources or instruction count moved (and how many did not): VGPRs, scratch, LDS, instructions, old -> new."""
+    old, new = kernels(old_text), kernels(new_text)
+    names = sorted(set(old) | set(new))
+    plain = demangled(names)
+    same = 0
+    for n in names:
+        if old.get(n) == new.get(n):
+            same += 1
+            continue
+        a, b = old.get(n), new.get(n)
+        cols = [f"{x[k] if x else '-'}" for k in range(4) for x in (a, b)]
+        print("    vgpr {} -> {}  scratch {} -> {}  lds {} -> {}  instructions {} -> {}  {}".format(*cols, re.sub(r"^pnr::|\(.*$", "", plain[n].replace("void ", ""))))
+    print(f"    ({same} of {len(names)} kernels: same registers, scratch, LDS and instruction count)")
+
+
 def main():
     old_rev = sys.argv[1] if len(sys.argv) > 1 else "HEAD~1"
     new_rev = sys.argv[2] if len(sys.argv) > 2 else None
@@ -63,6 +110,8 @@ def main():
         else:
             verdict, differ = "differs: " + first_difference(text["old", u], text["new", u]), differ + 1
         print(f"{u:16s} {verdict}")
+        if verdict.startswith("differs"):
+            summary(text["old", u], text["new", u])
     return 1 if differ else 0
 
 

@@ -564,6 +564,30 @@ def test_grid_encode_tiled_and_align_corners(cuda):
         np.testing.assert_array_equal(host(out), oracle.grid_encode_forward(x, emb, offsets, pls, 8, gridtype=gridtype, align_corners=ac))
 
 
+@pytest.mark.parametrize("gridtype", ["hash", "tiled"])
+def test_grid_pair_lookup_with_align_corners_is_bit_identical_to_two_lookups(cuda, gridtype):
+    """fused.grid_encode_raw_pair with align_corners=True -- the pair kernel's own branch, which no other test reaches -- against two single lookups
+    and the oracle, bit for bit; the shapes of test_grid_encode_tiled_and_align_corners (6 levels, H = 8, 2^10 rows, 3001 points: the faces 0 and 1
+    and points an epsilon outside among them)."""
+    from palettenerf_amd import fused
+    rng = np.random.default_rng(24)
+    torch.manual_seed(24)
+    mk = lambda: gridencoder.GridEncoder(input_dim=3, num_levels=6, level_dim=2, per_level_scale=2, base_resolution=8, log2_hashmap_size=10, gridtype=gridtype,
+                                         align_corners=True).to(cuda)
+    ea, eb = mk(), mk()
+    for e in (ea, eb):
+        e.embeddings.data.uniform_(-0.5, 0.5)
+    assert fused.pairable(ea, eb)
+    _, _, _, x = _grid_setup(rng, 6, 8, 10, None, 2, 3001)
+    x01 = dev(x, cuda)
+    a, b = fused.grid_encode_raw_pair(ea, eb, x01)
+    for got, e in ((a, ea), (b, eb)):
+        assert torch.equal(got, fused.grid_encode_raw(e, x01))
+        want = oracle.grid_encode_forward(x, host(e.embeddings.detach()), host(e.offsets), 2.0, 8, gridtype=e.gridtype_id, align_corners=True, raw=True)
+        np.testing.assert_array_equal(host(got), want)
+    assert float(a[:, 3].abs().max()) == 0.0 and float(b[:, 4].abs().max()) == 0.0      # the two points outside [0, 1]^3
+
+
 def test_grid_encode_align_corners_wraps_the_corner_beyond_a_dense_level(cuda):
     """align_corners: side == resolution, so an input of exactly 1.0 puts the +1 corner at index side on that axis and (z == 1.0) the row index at
     or beyond side^3 -- the reference wraps it with `% hashmap_size` (gridencoder.cu:49-72).  Its weight is 0, so a kernel that skips the wrap on
