@@ -1134,6 +1134,45 @@ int pnr_train_batch(const pnr_train_batch_args* args, pnr_stream_t stream);
 int pnr_error_map_update(float* error_map, uint32_t cells, const int64_t* view_index, const int64_t* inds_coarse, const float* loss_ray, uint32_t B,
                          uint32_t N, pnr_stream_t stream);
 
+/* ---- Stylizer fit: the GUI's "optimize" step as one launch (additive, ABI 10; csrc/stylizer.hip) ----
+ * pnr_stylizer_fit replaces the optimisation loop of palette/gui.py:153-194: `iters` steps of SGD with momentum on the Stylizer's dI [nb],
+ * dP [nb,3] and ddelta [nb,3,3] (palette/renderer.py:150-183) against M picked colours -- ONE launch of one wave, the parameters on chip for
+ * the whole run, every sum over the points in a fixed order (bit-for-bit reproducible).  All arrays fp32 on the device.  Per iteration:
+ *   s_n = softplus(radiance_n)  (log1p(exp(r)), r itself past 20),   I_np = max(s_n + dI_p, 0),   C_npj = palette_pj + dP_pj + sum_i offsets_npi ddelta_pij
+ *   rgb_nj = sum_p omega_np clamp(I_np C_npj, 0, 1) (+ view_dep_nj),   e = rgb - target
+ *   loss = sum e^2 + lambda_arap (sum_p |D_p D_p^T - 1|_F^2 + sum dP^2)            (D_p = ddelta_p)
+ *   the gradient of loss as torch's autograd takes it (clamp: bounds inclusive; max(., 0): zero included)
+ *   buf = momentum buf + grad  (the first step of a run without momentum buffers: buf = grad),   x -= lr[t] buf
+ *   radiance [M] raw; omega [M,nb]; offsets [M,nb,3]; palette [nb,3], the caller's basis_color.clamp(0,1); target [M,3]; view_dep [M,3] optional,
+ *   added to the colour as a constant; lr [iters], the learning rate of every iteration (the scheduler's values, narrowed to fp32 by the caller).
+ *   dI, dP, ddelta: in/out.  mom_dI, mom_dP, mom_ddelta: optional (all three or none), written back when given; has_momentum != 0 continues from them.
+ *   trace [iters,2], optional: (total loss, regulariser) at the parameters BEFORE that iteration's update, as the reference prints them.
+ * PNR_ERR_UNSUPPORTED: num_basis outside 4 .. PNR_MAX_BASIS, M > PNR_STYLIZER_MAX_POINTS, iters > PNR_STYLIZER_MAX_ITERS (a longer run is several
+ * launches, continued through the momentum buffers: no single kernel runs for long).  Then M == 0 or iters == 0 is PNR_OK and nothing is touched.
+ * PNR_ERR_INVALID: a NULL struct or required pointer, one or two of the three momentum buffers, has_momentum without them.  All before any launch. */
+#define PNR_STYLIZER_MAX_POINTS 512
+#define PNR_STYLIZER_MAX_ITERS 10000
+typedef struct pnr_stylizer_fit_args {
+    uint32_t M, num_basis, iters;
+    const float* radiance;
+    const float* omega;
+    const float* offsets;
+    const float* palette;
+    const float* target;
+    const float* view_dep;
+    float* dI;
+    float* dP;
+    float* ddelta;
+    float* mom_dI;
+    float* mom_dP;
+    float* mom_ddelta;
+    int has_momentum;
+    const float* lr;
+    float momentum, lambda_arap;
+    float* trace;
+} pnr_stylizer_fit_args;
+int pnr_stylizer_fit(const pnr_stylizer_fit_args* args, pnr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

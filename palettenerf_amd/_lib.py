@@ -131,6 +131,7 @@ SIGNATURES = {
     "pnr_frame_metrics": [_ptr, _ptr],
     "pnr_train_batch": [_ptr, _ptr],
     "pnr_error_map_update": [_ptr, _u32, _ptr, _ptr, _ptr, _u32, _u32, _ptr],
+    "pnr_stylizer_fit": [_ptr, _ptr],
 }
 _RESTYPES = {"pnr_frame_metrics_workspace_bytes": _u64, "pnr_mesh_workspace_bytes": _u64, "pnr_lattice_density_workspace_bytes": _u64, "pnr_occupancy_workspace_bytes": _u64, "pnr_occupancy_samples": _u32, "pnr_adam_max_tensors": _u32, "pnr_error_string": ctypes.c_char_p, "pnr_scan_scratch_bytes": _u64, "pnr_nerf_field_packed_bytes": _u64, "pnr_occupancy_mip_bytes": _u64, "pnr_nerf_frame_workspace_bytes": _u64, "pnr_palette_field_packed_bytes": _u64, "pnr_palette_frame_workspace_bytes": _u64,
              "pnr_palette_aux_channels": _u32, "pnr_linear_wgrad_workspace_bytes": _u64, "pnr_grid_backward_binned_workspace_bytes": _u64,
@@ -294,6 +295,17 @@ class TrainBatchArgs(ctypes.Structure):
                    ("hist_weights", _ptr)]
                 + [(n, _u32) for n in ("num_basis", "Sr", "Sg", "Sb")] + [("hist_stride", _u64 * 4), ("srgb_to_linear", _int)]
                 + [(n, _ptr) for n in ("rays_o", "rays_d", "pixels", "gt_rgb", "gt_weights", "gt_clip")])
+
+
+STYLIZER_MIN_BASIS, STYLIZER_MAX_POINTS, STYLIZER_MAX_ITERS = 4, 512, 10000   # PNR_STYLIZER_MAX_POINTS, PNR_STYLIZER_MAX_ITERS
+
+
+class StylizerFitArgs(ctypes.Structure):
+    """Mirror of `pnr_stylizer_fit_args` (include/pnr.h)."""
+    _fields_ = ([(n, _u32) for n in ("M", "num_basis", "iters")]
+                + [(n, _ptr) for n in ("radiance", "omega", "offsets", "palette", "target", "view_dep", "dI", "dP", "ddelta", "mom_dI", "mom_dP",
+                                       "mom_ddelta")]
+                + [("has_momentum", _int), ("lr", _ptr), ("momentum", _f32), ("lambda_arap", _f32), ("trace", _ptr)])
 
 
 _lib = None

@@ -272,7 +272,9 @@ def viewer_frame(model, pose, intrinsics, W, H, bg_color=None, spp=1, downscale=
     else spp` (the frames of a still camera are jittered and averaged; the native frame loop takes the jitter), then ONE launch (present_frame) for
     the clamp, the nearest upsampling to H x W, linear->sRGB for linear-colour scenes, PaletteNeRF's xyz / clip_feat pick maps and -- with `accum` --
     the running mean of gui.py:225-231.  Returns device tensors: image [H,W,3], depth [H,W], for a PaletteNeRF model also xyz [H,W,3] and clip_feat
-    [H,W,clip_dim], and `frame`, the model's own result dict; `.cpu()` is the caller's.  Wrap the call in torch.autocast for the reference's -O mode."""
+    [H,W,clip_dim], and `frame`, the model's own result dict; `.cpu()` is the caller's.  Wrap the call in torch.autocast for the reference's -O mode.
+    Style transfer (palette/gui.py:153-194): pick points from `xyz`, `model.stylizer = stylize.fit_stylizer(model, points, colors)`, and the next
+    gui_mode frame is stylised."""
     from . import rays as prays
     rH, rW = int(H * downscale), int(W * downscale)
     if rH < 1 or rW < 1:

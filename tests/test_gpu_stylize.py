@@ -1,0 +1,197 @@
+"""pnr_stylizer_fit on the GPU against the float64 statement of tests/stylizer_reference.py.
+
+Every bound is 4 x the error of the fp32 per-op formulation (Stylizer.forward / ARAP_loss under autograd, torch's SGD, run on the GPU here) on
+the same inputs against the same float64 numbers -- this project's margin for another summation order of the same fp32 arithmetic.  Each test
+prints its figures before it asserts; profiles/stylize/README.md records them."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from palettenerf_amd import renderer, stylize
+from tests import stylizer_reference as ref
+
+pytestmark = pytest.mark.gpu
+
+LAMBDA = 0.1
+CAP = 512
+GRADIENT_CASES = [(1, 4, "mild"), (3, 4, "mild"), (5, 8, "mild"), (17, 5, "hard"), (64, 4, "hard"), (65, 10, "hard"), (130, 8, "hard"), (CAP, 10, "hard")]
+RUN_CASES = [(1, 4, "mild"), (3, 4, "mild"), (5, 8, "mild"), (3, 4, "hard"), (17, 5, "hard"), (64, 4, "hard")]
+SHORT_CASES = [(130, 8, "hard"), (CAP, 10, "hard")]
+
+
+@pytest.fixture
+def launch_only(monkeypatch):
+    """The per-op loop is not an answer in the kernel's tests."""
+    def refuse(*a, **k):
+        raise AssertionError("fit_stylizer fell back to the per-op loop")
+    monkeypatch.setattr(stylize, "fit_stylizer_per_op", refuse)
+
+
+def kwargs(inp):
+    return dict(radiance=inp["radiance"], omega=inp["omega"], offsets=inp["offsets"], palette=inp["palette"], colors=inp["target"], view_dep=inp["view_dep"])
+
+
+def fit(inp, iters, **kw):
+    return stylize.fit_stylizer_from_inputs(**kwargs(inp), iters=iters, return_trace=True, **kw)
+
+
+def per_op(inp, iters, **kw):
+    st = renderer.Stylizer(types.SimpleNamespace(num_basis=inp["omega"].shape[1])).to(inp["omega"].device)
+    bufs, trace = stylize.fit_stylizer_per_op(st, inp["radiance"], inp["omega"], inp["offsets"], inp["palette"], inp["target"], iters,
+                                              view_dep=inp["view_dep"], want_trace=True, **kw)
+    return st, trace, bufs
+
+
+def same(a, b):
+    return all(torch.equal(x, y) for x, y in zip(stylize._params(a), stylize._params(b)))
+
+
+@pytest.mark.parametrize("M,nb,regime", GRADIENT_CASES)
+def test_one_iteration_is_the_float64_gradient(cuda, launch_only, M, nb, regime):
+    """After one iteration from the initial state the momentum buffer IS the gradient and x1 = x0 - lr * buffer in fp32, exactly -- so
+    -(x1 - x0) / lr is the gradient up to that one rounding of x1 (half an ulp of 1 on ddelta's diagonal, i.e. 3e-5 of gradient at lr = 1e-3,
+    which would drown what is being compared; hence the buffer is what is held against float64, and the update is checked to the bit)."""
+    inp64 = ref.make_inputs(M, nb, regime)
+    inp = ref.as_fp32(inp64, cuda)
+    want, _, _ = ref.autograd_gradient(ref.initial_params(nb), inp64, LAMBDA)
+    st32 = renderer.Stylizer(types.SimpleNamespace(num_basis=nb)).to(cuda)
+    rgbs = st32(inp["radiance"], inp["omega"], inp["palette"], inp["offsets"])
+    loss = ((rgbs - inp["target"]) ** 2).sum() + st32.ARAP_loss() * LAMBDA + (st32.dP ** 2).sum() * LAMBDA
+    E = ref.deviation(torch.autograd.grad(loss, stylize._params(st32)), want)
+    st, _, state = fit(inp, 1, total_iters=1000)
+    dev = ref.deviation(state["momentum"], want)
+    print(f"gradient M={M} nb={nb} {regime}: per-op E={E:.3e} kernel={dev:.3e} scale={max(float(w.abs().max()) for w in want):.3e}")
+    lr = np.float32(stylize.lr_table(1)[0])
+    for x1, x0, b in zip(stylize._params(st), ref.initial_params(nb, torch.float32), state["momentum"]):
+        step = x0.numpy().reshape(-1) - lr * b.cpu().numpy().reshape(-1)
+        assert step.dtype == np.float32 and np.array_equal(x1.detach().cpu().numpy().reshape(-1), step)
+    assert dev <= 4 * E
+
+
+@pytest.mark.parametrize("M,nb,regime", RUN_CASES)
+def test_a_full_run_follows_the_float64_loop(cuda, launch_only, monkeypatch, M, nb, regime):
+    inp64, want, trace64, _ = ref.reference_run(M, nb, regime)
+    inp = ref.as_fp32(inp64, cuda)
+    st, trace, state = fit(inp, 1000)
+    monkeypatch.undo()
+    st32, trace32, _ = per_op(inp, 1000)
+    E, Et = ref.deviation(stylize._params(st32), want), float((trace32.double().cpu() - trace64).abs().max())
+    dev, devt = ref.deviation(stylize._params(st), want), float((trace.double().cpu() - trace64).abs().max())
+    print(f"run M={M} nb={nb} {regime}: per-op E={E:.3e} kernel={dev:.3e}; trace per-op={Et:.3e} kernel={devt:.3e}; loss {float(trace64[0, 0]):.4f} -> {float(trace64[-1, 0]):.4f}")
+    assert state["iters"] == 1000 and trace.shape == (1000, 2)
+    assert E <= 1e-3                       # the condition: past it the trajectories are chaotic and nothing is being compared
+    assert dev <= 4 * E and devt <= 4 * Et
+
+
+@pytest.mark.parametrize("M,nb,regime", SHORT_CASES)
+def test_fifty_small_steps_at_large_m_follow_the_float64_loop(cuda, M, nb, regime):
+    """With the default learning rate M = 130 is past the condition and M = 1000 diverges, so the shapes with several trips per lane run 50
+    iterations at lr = 1e-4."""
+    inp64, want, trace64, _ = ref.reference_run(M, nb, regime, iters=50, lr=1e-4)
+    inp = ref.as_fp32(inp64, cuda)
+    st32, trace32, _ = per_op(inp, 50, lr=1e-4, total_iters=50)
+    E, Et = ref.deviation(stylize._params(st32), want), float((trace32.double().cpu() - trace64).abs().max())
+    st, trace, _ = fit(inp, 50, lr=1e-4)
+    dev, devt = ref.deviation(stylize._params(st), want), float((trace.double().cpu() - trace64).abs().max())
+    print(f"short M={M} nb={nb} {regime}: per-op E={E:.3e} kernel={dev:.3e}; trace per-op={Et:.3e} kernel={devt:.3e}")
+    assert not same(st, st32) or E == 0          # the launch ran, not the loop
+    assert E <= 1e-3 and dev <= 4 * E and devt <= 4 * Et
+
+
+def test_view_dep_is_added_as_a_constant(cuda, launch_only, monkeypatch):
+    inp64, want, trace64, _ = ref.reference_run(17, 5, "hard", view_dep=True)
+    inp = ref.as_fp32(inp64, cuda)
+    st, trace, _ = fit(inp, 1000)
+    _, plain, _, _ = ref.reference_run(17, 5, "hard")
+    monkeypatch.undo()
+    st32, trace32, _ = per_op(inp, 1000)
+    E, dev = ref.deviation(stylize._params(st32), want), ref.deviation(stylize._params(st), want)
+    Et, devt = float((trace32.double().cpu() - trace64).abs().max()), float((trace.double().cpu() - trace64).abs().max())
+    print(f"view_dep M=17 nb=5 hard: per-op E={E:.3e} kernel={dev:.3e}; trace per-op={Et:.3e} kernel={devt:.3e}; distance to the run without view_dep {ref.deviation(want, plain):.3e}")
+    assert ref.deviation(want, plain) > 1e-2      # the term matters
+    assert E <= 1e-3 and dev <= 4 * E and devt <= 4 * Et
+
+
+def test_runs_are_reproducible_bit_for_bit(cuda, launch_only):
+    inp = ref.as_fp32(ref.make_inputs(70, 5, "hard", seed=2), cuda)        # two trips, the second partial
+    a, trace_a, state_a = fit(inp, 1000)
+    b, trace_b, state_b = fit(inp, 1000)
+    assert same(a, b) and torch.equal(trace_a, trace_b) and all(torch.equal(x, y) for x, y in zip(state_a["momentum"], state_b["momentum"]))
+    assert bool(torch.isfinite(trace_a).all()) and float(trace_a[-1, 0]) < float(trace_a[0, 0])
+    # 600 + 400 on the schedule of 1000
+    c, trace_c, state_c = fit(inp, 600, total_iters=1000)
+    assert state_c["iters"] == 600 and not same(a, c)
+    c, trace_d, state_d = fit(inp, 400, stylizer=c, state=state_c)
+    assert state_d["iters"] == 1000 and same(a, c) and torch.equal(torch.cat([trace_c, trace_d]), trace_a)
+    assert all(torch.equal(x, y) for x, y in zip(state_a["momentum"], state_d["momentum"]))
+    # without a trace buffer
+    d = stylize.fit_stylizer_from_inputs(**kwargs(inp), iters=1000)
+    assert same(a, d)
+    # on another stream
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        e, trace_e, _ = fit(inp, 1000)
+    s.synchronize()
+    assert same(a, e) and torch.equal(trace_a, trace_e)
+
+
+def test_the_switch_and_the_limits_give_the_per_op_loop(cuda, monkeypatch):
+    inp = ref.as_fp32(ref.make_inputs(9, 4, "mild", seed=4), cuda)
+    want, want_trace, _ = per_op(inp, 40, total_iters=40)
+    launched, _, _ = fit(inp, 40)
+    monkeypatch.setattr(stylize, "enabled", False)
+    got, trace, state = fit(inp, 40)
+    assert same(got, want) and torch.equal(trace, want_trace) and state["iters"] == 40
+    assert not same(got, launched) and ref.deviation(stylize._params(launched), [p.detach().double().cpu() for p in stylize._params(want)]) < 1e-4
+    monkeypatch.setattr(stylize, "enabled", True)
+    big = ref.as_fp32(ref.make_inputs(CAP + 1, 4, "mild"), cuda)            # past the entry's cap: PNR_ERR_UNSUPPORTED, then the loop
+    want, _, _ = per_op(big, 3, lr=1e-4, total_iters=3)
+    got, _, _ = fit(big, 3, lr=1e-4)
+    assert same(got, want)
+
+
+def test_a_fitted_stylizer_reaches_the_next_native_frame(cuda, golden_dir, launch_only):
+    from palettenerf_amd.fused import PaletteFieldFused
+    from tests.test_gpu_frames import frame_rays, load, put_scene
+    from tests.test_host_logic import _extra_model
+    g = load(golden_dir, "frame_palette_style_a")
+    opt, m = _extra_model(g)
+    m = m.to(cuda).eval()
+    put_scene(m, cuda)
+    ro, rd = frame_rays(g, cuda)
+    kw = dict(dt_gamma=float(g["dt_gamma"]), perturb=False, max_steps=1024, T_thresh=1e-4, gui_mode=True)
+    m.march_mode, m.fused_field = "native", True
+    m._fused = PaletteFieldFused(m)
+    gen = torch.Generator().manual_seed(9)
+    points = (torch.rand(12, 3, generator=gen) - 0.5).to(cuda)
+    colors = torch.rand(12, 3, generator=gen)
+
+    def frame():
+        with torch.no_grad():
+            return m.render(ro, rd, **kw)["image"].clone()
+
+    def through_state_dict(st):
+        fresh = renderer.Stylizer(opt).to(cuda)
+        fresh.load_state_dict(st.state_dict())
+        return fresh
+
+    plain = frame()
+    st = stylize.fit_stylizer(m, points, colors, iters=100)
+    assert isinstance(st, renderer.Stylizer) and st.dI.device.type == "cuda" and float(st.dP.abs().max()) > 0
+    m.stylizer = st
+    first = frame()
+    assert not torch.equal(first, plain)
+    m.stylizer = through_state_dict(st)
+    assert torch.equal(frame(), first)
+    m.stylizer = st
+    assert torch.equal(frame(), first)
+    versions = [p._version for p in stylize._params(st)]
+    again = stylize.fit_stylizer(m, points, colors, iters=400, stylizer=st)       # a second, longer fit into the same module
+    assert again is st and all(p._version > v for p, v in zip(stylize._params(st), versions))
+    second = frame()
+    assert not torch.equal(second, first)            # the version bump reached the edit blob
+    m.stylizer = through_state_dict(st)
+    assert torch.equal(frame(), second)
