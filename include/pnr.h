@@ -632,6 +632,32 @@ typedef struct pnr_adam_scalars { float one_minus_beta1, beta2, one_minus_beta2,
 uint32_t pnr_adam_max_tensors(void);
 int pnr_adam_step(const pnr_adam_tensor* tensors, uint32_t count, const pnr_adam_scalars* scalars, pnr_stream_t stream);
 
+/* The loss-scaled (-O: fp16 autocast + GradScaler) step without a read-back: what torch.amp.GradScaler.step + torch.optim.Adam compute, skipped
+ * steps included, bit for bit, in two launches that never return to the host.
+ *
+ * pnr_grad_check: GradScaler's finite test on the SCALED gradients of up to pnr_adam_max_tensors() tensors in one launch (only `grad` and `n` of
+ * every entry are used).  Every element is read once; the only store is *found_inf = 1.0f where an element is inf or nan.  It never clears the
+ * flag: the caller zeroes it once per step, so several launches (more than the cap of tensors) accumulate into one flag.
+ *
+ * pnr_adam_step_amp: pnr_adam_step under a device control block (pnr_adam_amp_ctl, a HOST struct of device pointers):
+ *   scale      torch's GradScaler._scale (fp32); the gradients are multiplied by (float)(1.0 / (double)*scale), torch's
+ *              _scale.double().reciprocal().float(), whatever inv_grad_scale the rows carry
+ *   found_inf  the flag of pnr_grad_check: non-zero = every workgroup returns without a store to any tensor
+ *   state      int32[3]: {skipped, skipped, error}.  The number of steps skipped so far is a ping-pong pair: the launches of one step read
+ *              state[parity & 1] and each writes state[(parity & 1) ^ 1] = state[parity & 1] + (*found_inf != 0) (the same value from every launch
+ *              of the step); the caller flips `parity` from one step to the next.  state[2] is the error word (below).
+ *   skipped_base, parity   by value
+ * The bias corrections of Adam are doubles the host forms from the true step count, which a skipped step does not advance -- and the host does
+ * not know about a skip without reading back.  So it passes n_rows (1..8) rows of scalars, row r formed for a step count r lower than its
+ * optimistic one, and the device takes rows[skipped - skipped_base]: no pow on the device, and the update stays torch's bits.  A row index
+ * outside [0, n_rows) on a finite step leaves every tensor untouched and sets state[2] = 1 (a guard: the caller bounds how far it runs ahead of
+ * its last look at `skipped` by n_rows).  NULL pointers: PNR_ERR_INVALID; count above the cap, n_rows 0 or above 8: PNR_ERR_UNSUPPORTED; tensors
+ * with n == 0 are skipped. */
+typedef struct pnr_adam_amp_ctl { const float* scale; const float* found_inf; int32_t* state; int32_t skipped_base; int32_t parity; } pnr_adam_amp_ctl;
+int pnr_grad_check(const pnr_adam_tensor* tensors, uint32_t count, float* found_inf, pnr_stream_t stream);
+int pnr_adam_step_amp(const pnr_adam_tensor* tensors, uint32_t count, const pnr_adam_scalars* rows, uint32_t n_rows, const pnr_adam_amp_ctl* ctl,
+                      pnr_stream_t stream);
+
 /* ---------------------------------------------------------------- cache guard -------------- */
 
 /* 64-bit checksums of `count` (<= 24) device buffers in one launch: buffers / nbytes / word_stride are HOST arrays (device pointers, sizes in

@@ -101,6 +101,8 @@ SIGNATURES = {
     "pnr_present_frame": [_ptr, _ptr],
     "pnr_adam_max_tensors": [],
     "pnr_adam_step": [_ptr, _u32, _ptr, _ptr],
+    "pnr_grad_check": [_ptr, _u32, _ptr, _ptr],
+    "pnr_adam_step_amp": [_ptr, _u32, _ptr, _u32, _ptr, _ptr],
     "pnr_get_rays": [_ptr, _u32, _f32, _f32, _f32, _f32, _u32, _u32, _ptr, _u32, _ptr, _ptr, _ptr],
     "pnr_checksum": [_ptr, _ptr, _ptr, _u32, _ptr, _ptr],
     "pnr_occupancy_workspace_bytes": [_u32, _u32, _u32],
@@ -146,6 +148,11 @@ class AdamTensor(ctypes.Structure):
 class AdamScalars(ctypes.Structure):
     """Mirror of `pnr_adam_scalars` (include/pnr.h)."""
     _fields_ = [(n, _f32) for n in ("one_minus_beta1", "beta2", "one_minus_beta2", "bias_correction2_sqrt", "eps", "neg_step_size", "inv_grad_scale")]
+
+
+class AdamAmpCtl(ctypes.Structure):
+    """Mirror of `pnr_adam_amp_ctl` (include/pnr.h)."""
+    _fields_ = [("scale", _ptr), ("found_inf", _ptr), ("state", _ptr), ("skipped_base", ctypes.c_int32), ("parity", ctypes.c_int32)]
 
 
 MLP_OUT_SIGMOID = 0x100   # PNR_MLP_OUT_SIGMOID

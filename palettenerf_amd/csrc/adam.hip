@@ -8,6 +8,7 @@
 // lerp = fma(w, g - m, m); addcmul = fma(alpha, g * g, v); division by the fp32 scalar; addcdiv = fma(alpha, m / denom, p)), so that a
 // training run is bit-identical to one driven by torch.optim.Adam (tests/test_gpu_ops.py).
 #include "pnr_common.hpp"
+#include <type_traits>
 
 namespace pnr {
 
@@ -22,7 +23,34 @@ struct AdamTable {
 };
 struct AdamScalars { float w1, beta2, c2, bc2_sqrt, inv_bc2_sqrt, eps, neg_step_size; float inv_grad_scale; int variant; };
 
-__global__ void __launch_bounds__(kAdamThreads) k_adam(AdamTable tab, AdamScalars s) {
+// The loss-scaled (-O) step: GradScaler.step without its read-back.  `rows` are the host scalars of the step for every number of steps the device
+// may have skipped since the host last looked (row r: r unobserved skips, i.e. a true step count r lower); `state` = {skipped, skipped, error}: the
+// number of skipped steps so far as a ping-pong pair -- every workgroup of every launch of one step reads state[cur], and the first thread of each
+// launch writes state[cur ^ 1] = state[cur] + (found_inf != 0), the same value from every launch of the step -- and an error word.
+constexpr int kAdamAmpRows = 8;
+struct AdamAmp {
+    AdamScalars rows[kAdamAmpRows];
+    const float* scale; const float* found_inf; int32_t* state;
+    int32_t skipped_base, n_rows, cur;
+};
+
+template <bool kAmp>
+__global__ void __launch_bounds__(kAdamThreads) k_adam(AdamTable tab, std::conditional_t<kAmp, AdamAmp, AdamScalars> a) {
+    AdamScalars amp_row;
+    if constexpr (kAmp) {
+        const int32_t skipped = a.state[a.cur];
+        const bool overflow = *a.found_inf != 0.0f;
+        const int32_t r = skipped - a.skipped_base;
+        const bool bad = !overflow && (r < 0 || r >= a.n_rows);              // never: the host bounds its run-ahead by the number of rows
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            a.state[a.cur ^ 1] = skipped + (overflow ? 1 : 0);
+            if (bad) a.state[2] = 1;
+        }
+        if (overflow || bad) return;                                          // a skipped step: no store to any tensor
+        amp_row = a.rows[r];
+        amp_row.inv_grad_scale = (float)(1.0 / (double)*a.scale);            // torch: _scale.double().reciprocal().float()
+    }
+    const AdamScalars& s = [&]() -> const AdamScalars& { if constexpr (kAmp) return amp_row; else return a; }();
     int ti = 0;
     while (ti + 1 < tab.count && blockIdx.x >= tab.first_chunk[ti + 1]) ti++;   // <= 32 scalar compares
     const AdamTensor t = tab.t[ti];
@@ -50,6 +78,33 @@ __global__ void __launch_bounds__(kAdamThreads) k_adam(AdamTable tab, AdamScalar
     }
 }
 
+// GradScaler's finite check on the scaled gradients (torch._amp_foreach_non_finite_check_and_unscale_'s test, without its write pass): every
+// element read once; the only store is *found_inf = 1 -- the same value from whichever lanes find one, so no atomic -- and never a clear.
+__device__ __forceinline__ bool not_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+__global__ void __launch_bounds__(kAdamThreads) k_grad_check(AdamTable tab, float* found_inf) {
+    int ti = 0;
+    while (ti + 1 < tab.count && blockIdx.x >= tab.first_chunk[ti + 1]) ti++;
+    const float* g = tab.t[ti].g;
+    const uint64_t n = tab.t[ti].n;
+    const uint64_t base = (uint64_t)(blockIdx.x - tab.first_chunk[ti]) * kAdamChunk + threadIdx.x;
+    bool bad = false;
+    if (base - threadIdx.x + kAdamChunk <= n) {                               // a whole chunk: eight loads in flight
+        float x[kAdamPerThread];
+#pragma unroll
+        for (uint32_t k = 0; k < kAdamPerThread; k++) x[k] = g[base + (uint64_t)k * kAdamThreads];
+#pragma unroll
+        for (uint32_t k = 0; k < kAdamPerThread; k++) bad |= not_finite(x[k]);
+    } else {
+        for (uint32_t k = 0; k < kAdamPerThread; k++) {
+            const uint64_t i = base + (uint64_t)k * kAdamThreads;
+            if (i >= n) break;
+            bad |= not_finite(g[i]);
+        }
+    }
+    if (bad) *found_inf = 1.0f;
+}
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -59,31 +114,72 @@ extern "C" {
 
 uint32_t pnr_adam_max_tensors(void) { return kAdamMaxTensors; }
 
+// the chunk table of the tensors with n > 0 (grads_only: pnr_grad_check's, which needs no other pointer); PNR_OK with *chunks == 0 = nothing to launch
+static int adam_table(const pnr_adam_tensor* tensors, uint32_t count, bool grads_only, AdamTable& tab, uint64_t* chunks_out) {
+    uint64_t chunks = 0;
+    int used = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        if (tensors[i].n == 0) continue;
+        if (!tensors[i].grad || (!grads_only && (!tensors[i].param || !tensors[i].exp_avg || !tensors[i].exp_avg_sq))) return PNR_ERR_INVALID;
+        tab.t[used] = AdamTensor{tensors[i].param, tensors[i].grad, tensors[i].exp_avg, tensors[i].exp_avg_sq, tensors[i].n};
+        tab.first_chunk[used] = (uint32_t)chunks;
+        chunks += (tensors[i].n + kAdamChunk - 1) / kAdamChunk;
+        used++;
+    }
+    if (chunks > 0x7fffffffull) return PNR_ERR_UNSUPPORTED;
+    tab.first_chunk[used] = (uint32_t)chunks;
+    tab.count = used;
+    *chunks_out = chunks;
+    return PNR_OK;
+}
+
+static AdamScalars adam_scalars(const pnr_adam_scalars* sc) {
+    AdamScalars s;
+    s.w1 = sc->one_minus_beta1; s.beta2 = sc->beta2; s.c2 = sc->one_minus_beta2; s.bc2_sqrt = sc->bias_correction2_sqrt; s.inv_bc2_sqrt = 1.0f / sc->bias_correction2_sqrt; s.eps = sc->eps;
+    s.neg_step_size = sc->neg_step_size;
+    s.inv_grad_scale = sc->inv_grad_scale > 0.0f ? sc->inv_grad_scale : 1.0f;
+    s.variant = g_opt_adam_variant;
+    return s;
+}
+
 int pnr_adam_step(const pnr_adam_tensor* tensors, uint32_t count, const pnr_adam_scalars* sc, pnr_stream_t stream) {
     if (count == 0) return PNR_OK;
     if (!tensors || !sc) return PNR_ERR_INVALID;
     if (count > (uint32_t)kAdamMaxTensors) return PNR_ERR_UNSUPPORTED;
     AdamTable tab;
     uint64_t chunks = 0;
-    int used = 0;
-    for (uint32_t i = 0; i < count; i++) {
-        if (tensors[i].n == 0) continue;
-        if (!tensors[i].param || !tensors[i].grad || !tensors[i].exp_avg || !tensors[i].exp_avg_sq) return PNR_ERR_INVALID;
-        tab.t[used] = AdamTensor{tensors[i].param, tensors[i].grad, tensors[i].exp_avg, tensors[i].exp_avg_sq, tensors[i].n};
-        tab.first_chunk[used] = (uint32_t)chunks;
-        chunks += (tensors[i].n + kAdamChunk - 1) / kAdamChunk;
-        used++;
-    }
-    if (used == 0) return PNR_OK;
-    if (chunks > 0x7fffffffull) return PNR_ERR_UNSUPPORTED;
-    tab.first_chunk[used] = (uint32_t)chunks;
-    tab.count = used;
-    AdamScalars s;
-    s.w1 = sc->one_minus_beta1; s.beta2 = sc->beta2; s.c2 = sc->one_minus_beta2; s.bc2_sqrt = sc->bias_correction2_sqrt; s.inv_bc2_sqrt = 1.0f / sc->bias_correction2_sqrt; s.eps = sc->eps;
-    s.neg_step_size = sc->neg_step_size;
-    s.inv_grad_scale = sc->inv_grad_scale > 0.0f ? sc->inv_grad_scale : 1.0f;
-    s.variant = g_opt_adam_variant;
-    hipLaunchKernelGGL(k_adam, dim3((uint32_t)chunks), dim3(kAdamThreads), 0, as_stream(stream), tab, s);
+    if (int rc = adam_table(tensors, count, false, tab, &chunks)) return rc;
+    if (chunks == 0) return PNR_OK;
+    hipLaunchKernelGGL(k_adam<false>, dim3((uint32_t)chunks), dim3(kAdamThreads), 0, as_stream(stream), tab, adam_scalars(sc));
+    return check_launch();
+}
+
+int pnr_grad_check(const pnr_adam_tensor* tensors, uint32_t count, float* found_inf, pnr_stream_t stream) {
+    if (count == 0) return PNR_OK;
+    if (!tensors || !found_inf) return PNR_ERR_INVALID;
+    if (count > (uint32_t)kAdamMaxTensors) return PNR_ERR_UNSUPPORTED;
+    AdamTable tab;
+    uint64_t chunks = 0;
+    if (int rc = adam_table(tensors, count, true, tab, &chunks)) return rc;
+    if (chunks == 0) return PNR_OK;
+    hipLaunchKernelGGL(k_grad_check, dim3((uint32_t)chunks), dim3(kAdamThreads), 0, as_stream(stream), tab, found_inf);
+    return check_launch();
+}
+
+int pnr_adam_step_amp(const pnr_adam_tensor* tensors, uint32_t count, const pnr_adam_scalars* rows, uint32_t n_rows, const pnr_adam_amp_ctl* ctl,
+                      pnr_stream_t stream) {
+    if (count == 0) return PNR_OK;
+    if (!tensors || !rows || !ctl || !ctl->scale || !ctl->found_inf || !ctl->state) return PNR_ERR_INVALID;
+    if (count > (uint32_t)kAdamMaxTensors || n_rows == 0 || n_rows > (uint32_t)kAdamAmpRows) return PNR_ERR_UNSUPPORTED;
+    AdamTable tab;
+    uint64_t chunks = 0;
+    if (int rc = adam_table(tensors, count, false, tab, &chunks)) return rc;
+    if (chunks == 0) return PNR_OK;
+    AdamAmp a;
+    for (uint32_t r = 0; r < (uint32_t)kAdamAmpRows; r++) a.rows[r] = adam_scalars(&rows[r < n_rows ? r : n_rows - 1]);
+    a.scale = ctl->scale; a.found_inf = ctl->found_inf; a.state = ctl->state;
+    a.skipped_base = ctl->skipped_base; a.n_rows = (int32_t)n_rows; a.cur = ctl->parity & 1;
+    hipLaunchKernelGGL(k_adam<true>, dim3((uint32_t)chunks), dim3(kAdamThreads), 0, as_stream(stream), tab, a);
     return check_launch();
 }
 

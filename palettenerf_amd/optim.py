@@ -3,11 +3,16 @@
 (`step`, `exp_avg`, `exp_avg_sq`) and, bit for bit, the same updates (pnr_adam_step) -- so schedulers, GradScaler and checkpoints of the
 reference's trainer work unchanged.  torch runs seven elementwise kernels per parameter tensor (~75 launches and seven passes over the
 50 MB hash tables per step); this makes one pass in one launch.
+
+`GradScaler` is `torch.amp.GradScaler` for the reference's default `-O` recipe (fp16 autocast + loss scaling) whose `step` stays on the device
+with `Adam`: a finite check that writes one flag (pnr_grad_check) and the step under that flag (pnr_adam_step_amp) instead of torch's
+`unscale_` pass and its `found_inf.item()` read-back per training step -- torch's bits, skipped steps included.
 """
 import ctypes
 
 import numpy as np
 import torch
+from torch.amp.grad_scaler import OptState
 
 from . import _lib
 
@@ -27,7 +32,7 @@ class Adam(torch.optim.Optimizer):
                 loss = closure()
         lib = _lib.load()
         cap = int(lib.pnr_adam_max_tensors())
-        f32 = np.float32
+        self._amp_reconcile()   # (steps enqueued through GradScaler.step, below: their skips come off `step` first)
         # ONE launch for every tensor that shares its hyperparameters and step count (the reference's get_params makes ten param groups with the
         # same lr / betas / eps: torch runs them group by group); tensors that joined later have their own bias corrections and go separately
         batches = {}
@@ -52,25 +57,191 @@ class Adam(torch.optim.Optimizer):
             key = (float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), int(st["step"].item()), p.device.index)
             batches.setdefault(key, []).append((p, st))
         for (lr, beta1, beta2, eps, step, _dev), items in batches.items():
-            # the host scalars exactly as torch/optim/adam.py forms them (Python floats), narrowed where its CUDA kernels narrow them
-            bias_correction1 = 1 - beta1 ** step
-            bias_correction2 = 1 - beta2 ** step
-            step_size = lr / bias_correction1
-            bias_correction2_sqrt = bias_correction2 ** 0.5
-            sc = _lib.AdamScalars()
-            sc.one_minus_beta1, sc.beta2, sc.one_minus_beta2 = 1 - beta1, beta2, 1 - beta2
-            sc.bias_correction2_sqrt = bias_correction2_sqrt
-            sc.eps, sc.neg_step_size = eps, -step_size
-            sc.inv_grad_scale = 1.0 if not self.grad_scale else float(f32(1.0) / f32(self.grad_scale))
+            sc = self._scalars(lr, beta1, beta2, eps, step, self.grad_scale)
             for i in range(0, len(items), cap):
-                chunk = items[i:i + cap]
-                arr = (_lib.AdamTensor * len(chunk))()
-                for k, (p, st) in enumerate(chunk):
-                    arr[k].param, arr[k].grad = p.data_ptr(), p.grad.data_ptr()
-                    arr[k].exp_avg, arr[k].exp_avg_sq, arr[k].n = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
+                arr = self._tensor_array(items[i:i + cap])
                 with torch.cuda.device(_dev):   # the launch goes to the tensors' device, on torch's current stream there
                     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-                    _lib.check(lib.pnr_adam_step(arr, ctypes.c_uint32(len(chunk)), ctypes.byref(sc), stream), "pnr_adam_step")
+                    _lib.check(lib.pnr_adam_step(arr, ctypes.c_uint32(len(arr)), ctypes.byref(sc), stream), "pnr_adam_step")
             for p, _ in items:
                 torch.autograd.graph.increment_version(p)   # written by a raw kernel: caches keyed on the version (packed blobs, pair tables) must see it
         return loss
+
+    @staticmethod
+    def _scalars(lr, beta1, beta2, eps, step, grad_scale=None):
+        """The host scalars exactly as torch/optim/adam.py forms them (Python floats), narrowed where its CUDA kernels narrow them."""
+        bias_correction1 = 1 - beta1 ** step
+        bias_correction2 = 1 - beta2 ** step
+        step_size = lr / bias_correction1
+        bias_correction2_sqrt = bias_correction2 ** 0.5
+        sc = _lib.AdamScalars()
+        sc.one_minus_beta1, sc.beta2, sc.one_minus_beta2 = 1 - beta1, beta2, 1 - beta2
+        sc.bias_correction2_sqrt = bias_correction2_sqrt
+        sc.eps, sc.neg_step_size = eps, -step_size
+        sc.inv_grad_scale = 1.0 if not grad_scale else float(np.float32(1.0) / np.float32(grad_scale))
+        return sc
+
+    @staticmethod
+    def _tensor_array(items):
+        arr = (_lib.AdamTensor * len(items))()
+        for k, (p, st) in enumerate(items):
+            arr[k].param, arr[k].grad = p.data_ptr(), p.grad.data_ptr()
+            arr[k].exp_avg, arr[k].exp_avg_sq, arr[k].n = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
+        return arr
+
+    # ---------------------------------------------------------------- the loss-scaled (-O) step: GradScaler.step without a read-back
+    #
+    # torch's GradScaler.step reads found_inf back on every step to decide whether to call optimizer.step().  Here the decision is the device's
+    # (pnr_adam_step_amp), and what the host does not know -- how many of the steps it has enqueued were skipped -- it bounds: `step` advances
+    # optimistically, the device's count of skipped steps follows every step into pinned memory behind an event, and the launch carries the
+    # scalars of the step for 0 .. AMP_ROWS - 1 skips the host has not seen yet (the device picks the row).  Skips the host learns of are taken
+    # off every `step`; it waits only if the oldest step it has not seen the end of is AMP_ROWS calls back.
+    AMP_ROWS = 8
+
+    @classmethod
+    def _amp_rows(cls, lr, beta1, beta2, eps, step):
+        """(rows, n_rows): row r = the scalars of true step count `step - r` (`step` = the optimistic count: every enqueued step taken); a step
+        count below 1 cannot be (no more steps were skipped than made), so n_rows = min(AMP_ROWS, step)."""
+        n_rows = max(1, min(cls.AMP_ROWS, int(step)))
+        rows = (_lib.AdamScalars * cls.AMP_ROWS)()
+        for r in range(n_rows):
+            rows[r] = cls._scalars(lr, beta1, beta2, eps, step - r)
+        return rows, n_rows
+
+    def _amp_init(self, device):
+        amp = self.__dict__.get("_amp")
+        if amp is None or amp["device"] != device:
+            if amp is not None:
+                self._amp_reconcile()
+            amp = self.__dict__["_amp"] = dict(
+                device=device,
+                found_inf=torch.zeros((), dtype=torch.float32, device=device),
+                state=torch.zeros(3, dtype=torch.int32, device=device),          # {skipped, skipped, error}: pnr_adam_amp_ctl.state
+                pinned=torch.zeros(2 * self.AMP_ROWS, 3, dtype=torch.int32).pin_memory(),
+                calls=0,              # amp steps launched: the ping-pong parity and the pinned slot
+                skipped_base=0,       # skipped steps the host has seen (and taken off every `step`)
+                pending=[],           # (event, slot, parity after the step) of the steps whose end the host has not seen, oldest first
+                params=[])            # the parameters of the pending steps (the same set for all of them)
+        return amp
+
+    def _amp_observe(self, slot, parity):
+        amp = self._amp
+        row = amp["pinned"][slot]
+        if int(row[2]) != 0:
+            raise RuntimeError("palettenerf_amd.optim.Adam: the device found no scalar row for a loss-scaled step (more skipped steps than rows)")
+        new = int(row[parity]) - amp["skipped_base"]
+        if new:
+            for p in amp["params"]:
+                self.state[p]["step"] -= new
+            amp["skipped_base"] += new
+
+    def _amp_poll(self, keep):
+        """Take in every finished step's count of skips, oldest first; wait until at most `keep` steps are unobserved."""
+        amp = self.__dict__.get("_amp")
+        if amp is None:
+            return
+        pending = amp["pending"]
+        while pending:
+            event, slot, parity = pending[0]
+            if not event.query():
+                if len(pending) <= keep:
+                    break
+                event.synchronize()
+            pending.pop(0)
+            if not pending or not pending[0][0].query():       # the newest finished one carries every earlier skip
+                self._amp_observe(slot, parity)
+
+    def _amp_reconcile(self):
+        """Every enqueued loss-scaled step observed (waits for the device): `step` is then the true count, as torch keeps it."""
+        self._amp_poll(0)
+
+    def state_dict(self):
+        self._amp_reconcile()
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        self._amp_reconcile()
+        return super().load_state_dict(state_dict)
+
+    @torch.no_grad()
+    def _amp_step(self, scale):
+        """GradScaler.step's device path (called by palettenerf_amd.optim.GradScaler): the finite check over every gradient, then the step under
+        the flag.  Returns the flag (a device fp32 scalar: GradScaler.update's found_inf), or None where this path does not apply."""
+        lib = _lib.load()
+        cap = int(lib.pnr_adam_max_tensors())
+        todo = []
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse or p.dtype != torch.float32 or p.grad.dtype != torch.float32 or not p.is_cuda:
+                    raise RuntimeError("palettenerf_amd.optim.Adam: dense fp32 CUDA(HIP) parameters only (no CPU fallback)")
+                if not (p.is_contiguous() and p.grad.is_contiguous()):
+                    raise RuntimeError("palettenerf_amd.optim.Adam: parameters and gradients must be contiguous")
+                todo.append((group, p))
+        if not any(p.numel() for _, p in todo) or any(p.device != scale.device for _, p in todo):
+            return None
+        amp = self._amp_init(scale.device)
+        params = [p for _, p in todo]
+        if len(params) != len(amp["params"]) or any(a is not b for a, b in zip(params, amp["params"])):
+            self._amp_reconcile()         # the skips of the pending steps belong to the parameters those steps had
+            amp["params"] = params
+        self._amp_poll(self.AMP_ROWS - 1)
+        batches = {}
+        for group, p in todo:
+            beta1, beta2 = group["betas"]
+            st = self.state[p]
+            if len(st) == 0:
+                st["step"] = torch.tensor(0.0)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["step"] += 1               # optimistic: taken back when the host learns that the step was skipped
+            key = (float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), int(st["step"].item()))
+            batches.setdefault(key, []).append((p, st))
+        items = [(p, self.state[p]) for p in params]
+        found_inf, state = amp["found_inf"], amp["state"]
+        ctl = _lib.AdamAmpCtl()
+        ctl.scale, ctl.found_inf, ctl.state = scale.data_ptr(), found_inf.data_ptr(), state.data_ptr()
+        ctl.skipped_base, ctl.parity = amp["skipped_base"], amp["calls"] & 1
+        with torch.cuda.device(scale.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            found_inf.zero_()
+            for i in range(0, len(items), cap):             # every check before every step: a late tensor's inf holds the early ones too
+                arr = self._tensor_array(items[i:i + cap])
+                _lib.check(lib.pnr_grad_check(arr, ctypes.c_uint32(len(arr)), ctypes.c_void_p(found_inf.data_ptr()), stream), "pnr_grad_check")
+            for (lr, beta1, beta2, eps, step), members in batches.items():
+                rows, n_rows = self._amp_rows(lr, beta1, beta2, eps, step)
+                for i in range(0, len(members), cap):
+                    arr = self._tensor_array(members[i:i + cap])
+                    _lib.check(lib.pnr_adam_step_amp(arr, ctypes.c_uint32(len(arr)), rows, ctypes.c_uint32(n_rows), ctypes.byref(ctl), stream), "pnr_adam_step_amp")
+            slot = amp["calls"] % amp["pinned"].shape[0]
+            amp["pinned"][slot].copy_(state, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+        amp["pending"].append((event, slot, (amp["calls"] & 1) ^ 1))
+        amp["calls"] += 1
+        for p in params:
+            torch.autograd.graph.increment_version(p)
+        return found_inf
+
+
+class GradScaler(torch.amp.GradScaler):
+    """torch.amp.GradScaler whose `step` does not return to the host when the optimiser is `Adam` (above): torch's `step` runs `unscale_` -- a
+    read-and-write pass over every gradient -- and then reads found_inf back to decide whether to call optimizer.step(); here the finite check
+    (pnr_grad_check) writes nothing but the flag and the step (pnr_adam_step_amp) unscales in its own pass and skips itself on the device.  Bit
+    for bit torch's parameters, moments, `_scale`, `_growth_tracker` and step counts, skipped steps included.  Any other optimiser, an explicit
+    `unscale_` before `step` (gradient clipping) and a disabled scaler take torch's path unchanged; so do `scale`, `update` and `state_dict`."""
+
+    def step(self, optimizer, *args, **kwargs):
+        if not self._enabled or not isinstance(optimizer, Adam) or args or kwargs:
+            return super().step(optimizer, *args, **kwargs)
+        self._check_scale_growth_tracker("step")
+        optimizer_state = self._per_optimizer_states[id(optimizer)]
+        if optimizer_state["stage"] is not OptState.READY:
+            return super().step(optimizer)
+        found_inf = optimizer._amp_step(self._scale)
+        if found_inf is None:
+            return super().step(optimizer)
+        optimizer_state["found_inf_per_device"] = {found_inf.device: found_inf}      # what the inherited update() consumes
+        optimizer_state["stage"] = OptState.STEPPED
+        return None
