@@ -658,6 +658,23 @@ int pnr_grad_check(const pnr_adam_tensor* tensors, uint32_t count, float* found_
 int pnr_adam_step_amp(const pnr_adam_tensor* tensors, uint32_t count, const pnr_adam_scalars* rows, uint32_t n_rows, const pnr_adam_amp_ctl* ctl,
                       pnr_stream_t stream);
 
+/* The weights' average: torch_ema.ExponentialMovingAverage, which every recipe of the reference keeps over all model parameters
+ * (main_nerf.py:151, main_palette.py:228: ema_decay 0.95), for up to pnr_adam_max_tensors() fp32 tensors in ONE launch over pnr_adam_step's
+ * chunk table (additive entries, ABI still 10).
+ *
+ * pnr_ema_update: every element reads param and shadow and writes shadow, once: s' = s - fl(fl(s - p) * one_minus_decay), torch_ema's three
+ * elementwise kernels per tensor (tmp = s - p; tmp.mul_(w); s.sub_(tmp)) rounding for rounding -- the product and the subtraction are not
+ * contracted into one fma.  one_minus_decay is the fp32 narrowing of the host double 1.0 - decay, as torch narrows the scalar of mul_.
+ *
+ * pnr_ema_swap: exchanges param and shadow in place, two reads and two writes per element: `store(); copy_to()` before an evaluation and, called
+ * again, `restore()` after it, without a third copy of any tensor.
+ *
+ * count == 0: PNR_OK.  A NULL array, or a NULL param / shadow in a tensor with n > 0: PNR_ERR_INVALID; count above the cap: PNR_ERR_UNSUPPORTED;
+ * tensors with n == 0 are skipped.  param and shadow of one tensor must not overlap. */
+typedef struct pnr_ema_tensor { float* param; float* shadow; uint64_t n; } pnr_ema_tensor;   /* HOST array of device pointers */
+int pnr_ema_update(const pnr_ema_tensor* tensors, uint32_t count, float one_minus_decay, pnr_stream_t stream);
+int pnr_ema_swap(const pnr_ema_tensor* tensors, uint32_t count, pnr_stream_t stream);
+
 /* ---------------------------------------------------------------- cache guard -------------- */
 
 /* 64-bit checksums of `count` (<= 24) device buffers in one launch: buffers / nbytes / word_stride are HOST arrays (device pointers, sizes in

@@ -103,6 +103,8 @@ SIGNATURES = {
     "pnr_adam_step": [_ptr, _u32, _ptr, _ptr],
     "pnr_grad_check": [_ptr, _u32, _ptr, _ptr],
     "pnr_adam_step_amp": [_ptr, _u32, _ptr, _u32, _ptr, _ptr],
+    "pnr_ema_update": [_ptr, _u32, _f32, _ptr],
+    "pnr_ema_swap": [_ptr, _u32, _ptr],
     "pnr_get_rays": [_ptr, _u32, _f32, _f32, _f32, _f32, _u32, _u32, _ptr, _u32, _ptr, _ptr, _ptr],
     "pnr_checksum": [_ptr, _ptr, _ptr, _u32, _ptr, _ptr],
     "pnr_occupancy_workspace_bytes": [_u32, _u32, _u32],
@@ -153,6 +155,11 @@ class AdamScalars(ctypes.Structure):
 class AdamAmpCtl(ctypes.Structure):
     """Mirror of `pnr_adam_amp_ctl` (include/pnr.h)."""
     _fields_ = [("scale", _ptr), ("found_inf", _ptr), ("state", _ptr), ("skipped_base", ctypes.c_int32), ("parity", ctypes.c_int32)]
+
+
+class EmaTensor(ctypes.Structure):
+    """Mirror of `pnr_ema_tensor` (include/pnr.h)."""
+    _fields_ = [("param", _ptr), ("shadow", _ptr), ("n", _u64)]
 
 
 MLP_OUT_SIGMOID = 0x100   # PNR_MLP_OUT_SIGMOID

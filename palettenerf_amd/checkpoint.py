@@ -2,7 +2,9 @@
 
 The models here carry the reference's parameter and buffer names, shapes and dtypes (pinned by tests/golden/state_dict_layout.json,
 generated from the reference's own modules), so a `.pth` written by the reference trainer loads unchanged and vice versa.
-Only the model part is handled: optimizer / scheduler / scaler / EMA state belong to the trainer, which is out of scope.
+Only the model part is handled: optimizer / scheduler / scaler / EMA state belong to the trainer, which is out of scope.  Their entries load
+into this package's counterparts as they are: `state['optimizer']` into optim.Adam, `state['scaler']` into optim.GradScaler and `state['ema']`
+(torch_ema's state_dict: decay, num_updates, shadow_params, collected_params) into optim.ExponentialMovingAverage.load_state_dict.
 """
 import os
 

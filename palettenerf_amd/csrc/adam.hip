@@ -105,10 +105,73 @@ __global__ void __launch_bounds__(kAdamThreads) k_grad_check(AdamTable tab, floa
     if (bad) *found_inf = 1.0f;
 }
 
+// The weights' average (torch_ema's ExponentialMovingAverage, which every recipe of the reference keeps: main_nerf.py:151, main_palette.py:228)
+// on its own, over the same kind of chunk table: kSwap = false is torch_ema's update -- tmp = s - p; tmp.mul_(w); s.sub_(tmp), three launches and
+// eight passes per tensor there -- as one trip, read p and s, write s, with its roundings: the product and the subtraction are NOT one fma (the intrinsics
+// say so whatever the unit's contraction setting; grid_core.hpp: half_of_product is the precedent).  kSwap = true exchanges p and s in place: what
+// store + copy_to and, called again, restore do around an evaluation, without their third copy of every table.
+struct EmaTensor { float* p; float* s; uint64_t n; };
+struct EmaTable {
+    EmaTensor t[kAdamMaxTensors];
+    uint32_t first_chunk[kAdamMaxTensors + 1];
+    int count;
+};
+
+__device__ __forceinline__ float ema_next(float s, float p, float w) { return __fsub_rn(s, __fmul_rn(__fsub_rn(s, p), w)); }
+
+template <bool kSwap>
+__global__ void __launch_bounds__(kAdamThreads) k_ema(EmaTable tab, float w) {
+    int ti = 0;
+    while (ti + 1 < tab.count && blockIdx.x >= tab.first_chunk[ti + 1]) ti++;
+    const EmaTensor t = tab.t[ti];
+    const uint64_t base = (uint64_t)(blockIdx.x - tab.first_chunk[ti]) * kAdamChunk + threadIdx.x;
+    if (base - threadIdx.x + kAdamChunk <= t.n) {                             // a whole chunk: sixteen loads in flight
+        float p[kAdamPerThread], s[kAdamPerThread];
+#pragma unroll
+        for (uint32_t k = 0; k < kAdamPerThread; k++) { p[k] = t.p[base + (uint64_t)k * kAdamThreads]; s[k] = t.s[base + (uint64_t)k * kAdamThreads]; }
+#pragma unroll
+        for (uint32_t k = 0; k < kAdamPerThread; k++) {
+            if constexpr (kSwap) { t.p[base + (uint64_t)k * kAdamThreads] = s[k]; t.s[base + (uint64_t)k * kAdamThreads] = p[k]; }
+            else t.s[base + (uint64_t)k * kAdamThreads] = ema_next(s[k], p[k], w);
+        }
+    } else {
+        for (uint32_t k = 0; k < kAdamPerThread; k++) {
+            const uint64_t i = base + (uint64_t)k * kAdamThreads;
+            if (i >= t.n) break;
+            const float p = t.p[i], s = t.s[i];
+            if constexpr (kSwap) { t.p[i] = s; t.s[i] = p; }
+            else t.s[i] = ema_next(s, p, w);
+        }
+    }
+}
+
 }  // namespace pnr
 
 using namespace pnr;
 
+template <bool kSwap>
+static int ema_launch(const pnr_ema_tensor* tensors, uint32_t count, float w, pnr_stream_t stream) {
+    if (count == 0) return PNR_OK;
+    if (!tensors) return PNR_ERR_INVALID;
+    if (count > (uint32_t)kAdamMaxTensors) return PNR_ERR_UNSUPPORTED;
+    EmaTable tab;
+    uint64_t chunks = 0;
+    int used = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        if (tensors[i].n == 0) continue;
+        if (!tensors[i].param || !tensors[i].shadow) return PNR_ERR_INVALID;
+        tab.t[used] = EmaTensor{tensors[i].param, tensors[i].shadow, tensors[i].n};
+        tab.first_chunk[used] = (uint32_t)chunks;
+        chunks += (tensors[i].n + kAdamChunk - 1) / kAdamChunk;
+        used++;
+    }
+    if (chunks > 0x7fffffffull) return PNR_ERR_UNSUPPORTED;
+    if (chunks == 0) return PNR_OK;
+    tab.first_chunk[used] = (uint32_t)chunks;
+    tab.count = used;
+    hipLaunchKernelGGL(k_ema<kSwap>, dim3((uint32_t)chunks), dim3(kAdamThreads), 0, as_stream(stream), tab, w);
+    return check_launch();
+}
 
 extern "C" {
 
@@ -182,5 +245,11 @@ int pnr_adam_step_amp(const pnr_adam_tensor* tensors, uint32_t count, const pnr_
     hipLaunchKernelGGL(k_adam<true>, dim3((uint32_t)chunks), dim3(kAdamThreads), 0, as_stream(stream), tab, a);
     return check_launch();
 }
+
+int pnr_ema_update(const pnr_ema_tensor* tensors, uint32_t count, float one_minus_decay, pnr_stream_t stream) {
+    return ema_launch<false>(tensors, count, one_minus_decay, stream);
+}
+
+int pnr_ema_swap(const pnr_ema_tensor* tensors, uint32_t count, pnr_stream_t stream) { return ema_launch<true>(tensors, count, 0.0f, stream); }
 
 }  // extern "C"

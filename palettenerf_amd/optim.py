@@ -7,8 +7,14 @@ reference's trainer work unchanged.  torch runs seven elementwise kernels per pa
 `GradScaler` is `torch.amp.GradScaler` for the reference's default `-O` recipe (fp16 autocast + loss scaling) whose `step` stays on the device
 with `Adam`: a finite check that writes one flag (pnr_grad_check) and the step under that flag (pnr_adam_step_amp) instead of torch's
 `unscale_` pass and its `found_inf.item()` read-back per training step -- torch's bits, skipped steps included.
+
+`ExponentialMovingAverage` is torch_ema's, which every recipe of the reference keeps over the model's parameters: `update` as one launch
+(pnr_ema_update) and `swap` (pnr_ema_swap) in place of store + copy_to / restore around an evaluation -- torch_ema's bits and state_dict.
 """
+import contextlib
+import copy
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -245,3 +251,159 @@ class GradScaler(torch.amp.GradScaler):
         optimizer_state["found_inf_per_device"] = {found_inf.device: found_inf}      # what the inherited update() consumes
         optimizer_state["stage"] = OptState.STEPPED
         return None
+
+
+class ExponentialMovingAverage:
+    """torch_ema 0.3's ExponentialMovingAverage (what the reference's Trainer builds over model.parameters(): nerf/utils.py, palette/utils.py,
+    ema_decay 0.95) with the same constructor, attributes, methods and state_dict keys -- a reference checkpoint's 'ema' entry loads into it --
+    whose `update` is one HIP launch per 32 tensors (pnr_ema_update: read p and s, write s; torch_ema's bits) instead of three elementwise
+    launches per tensor, and no CPU path: parameters must be dense, contiguous, fp32 and on the device.
+
+    `swap()` is new: it exchanges parameters and shadows in place (pnr_ema_swap) -- `store(); copy_to()` before an evaluation and, called again,
+    `restore()` after it, without the third copy of every table -- and bumps the parameters' version counters, so every cache keyed on them (packed
+    weights, interleaved tables, the occupancy mip) rebuilds by itself.  `average_parameters()` is swap / yield / swap.  `store`, `copy_to` and
+    `restore` keep torch_ema's meaning and bump the versions of the parameters they write too (torch_ema writes through `.data`, which the caches
+    only notice through the frame's source checksums)."""
+
+    def __init__(self, parameters, decay, use_num_updates=True):
+        if decay < 0.0 or decay > 1.0:
+            raise ValueError("Decay must be between 0 and 1")
+        self.decay = decay
+        self.num_updates = 0 if use_num_updates else None
+        parameters = list(parameters)
+        self.shadow_params = [p.clone().detach() for p in parameters]      # every parameter passed, frozen ones included (torch_ema 0.3)
+        self.collected_params = None
+        self._params_refs = [weakref.ref(p) for p in parameters]
+        self._swapped = False
+
+    def _get_parameters(self, parameters):
+        if parameters is None:
+            parameters = [p() for p in self._params_refs]
+            if any(p is None for p in parameters):
+                raise ValueError("(One of) the parameters with which this ExponentialMovingAverage was initialized no longer exists (was garbage collected);"
+                                 " please either provide `parameters` explicitly or keep the model to which they belong from being garbage collected.")
+            return parameters
+        parameters = list(parameters)
+        if len(parameters) != len(self.shadow_params):
+            raise ValueError(f"Number of parameters passed as argument is different from number of shadow parameters maintained by this "
+                             f"ExponentialMovingAverage ({len(parameters)} != {len(self.shadow_params)})")
+        return parameters
+
+    @staticmethod
+    def decay_at(decay, num_updates):
+        """torch_ema's warm-up, in Python doubles: the decay of update number `num_updates` (counted from 1)."""
+        return min(decay, (1 + num_updates) / (10 + num_updates))
+
+    def _device_pairs(self, parameters, what):
+        """(parameter, shadow) pairs by device.  Every check before any launch: a rejected tensor must not leave earlier ones updated."""
+        pairs = list(zip(parameters, self.shadow_params))
+        for p, s in pairs:
+            for t in (p, s):
+                if t.is_sparse or t.dtype != torch.float32 or not t.is_cuda:
+                    raise RuntimeError(f"palettenerf_amd.optim.ExponentialMovingAverage.{what}: dense fp32 CUDA(HIP) parameters and shadows only (no CPU fallback)")
+                if not t.is_contiguous():
+                    raise RuntimeError(f"palettenerf_amd.optim.ExponentialMovingAverage.{what}: parameters and shadows must be contiguous")
+            if p.shape != s.shape or p.device != s.device:
+                raise RuntimeError(f"palettenerf_amd.optim.ExponentialMovingAverage.{what}: a shadow does not match its parameter (shape or device)")
+        by_device = {}
+        for p, s in pairs:
+            by_device.setdefault(p.device, []).append((p, s))
+        return by_device
+
+    def _launch(self, entry, by_device, *scalars):
+        lib = _lib.load()
+        cap = int(lib.pnr_adam_max_tensors())
+        for device, pairs in by_device.items():
+            with torch.cuda.device(device):      # the launch goes to the tensors' device, on torch's current stream there
+                stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+                for i in range(0, len(pairs), cap):
+                    arr = (_lib.EmaTensor * len(pairs[i:i + cap]))()
+                    for k, (p, s) in enumerate(pairs[i:i + cap]):
+                        arr[k].param, arr[k].shadow, arr[k].n = p.data_ptr(), s.data_ptr(), p.numel()
+                    _lib.check(getattr(lib, entry)(arr, ctypes.c_uint32(len(arr)), *scalars, stream), entry)
+
+    @torch.no_grad()
+    def update(self, parameters=None):
+        parameters = self._get_parameters(parameters)
+        if self._swapped:
+            raise RuntimeError("palettenerf_amd.optim.ExponentialMovingAverage.update inside a swap: the parameters hold the averages (call swap() back first)")
+        by_device = self._device_pairs(parameters, "update")
+        decay = self.decay
+        if self.num_updates is not None:
+            self.num_updates += 1
+            decay = self.decay_at(decay, self.num_updates)
+        self._launch("pnr_ema_update", by_device, ctypes.c_float(1.0 - decay))
+
+    @torch.no_grad()
+    def swap(self, parameters=None):
+        """Exchange parameters and averages in place, one launch per 32 tensors and no copy; a second call puts both back, bit for bit."""
+        parameters = self._get_parameters(parameters)
+        self._launch("pnr_ema_swap", self._device_pairs(parameters, "swap"))
+        self._swapped = not self._swapped
+        for p in parameters:
+            torch.autograd.graph.increment_version(p)   # written by a raw kernel: caches keyed on the version must see it
+
+    @staticmethod
+    def _copy(dst, src):
+        if dst:
+            with torch.no_grad():
+                torch._foreach_copy_(dst, src)           # in place on the parameters themselves (not `.data`): their versions move
+
+    def copy_to(self, parameters=None):
+        self._copy(self._get_parameters(parameters), self.shadow_params)
+
+    def store(self, parameters=None):
+        self.collected_params = [p.detach().clone() for p in self._get_parameters(parameters)]
+
+    def restore(self, parameters=None):
+        if self.collected_params is None:
+            raise RuntimeError("This ExponentialMovingAverage has no `store()`ed weights to `restore()`")
+        self._copy(self._get_parameters(parameters), self.collected_params)
+
+    @contextlib.contextmanager
+    def average_parameters(self, parameters=None):
+        parameters = self._get_parameters(parameters)
+        self.swap(parameters)
+        try:
+            yield
+        finally:
+            self.swap(parameters)
+
+    def to(self, device=None, dtype=None):
+        move = lambda t: t.to(device=device, dtype=dtype) if t.is_floating_point() else t.to(device=device)
+        self.shadow_params = [move(s) for s in self.shadow_params]
+        if self.collected_params is not None:
+            self.collected_params = [move(c) for c in self.collected_params]
+
+    def state_dict(self):
+        """torch_ema's keys.  Inside a swap the shadows hold the raw parameters: refused."""
+        if self._swapped:
+            raise RuntimeError("palettenerf_amd.optim.ExponentialMovingAverage.state_dict inside a swap: the shadows hold the parameters (call swap() back first)")
+        return {"decay": self.decay, "num_updates": self.num_updates, "shadow_params": self.shadow_params, "collected_params": self.collected_params}
+
+    def load_state_dict(self, state_dict):
+        if self._swapped:
+            raise RuntimeError("palettenerf_amd.optim.ExponentialMovingAverage.load_state_dict inside a swap (call swap() back first)")
+        state_dict = copy.deepcopy(state_dict)
+        decay, num_updates = state_dict["decay"], state_dict["num_updates"]
+        shadow, collected = state_dict["shadow_params"], state_dict["collected_params"]
+        if decay < 0.0 or decay > 1.0:
+            raise ValueError("Decay must be between 0 and 1")
+        if not (num_updates is None or isinstance(num_updates, int)):
+            raise ValueError("Invalid num_updates")
+        if not (isinstance(shadow, list) and all(isinstance(s, torch.Tensor) for s in shadow)):
+            raise ValueError("shadow_params must be a list of Tensors")
+        if collected is not None:
+            if not (isinstance(collected, list) and all(isinstance(c, torch.Tensor) for c in collected)):
+                raise ValueError("collected_params must be a list of Tensors")
+            if len(collected) != len(shadow):
+                raise ValueError("collected_params and shadow_params had different lengths")
+        if len(shadow) != len(self._params_refs):
+            raise ValueError("Tried to `load_state_dict()` with the wrong number of parameters in the saved state.")
+        params = [p() for p in self._params_refs]
+        if not any(p is None for p in params):             # as torch.optim.Optimizer does: onto the parameters' device and dtype
+            cast = lambda t, p: t.to(device=p.device, dtype=p.dtype) if p.is_floating_point() else t.to(device=p.device)
+            shadow = [cast(s, p) for s, p in zip(shadow, params)]
+            if collected is not None:
+                collected = [cast(c, p) for c, p in zip(collected, params)]
+        self.decay, self.num_updates, self.shadow_params, self.collected_params = decay, num_updates, shadow, collected

@@ -241,12 +241,13 @@ def train_step(model, batch, render_kwargs=None, lambda_sparsity=0.0, lambda_off
 
 
 def train_epoch(model, trainset, optimizer, scheduler=None, scaler=None, update_extra_interval=16, global_step=0, batch_size=1, fp16=False,
-                render_kwargs=None, generator=None, max_steps=None, **lambdas):
+                render_kwargs=None, generator=None, max_steps=None, ema=None, **lambdas):
     """train_one_epoch (palette/utils.py:684-767): one pass over the views in a shuffled order -- update_extra_state every update_extra_interval
     global steps, zero_grad, train_step, backward, optimiser step, the per-step scheduler, the error-map update.  The running loss is summed on the
     device and read back ONCE at the end (the reference's loss.item() per step is a synchronisation).  Returns (average loss, new global_step).
     The per-epoch rules -- the lambda_weight decay, the lambda_palette switch, the smooth-loss switch (:649-674) -- stay the caller's: pass the
-    epoch's numbers in **lambdas (train_step's keywords)."""
+    epoch's numbers in **lambdas (train_step's keywords).  `ema` (an optim.ExponentialMovingAverage or torch_ema's) gets its update() where the
+    reference calls it: ONCE, after the pass (palette/utils.py:746-747, nerf/utils.py:920-921; train_gui: after its 16 steps, :789-790) -- not per step."""
     model.train()
     order = trainset.epoch_order(generator)
     total = torch.zeros((), dtype=torch.float32, device=trainset.images.device)
@@ -275,4 +276,6 @@ def train_epoch(model, trainset, optimizer, scheduler=None, scaler=None, update_
             scheduler.step()
         trainset.update_error_map(batch, loss_dict["loss_ray"])
         total += loss.detach()
+    if ema is not None:
+        ema.update()
     return (float(total) / max(1, steps)), global_step
