@@ -457,8 +457,10 @@ static int launch_bwd_c(const T* grad, const float* inputs, const int32_t* offse
                         const LevelParams& lp, uint32_t gridtype, bool ac, hipStream_t s) {
     const uint32_t nc = (sizeof(T) == 4 || C % 2 == 0) ? count_coarse_levels(lp, L) : 0;
     const dim3 block(256);
+    // (a half table with an odd C has no coarse levels, nc == 0 above: no run-combining instantiation for it)
 #define PNR_BWD(CV)                                                                                                                        \
-    if (nc) hipLaunchKernelGGL((k_grid_bwd<T, D, CV, true>), dim3(cdiv(B, 256), nc), block, 0, s, grad, inputs, offsets, gg, B, L, lp, gridtype, ac, 0u); \
+    if constexpr (sizeof(T) == 4 || CV % 2 == 0)                                                                                           \
+        if (nc) hipLaunchKernelGGL((k_grid_bwd<T, D, CV, true>), dim3(cdiv(B, 256), nc), block, 0, s, grad, inputs, offsets, gg, B, L, lp, gridtype, ac, 0u); \
     if (nc < L) hipLaunchKernelGGL((k_grid_bwd<T, D, CV, false>), dim3(cdiv(B, 256), L - nc), block, 0, s, grad, inputs, offsets, gg, B, L, lp, gridtype, ac, nc)
     switch (C) {
         case 1: PNR_BWD(1); break;

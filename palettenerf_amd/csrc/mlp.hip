@@ -1082,7 +1082,40 @@ int pnr_mlp_pack(const pnr_mlp_desc* desc, const float* w0, const float* w1, con
     } while (0)
 #ifdef PNR_MLP_MINI   /* compile-time experiments only: one instantiation, so that a resource-usage build takes seconds */
 #define PNR_MLP_SWITCH(KERNEL, ...) do { hipLaunchKernelGGL((KERNEL<3, 1, 1, 0>), dim3(grid), dim3(kMlpThreads), lds, s, __VA_ARGS__); } while (0)
+#define PNR_MLP_SWITCH_BWD(KERNEL, ...) PNR_MLP_SWITCH(KERNEL, __VA_ARGS__)
+#define PNR_MLP_SWITCH_BWD_H(KERNEL, ...) PNR_MLP_SWITCH(KERNEL, __VA_ARGS__)
 #else
+// The backward keeps both orientations of every layer in LDS: three layers with two tiles at both ends (166 944 bytes) never get past its LDS check, so
+// that stack has no backward instantiation ...
+#define PNR_MLP_SWITCH_BWD(KERNEL, ...)                                                               \
+    do {                                                                                              \
+        const int ti = (int)tiles32(p.dims[0]), to = (int)tiles32(p.dims[p.n_layers]);                \
+        if (p.n_layers == 2) {                                                                        \
+            if (ti == 1 && to == 1) PNR_MLP_DISPATCH(KERNEL, 2, 1, 1, __VA_ARGS__);                   \
+            else if (ti == 1) PNR_MLP_DISPATCH(KERNEL, 2, 1, 2, __VA_ARGS__);                         \
+            else if (to == 1) PNR_MLP_DISPATCH(KERNEL, 2, 2, 1, __VA_ARGS__);                         \
+            else PNR_MLP_DISPATCH(KERNEL, 2, 2, 2, __VA_ARGS__);                                      \
+        } else {                                                                                      \
+            if (ti == 1 && to == 1) PNR_MLP_DISPATCH(KERNEL, 3, 1, 1, __VA_ARGS__);                   \
+            else if (ti == 1) PNR_MLP_DISPATCH(KERNEL, 3, 1, 2, __VA_ARGS__);                         \
+            else if (to == 1) PNR_MLP_DISPATCH(KERNEL, 3, 2, 1, __VA_ARGS__);                         \
+            else return PNR_ERR_UNSUPPORTED;                                                          \
+        }                                                                                             \
+    } while (0)
+// ... and the split-fp16 backward is instantiated for the stacks mlp_backward_impl sends to it (h_fits), no others
+#define PNR_MLP_SWITCH_BWD_H(KERNEL, ...)                                                             \
+    do {                                                                                              \
+        const int ti = (int)tiles32(p.dims[0]), to = (int)tiles32(p.dims[p.n_layers]);                \
+        if (p.n_layers == 2) {                                                                        \
+            if (ti == 1 && to == 1) PNR_MLP_DISPATCH(KERNEL, 2, 1, 1, __VA_ARGS__);                   \
+            else if (ti == 1) PNR_MLP_DISPATCH(KERNEL, 2, 1, 2, __VA_ARGS__);                         \
+            else if (to == 1) PNR_MLP_DISPATCH(KERNEL, 2, 2, 1, __VA_ARGS__);                         \
+            else return PNR_ERR_UNSUPPORTED;                                                          \
+        } else {                                                                                      \
+            if (ti == 1 && to == 1) PNR_MLP_DISPATCH(KERNEL, 3, 1, 1, __VA_ARGS__);                   \
+            else return PNR_ERR_UNSUPPORTED;                                                          \
+        }                                                                                             \
+    } while (0)
 #define PNR_MLP_SWITCH(KERNEL, ...)                                                                   \
     do {                                                                                              \
         const int ti = (int)tiles32(p.dims[0]), to = (int)tiles32(p.dims[p.n_layers]);                \
@@ -1181,8 +1214,8 @@ static int mlp_backward_impl(const pnr_mlp_desc* desc, const float* packed, cons
     if (g_opt_mlp_f16x3 && h_fits && lds_h <= 160 * 1024) {
         const size_t lds_fp32 = lds;
         (void)lds_fp32;
-        { const size_t lds = lds_h; PNR_MLP_SWITCH(k_mlp_bwd_h, p, packed, x, x_tail, dy, y, B, dx, partial); }
-    } else PNR_MLP_SWITCH(k_mlp_bwd, p, packed, x, x_tail, dy, y, B, dx, partial);
+        { const size_t lds = lds_h; PNR_MLP_SWITCH_BWD_H(k_mlp_bwd_h, p, packed, x, x_tail, dy, y, B, dx, partial); }
+    } else PNR_MLP_SWITCH_BWD(k_mlp_bwd, p, packed, x, x_tail, dy, y, B, dx, partial);
     hipLaunchKernelGGL(k_mlp_dw_reduce, dim3(cdiv(p.dw_floats, 32)), dim3(256), 0, s, partial, grid, p, gr);
     return check_launch();
 }

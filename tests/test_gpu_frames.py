@@ -1437,3 +1437,134 @@ def test_finish_continues_from_the_submitted_plan(cuda, kind):
         assert torch.equal(torch.isnan(x), torch.isnan(y)) and torch.equal(torch.nan_to_num(x), torch.nan_to_num(y))
     if kind == "palette":
         assert torch.equal(got[-1]["depth_raw"], want[-1]["depth_raw"])
+
+
+def _watched_model(kind, cuda, **opt_kw):
+    """The weights of test_gpu_ops.py::test_split_fp16_field_when_activations_can_leave_the_fp16_range at its row scale 3e2: one hidden activation of
+    the view-dependent head in the hundreds, so that the static bound on the activations fails although nothing leaves fp16's range -- the frame
+    loops keep their fp16 form and WATCH the operands they split (pnr_*_frame_args::watch_overflow)."""
+    if kind == "nerf":
+        m = network.NeRFNetwork(bound=2, cuda_ray=True, density_scale=100.0, min_near=0.2)
+    else:
+        m = network.PaletteNetwork(renderer.default_opt(**opt_kw), bound=2, cuda_ray=True, density_scale=100.0, min_near=0.2)
+    scene.seed_field_(m, 11)
+    with torch.no_grad():
+        m.sigma_net[1].weight[1:].mul_(64.0)
+        m.color_net[0].weight[:, 16:].mul_(1.0 / 64.0)
+        if kind == "palette":
+            m.diff_net[0].weight.mul_(1.0 / 64.0)
+        m.color_net[0].weight[5, 16:].mul_(64.0)
+        m.color_net[0].weight[5].mul_(3.0e2)
+        m.color_net[1].weight[:, 5].mul_(1.0 / 3.0e2)
+    m = m.to(cuda).eval()
+    put_scene(m, cuda)
+    m.march_mode, m.fused_field, m.count_rendered = "native", True, True
+    return m
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["nerf_f16x2", "palette_edit", "palette_stylizer"])
+def test_watched_frames_are_inside_the_colour_contract(cuda, case):
+    """The instantiations that watch their split operands outside the plain split-fp16 frame: the NeRF field with activations rounded once to fp16
+    (k_frame_field<2, true>) and the palette field with a RegionEdit and with a Stylizer head (k_palette_field_fwd<1, 1, true, ..>, <1, 2, true, ..>).
+    Each against the same frame on the exact fp32 path, within the colour contract of test_palette_frame_f16x2_is_inside_the_colour_contract and
+    test_split_fp16_field_when_activations_can_leave_the_fp16_range (1e-4); nothing overflows, so the watch stays silent and the fp16 form stays."""
+    import warnings
+    from palettenerf_amd.fused import NeRFFieldFused, PaletteFieldFused
+    kind = case.split("_")[0]
+    m = _watched_model(kind, cuda)
+    f = m._fused = (NeRFFieldFused if kind == "nerf" else PaletteFieldFused)(m)
+    kw = dict(perturb=False, dt_gamma=0.0, max_steps=1024, T_thresh=1e-4)
+    level = 1
+    if case == "nerf_f16x2":
+        f.precision = level = 2
+    elif case == "palette_edit":
+        m.edit = renderer.RegionEdit(m.opt)
+        m.edit.update_cent(mean_xyz=torch.tensor([0.2, 0.1, -0.1], device=cuda))
+        m.edit.update_std(std_xyz=0.3)
+        m.edit.update_delta_hsv(m.basis_color.data.clamp(0, 1), (m.basis_color.data * 0.5 + 0.3).flip(0).clamp(0, 1))
+        kw["gui_mode"] = False
+    else:
+        m.stylizer = renderer.Stylizer(m.opt).to(cuda)
+        with torch.no_grad():
+            for k, v in scene.stylizer_state(m.opt.num_basis, 3).items():
+                getattr(m.stylizer, k).copy_(v)
+        kw["gui_mode"] = True
+    ro, rd = scene.get_rays(torch.from_numpy(scene.lookat_pose())[None], scene.intrinsics_from_fov(48, 48), 48, 48)
+    ro, rd = ro.to(cuda), rd.to(cuda)
+    with torch.no_grad(), warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        assert f.frame_precision() == (level, True)
+        got = m.render(ro, rd, **kw)
+        assert f.frame_precision() == (level, True) and not [w for w in caught if "fp16's range" in str(w.message)]      # watched, and nothing reported
+        f.precision = 0
+        assert f.frame_precision() == (0, False)
+        want = m.render(ro, rd, **kw)
+    assert int(want["rendered"].sum()) > 1000
+    for k in ("image", "weights_sum"):
+        assert torch.isfinite(got[k]).all()
+        err = float((got[k] - want[k]).abs().max())
+        print(f"{case} {k}: {err:.3g} from the fp32 frame")
+        assert err < COLOUR_TOL, (k, err)
+    assert float((got["image"] - want["image"]).abs().max()) > 0        # really another arithmetic
+
+
+@pytest.mark.gpu
+def test_palette_frame_f16x2_with_the_clip_head_is_inside_the_colour_contract(cuda):
+    """PNR_FIELD_F16X2 with a clip head: rows of 52 floats do not fit the 16-wave kernel, the frame runs the 8-wave F16X2 instantiation
+    (k_palette_field_fwd<2, 0, false, 4, 8>).  The checks of test_palette_frame_f16x2_is_inside_the_colour_contract on a 64 x 64 frame."""
+    from palettenerf_amd.fused import PaletteFieldFused
+    m = network.PaletteNetwork(renderer.default_opt(pred_clip=True), bound=2, cuda_ray=True, density_scale=100.0)
+    scene.seed_field_(m, 0)
+    m = m.to(cuda).eval()
+    put_scene(m, cuda)
+    m.march_mode, m.fused_field, m.count_rendered = "native", True, True
+    m._fused = PaletteFieldFused(m)
+    H = W = 64
+    ro, rd = scene.get_rays(torch.from_numpy(scene.lookat_pose())[None], scene.intrinsics_from_fov(H, W), H, W)
+    ro, rd = ro.to(cuda), rd.to(cuda)
+    kw = dict(perturb=False, dt_gamma=0, max_steps=1024, T_thresh=1e-4, gui_mode=False, bg_color=1)
+    keys = ("image", "direct_rgb", "view_dep_rgb", "basis_rgb", "unscaled_basis_rgb", "basis_acc", "clip_feat", "weights_sum")
+    with torch.no_grad():
+        ref = m.render(ro, rd, **kw)
+        m._fused.precision = 2
+        assert m._fused.frame_precision() == (2, False)
+        fast = m.render(ro, rd, **kw)
+    assert int(fast["rendered"].sum()) == int(ref["rendered"].sum()) > 1000 and torch.equal(fast["weights_sum"], ref["weights_sum"])
+    worst = max(float((fast[k] - ref[k]).abs().max()) for k in keys)
+    assert 1e-8 < worst < 1e-4, worst      # really the rounded form, and inside the contract
+    assert scene.psnr(fast["image"].cpu(), ref["image"].cpu()) > 85.0
+
+
+@pytest.mark.gpu
+def test_native_loop_ray_order_with_an_aux_row_wider_than_64_floats(cuda):
+    """test_native_loop_ray_order_leaves_every_output_bit_identical for a palette model with 8 bases and the 16-wide clip head: an aux row of 80
+    floats, which the frame's last launch moves with 32 lanes per ray (k_frame_unsort_outputs<32>) instead of 16."""
+    from palettenerf_amd import _lib
+    from palettenerf_amd.fused import PaletteFieldFused, tile_ray_order
+    opt = renderer.default_opt(pred_clip=True, num_basis=8)
+    assert int(_lib.load().pnr_palette_aux_channels(8, opt.clip_dim)) == 80
+    m = network.PaletteNetwork(opt, bound=2, cuda_ray=True, density_scale=30.0, min_near=0.2)
+    scene.seed_field_(m, 5)
+    m = m.to(cuda).eval()
+    put_scene(m, cuda)
+    m.count_rendered = True
+    m.march_mode, m.fused_field = "native", True
+    H, W = 40, 56
+    pose = torch.from_numpy(scene.lookat_pose())[None]
+    ro, rd = scene.get_rays(pose, scene.intrinsics_from_fov(H, W), H, W)
+    ro, rd = ro.to(cuda), rd.to(cuda)
+    m._fused = PaletteFieldFused(m)
+    kw = dict(perturb=False, dt_gamma=0, max_steps=1024, T_thresh=1e-4)
+    with torch.no_grad():
+        base = m.render(ro, rd, **kw)
+        outs = []
+        for order in (tile_ray_order(torch.arange(H * W), W, 8), torch.randperm(H * W, generator=torch.Generator().manual_seed(1)).to(torch.int32)):
+            m._fused.ray_order = order.to(cuda)
+            outs.append(m.render(ro, rd, **kw))
+    assert int(base["rendered"].item()) > 1000 and m._fused.aux_channels == 80
+    for o in outs:
+        assert int(o["rendered"].item()) == int(base["rendered"].item())
+        for k, v in base.items():
+            if torch.is_tensor(v) and v.dtype.is_floating_point and v.numel() > 1:
+                assert torch.equal(torch.nan_to_num(o[k], nan=-7.0), torch.nan_to_num(v, nan=-7.0)), k

@@ -123,6 +123,29 @@ def test_grid_variant_against_float64_and_the_oracle(cuda, D, C):
     assert not ck.fails, "\n".join(ck.fails)
 
 
+@pytest.mark.parametrize("nt", [1, 2, 3])
+def test_grid_d3c2_non_temporal_forms_against_float64_and_the_oracle(cuda, nt):
+    """pnr_set_option("grid_nt", 1 | 2 | 3) sends the D = 3, C = 2 forward to k_grid_fwd_d3c2<T, false, NT> (non-temporal output stores, input loads,
+    both): other instructions for the same arithmetic, so the checks of the (3, 2) case above hold unchanged, for both table types."""
+    from palettenerf_amd import _lib
+    lib = _lib.load()
+    D, C = 3, 2
+    ck = _Checks()
+    try:
+        assert lib.pnr_set_option(b"grid_nt", nt) == 0
+        for ci, (name, offsets, gridtype, ac) in enumerate(gr.variant_cases(D)):
+            emb, g999 = gr.variant_tables(D, C, ci)
+            for xname, x in gr.variant_inputs(D).items():
+                tag = f"nt{nt} {name} {xname}"
+                ref = gr.variant_geometry(D, ci, xname)
+                g = g999[: x.shape[0]]
+                _one_table(ck, cuda, tag, "fp32", ref, x, emb, offsets, gridtype, ac, g, D, C)
+                _one_table(ck, cuda, tag, "fp16", ref, x, emb.astype(np.float16), offsets, gridtype, ac, (g * 0.01).astype(np.float16), D, C)
+    finally:
+        lib.pnr_set_option(b"grid_nt", 0)
+    assert not ck.fails, "\n".join(ck.fails)
+
+
 @pytest.mark.parametrize("D,C,levels", [(6, 2, 4), (3, 3, 4), (3, 2, 33)])
 def test_grid_unsupported_shapes_raise_forward_and_backward(cuda, D, C, levels):
     """D = 6, C = 3 and L = 33 are not compiled: RuntimeError `unsupported` from the forward (through grid_encode) and from the backward entry point

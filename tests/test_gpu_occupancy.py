@@ -198,6 +198,47 @@ def test_full_size_sweep_against_the_oracle(cuda):
     assert abs(m2.mean_density - omean) <= 1e-7 * omean
 
 
+@pytest.mark.parametrize("bound", [1.5, 3.0])
+def test_small_sweep_at_a_bound_that_is_no_power_of_two(cuda, bound):
+    """C x 32^3 at bound 1.5 (two cascades) and 3 (three): k_occ_lookup takes the division branch of unit_cube_of (grid_xside.hpp) and the last
+    cascade's cells are bound / G wide, not 2^c / G.  The checks of test_full_size_sweep_against_the_oracle, on every cell: points bit for bit
+    against the oracle, densities to SIGMA_RTOL, the bitfield the packbits of the kernel's own grid and the oracle's away from the threshold."""
+    G = 32
+    density_scale = 0.7
+    m = network.NeRFNetwork(bound=bound, cuda_ray=True, density_scale=density_scale, min_near=0.2, density_thresh=1e9)
+    C = m.cascade
+    assert C == (2 if bound == 1.5 else 3)
+    scene.seed_field_(m, 5)
+    m = m.to(cuda).train()
+    resize_grid(m, G)
+    assert m._fused_sweep_ok()
+    noise = torch.rand(C, G ** 3, 3, device=cuda, generator=torch.Generator(device="cuda").manual_seed(11))
+    pts = _points_of_sweep(m, {"mode": 0, "noise": noise})
+    oxyz, ocells, op4 = oracle.occupancy_points(C, G, bound, noise.cpu().numpy())
+    assert np.array_equal(pts.cpu().numpy().view(np.int32), op4.view(np.int32))
+    assert float(np.abs(oxyz).max()) > (1.0 if bound == 1.5 else 2.0) and float(np.abs(oxyz).max()) <= bound      # the last cascade spans the bound, not 2^c
+    m.update_extra_state(noise=noise)
+    want = (_oracle_sigma(m, oxyz) * np.float32(density_scale)).reshape(C, -1)
+    grid = m.density_grid.cpu().numpy()
+    cells = op4[:, 3].view(np.int32)
+    assert np.array_equal(np.sort(cells), np.arange(C * G ** 3))             # a full sweep: one point per cell
+    want_grid = np.empty(C * G ** 3, np.float32)
+    want_grid[cells] = want.reshape(-1)
+    rel = np.abs(grid.reshape(-1) / want_grid - 1).max()
+    print(f"bound {bound}: densities within {rel:.3g} of the CPU arithmetic")
+    assert rel < SIGMA_RTOL, rel
+    mean = np.float32(m.mean_density)
+    assert abs(float(mean) / float(grid.astype(np.float64).mean()) - 1) < 1e-6
+    bits = m.density_bitfield.cpu().numpy()
+    assert np.array_equal(unpack(bits, C), grid > mean)
+    assert_bitfield(bits, want_grid.reshape(C, -1), mean, C)
+    mip = raymarching.occupancy_mip(m.density_bitfield, C, G, m.bound)
+    fresh = torch.empty_like(mip)
+    _lib.call("pnr_build_occupancy_mip", ctypes.c_void_p(m.density_bitfield.data_ptr()), ctypes.c_uint32(C), ctypes.c_uint32(G), ctypes.c_float(m.bound),
+              ctypes.c_void_p(fresh.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert torch.equal(mip, fresh)
+
+
 def test_partial_sweep_occupied_list_and_duplicates(cuda):
     """mode 1 at full size with the draws made here: the occupied list is torch.nonzero's, repeated cells keep their largest candidate,
     cascades without an occupied cell skip the occupied half, nothing waits for the device."""

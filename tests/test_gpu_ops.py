@@ -130,12 +130,21 @@ def test_occupancy_mip_matches_numpy(cuda, s0):
 
 @pytest.mark.parametrize("dt_gamma,min_near,bound", [(0.0, 0.2, 2.0), (1.0 / 128, 0.02, 2.0), (1.0 / 256, 0.05, 1.5)])
 def test_march_rays_train_bit_exact(cuda, s0, mip_mode, dt_gamma, min_near, bound, monkeypatch):
-    """Both second passes: the rows written from the stored sample parameters (default) and the second walk (t_store off, when
-    mip_mode is the plain one) must equal the oracle bit for bit."""
-    if not mip_mode:
-        monkeypatch.setattr(raymarching, "T_STORE_MAX", 0)
+    """Both second passes: the rows written from the stored sample parameters (default) and the second walk (k_march_train_write: t_store off,
+    which T_STORE_MAX = 0 forces) must equal the oracle bit for bit, with and without the mip, for both counting passes."""
+    _march_rays_train_bit_exact(cuda, s0, dt_gamma, min_near, bound, monkeypatch, 64, 48)
+
+
+@pytest.mark.parametrize("bound", [2.0, 1.5])
+def test_march_rays_train_bit_exact_four_rays_per_wave(cuda, s0, mip_mode, bound, monkeypatch):
+    """More than 8192 rays: the cooperative counting pass takes four rays per wave (k_march_train_count_coop<.., .., 4>), one instantiation per
+    (mip, power-of-two bound).  96 x 96 rays; the checks of test_march_rays_train_bit_exact."""
+    _march_rays_train_bit_exact(cuda, s0, 0.0, 0.2, bound, monkeypatch, 96, 96)
+
+
+def _march_rays_train_bit_exact(cuda, s0, dt_gamma, min_near, bound, monkeypatch, H, W):
     grid, bf = s0
-    ro, rd = rays_of(64, 48)
+    ro, rd = rays_of(H, W)
     N = ro.shape[0]
     aabb = np.array([-bound, -bound, -bound, bound, bound, bound], np.float32)
     on, of = oracle.near_far_from_aabb(ro, rd, aabb, min_near)
@@ -145,8 +154,9 @@ def test_march_rays_train_bit_exact(cuda, s0, mip_mode, dt_gamma, min_near, boun
     from palettenerf_amd import _lib
     lib = _lib.load()
     try:
-        for coop in (1, 0):   # the counting pass: four rays per wave cooperatively (k_march_train_count_coop) / one ray per lane
+        for coop, t_store in ((1, True), (0, True), (1, False), (0, False)):   # the counting pass: a wave per ray (or four) cooperatively (k_march_train_count_coop) / one ray per lane
             assert lib.pnr_set_option(b"train_coop", coop) == 0
+            monkeypatch.setattr(raymarching, "T_STORE_MAX", 1 << 26 if t_store else 0)
             counter = torch.zeros(2, dtype=torch.int32, device=cuda)
             x, d, dl, rays = raymarching.march_rays_train(dev(ro, cuda), dev(rd, cuda), bound, dev(bf, cuda), 2, 128, dev(on, cuda), dev(of, cuda), counter,
                                                           -1, False, 128, True, dt_gamma, 1024)
@@ -750,7 +760,7 @@ def test_sh_encode_forward_and_grad(cuda, degree, golden_dir):
         np.testing.assert_allclose(host(shencoder.sh_encode(dev(gold["x"], cuda), degree, False)), gold[f"y{degree}"], atol=2e-6)
 
 
-@pytest.mark.parametrize("degree,t,B", [(4, 15, 100003), (4, 15, 1), (1, 63, 255), (7, 15, 257), (3, 1, 4096), (5, 39, 513)])
+@pytest.mark.parametrize("degree,t,B", [(4, 15, 100003), (4, 15, 1), (1, 63, 255), (7, 15, 257), (3, 1, 4096), (5, 39, 513), (2, 60, 257), (6, 28, 513)])
 def test_sh_encode_cat_is_the_concatenation(cuda, degree, t, B):
     """pnr_sh_encode_cat_forward == torch.cat([sh_encode(d), tail]) bit for bit (color_net's input, nerf/network.py:109-115); the tail's
     gradient is the column slice, directions get none."""
@@ -1183,7 +1193,7 @@ def test_get_rays_bit_exact_vs_oracle_and_reference_golden(cuda, golden_dir):
 
 # ------------------------------------------------------------------------------------------ dense-layer weight gradient (training)
 @pytest.mark.parametrize("n_in,n_out", [(32, 64), (64, 16), (31, 64), (64, 64), (64, 3), (15, 13), (35, 64), (1, 1)])
-@pytest.mark.parametrize("dtypes", [(torch.float32, torch.float32), (torch.float16, torch.float16), (torch.float32, torch.float16)])
+@pytest.mark.parametrize("dtypes", [(torch.float32, torch.float32), (torch.float16, torch.float16), (torch.float32, torch.float16), (torch.float16, torch.float32)])
 def test_linear_weight_grad_matches_float64(cuda, n_in, n_out, dtypes):
     from palettenerf_amd import linear
     g = torch.Generator().manual_seed(n_in * 100 + n_out)
@@ -1490,15 +1500,33 @@ def test_fused_density_matches_the_torch_sigma_net(cuda, kind, precision):
     assert torch.equal(got["sigma"], d(x)[0]) or precision == 0
 
 
+# One stack per instantiation the MLP dispatcher (csrc/mlp.hip: PNR_MLP_SWITCH) can be asked for through run_mlp: layers {2, 3} x input tiles of 32
+# {1, 2} x output tiles {1, 2} x hidden activation {relu, elu}, every width odd or short of its tile somewhere.  Three layers with two tiles at both
+# ends do not fit the backward's LDS (mlp.fusable refuses them; test_fused_mlp_widest_stack_forward_through_the_c_abi has their forward).
+MLP_STACKS = [((20, 48, 9), "relu"), ((20, 48, 9), "elu"), ((9, 33, 50), "relu"), ((9, 33, 50), "elu"), ((40, 64, 17), "relu"), ((40, 64, 17), "elu"),
+              ((40, 64, 33), "relu"), ((64, 50, 64), "elu"), ((24, 40, 64, 5), "relu"), ((24, 40, 64, 5), "elu"), ((16, 64, 32, 48), "relu"),
+              ((30, 17, 64, 33), "elu"), ((33, 64, 64, 7), "relu"), ((33, 64, 64, 7), "elu")]
+# ... of which the split-fp16 default lacked these
+MLP_STACKS_SPLIT = [((20, 48, 9), "elu"), ((9, 33, 50), "relu"), ((40, 64, 33), "relu"), ((64, 50, 64), "elu"), ((24, 40, 64, 5), "elu"),
+                    ((16, 64, 32, 48), "relu"), ((30, 17, 64, 33), "elu"), ((33, 64, 64, 7), "elu")]
+
+
 @pytest.mark.parametrize("dims,act", [((31, 64, 64, 3), "relu"), ((15, 64, 64, 3), "relu"), ((35, 64, 15), "elu"), ((32, 64, 16), "relu"),
                                       ((7, 20, 40), "elu"), ((64, 33, 64, 16), "relu"),
-                                      ((31, 64, 64, 3), "relu+sigmoid"), ((15, 64, 64, 3), "relu+sigmoid"), ((7, 20, 40), "elu+sigmoid")])
-def test_fused_mlp_forward_backward_match_float64(cuda, dims, act):
+                                      ((31, 64, 64, 3), "relu+sigmoid"), ((15, 64, 64, 3), "relu+sigmoid"), ((7, 20, 40), "elu+sigmoid")]
+                         + MLP_STACKS_SPLIT + [(dims, act + "@fp32") for dims, act in MLP_STACKS])
+def test_fused_mlp_forward_backward_match_float64(cuda, request, dims, act):
     """pnr_mlp_forward / pnr_mlp_backward (csrc/mlp.hip) against the layer loop in float64: output 2e-6 relative to the largest output,
     dX and every dW 2e-5 relative to that gradient's largest entry (fp32 accumulation over 5e4 samples).  Shapes of every net of both
-    fields plus odd widths and a batch that is not a multiple of the 128-sample workgroup tile; dW is deterministic."""
+    fields plus odd widths and a batch that is not a multiple of the 128-sample workgroup tile; dW is deterministic.
+    "@fp32": the same with the exact fp32 launches ("mlp_f16x3" = 0), which the default never reaches."""
     import torch.nn.functional as F
-    from palettenerf_amd import mlp
+    from palettenerf_amd import mlp, _lib
+    act, _, arith = act.partition("@")
+    if arith == "fp32":
+        lib = _lib.load()
+        request.addfinalizer(lambda: lib.pnr_set_option(b"mlp_f16x3", 1))
+        assert lib.pnr_set_option(b"mlp_f16x3", 0) == 0
     torch.manual_seed(sum(dims))
     B = 50000 + 77
     net = torch.nn.ModuleList([torch.nn.Linear(dims[i], dims[i + 1], bias=False) for i in range(len(dims) - 1)]).to(cuda)
@@ -1537,6 +1565,40 @@ def test_fused_mlp_forward_backward_match_float64(cuda, dims, act):
         l.weight.grad = None
     (mlp.run_mlp(net, x.detach(), fact, out) * wy).sum().backward()
     assert all(torch.equal(l.weight.grad, g) for l, g in zip(net, got[1:]))
+
+
+@pytest.mark.parametrize("f16x3", [1, 0])
+@pytest.mark.parametrize("dims,act", [((33, 64, 64, 40), "relu"), ((64, 50, 64, 64), "elu")])
+def test_fused_mlp_widest_stack_forward_through_the_c_abi(cuda, dims, act, f16x3):
+    """Three layers with more than 32 columns at both ends: pnr_mlp_forward takes them (k_mlp_fwd / k_mlp_fwd_h <3, 2, 2, .>), the backward has no LDS
+    for them and palettenerf_amd.mlp never asks -- so the forward is called as a C caller would.  Against the float64 layer loop, to the forward bound of
+    test_fused_mlp_forward_backward_match_float64; a batch of one 128-row workgroup tile and a bit."""
+    import ctypes
+    import torch.nn.functional as F
+    from palettenerf_amd import mlp, _lib
+    from palettenerf_amd._torch_glue import call, ptr
+    lib = _lib.load()
+    torch.manual_seed(sum(dims))
+    B = 128 + 37
+    ws = [torch.randn(dims[i + 1], dims[i], device=cuda) / dims[i] ** 0.5 for i in range(3)]
+    fact = F.relu if act == "relu" else F.elu
+    x = torch.randn(B, dims[0], device=cuda)
+    net = torch.nn.ModuleList([torch.nn.Linear(dims[i], dims[i + 1], bias=False) for i in range(3)]).to(cuda)
+    assert not mlp.fusable(net, torch.zeros(mlp.MIN_ROWS, dims[0], device=cuda, requires_grad=True), fact)
+    desc = mlp._desc(list(dims), mlp._ACT[fact])
+    packed = torch.empty(int(lib.pnr_mlp_packed_bytes(ctypes.byref(desc))) // 4, dtype=torch.float32, device=cuda)
+    y = torch.empty(B, dims[-1], device=cuda)
+    try:
+        assert lib.pnr_set_option(b"mlp_f16x3", f16x3) == 0
+        call("pnr_mlp_pack", ctypes.byref(desc), ptr(ws[0]), ptr(ws[1]), ptr(ws[2]), ptr(packed))
+        call("pnr_mlp_forward", ctypes.byref(desc), ptr(packed), ptr(x), ctypes.c_uint32(B), ptr(y))
+        torch.cuda.synchronize()
+    finally:
+        lib.pnr_set_option(b"mlp_f16x3", 1)
+    h, _ = f64.mlp_block(x, ws, torch.zeros(B, dims[-1]), fact, None, torch.float64, "cpu")
+    scale = float(h.abs().max())
+    err = float((y.double().cpu() - h).abs().max())
+    assert scale > 0.1 and err <= 2e-6 * scale, (err, scale)
 
 
 @pytest.mark.parametrize("dims,act,scale", [((32, 64, 64, 16), "relu", 1.0), ((35, 64, 15), "elu", 1.0), ((32, 64, 16), "relu", 1e-4), ((31, 64, 64, 3), "relu", 3e3)])
@@ -1674,19 +1736,23 @@ def test_grid_pair_copy_lives_on_the_encoder_and_notices_data_writes(cuda):
     assert torch.equal(b, fused.grid_encode_raw(other, x01)) and torch.equal(a, fused.grid_encode_raw(m.encoder, x01))
 
 
-def test_sigma_geo_cat_matches_the_reference_composition(cuda):
+@pytest.mark.parametrize("B", [1, 255, 257, 70001])
+@pytest.mark.parametrize("degree,hw", [(1, 2), (3, 15), (4, 16), (6, 29), (7, 16)])
+def test_sigma_geo_cat_matches_the_reference_composition(cuda, degree, hw, B):
     """shencoder.sigma_geo_cat -- trunc_exp(h[:, 0]) and cat([SH(d), h[:, 1:]]) as one launch each way (pnr_sigma_geo_cat_*) -- against the composition the
     reference writes (nerf/network.py:109-121 with activation.py's trunc_exp): forward bit for bit, the gradient of h to 1 ulp of exp (a logit beyond the
-    clamp included)."""
+    clamp included).  Every SH degree's forward instantiation short of the 64-column limit or at it; h rows of 2 floats, of a power of two and of neither
+    (the backward's block is the width rounded up to one); one row, a block less a row, a block and a row, many blocks."""
     from palettenerf_amd import shencoder as she
     from palettenerf_amd.activation import trunc_exp
     torch.manual_seed(3)
-    B = 70001
-    enc = she.SHEncoder(degree=4)
-    h = torch.randn(B, 16, device=cuda)
-    h[5, 0], h[6, 0] = 20.0, -20.0                        # beyond the clamp of the gradient
+    enc = she.SHEncoder(degree=degree)
+    h = torch.randn(B, hw, device=cuda)
+    h[0, 0] = 20.0                                        # beyond the clamp of the gradient
+    if B > 6:
+        h[5, 0], h[6, 0] = 20.0, -20.0
     d = torch.nn.functional.normalize(torch.randn(B, 3, device=cuda), dim=-1)
-    w_s, w_c = torch.randn(B, device=cuda), torch.randn(B, 31, device=cuda)
+    w_s, w_c = torch.randn(B, device=cuda), torch.randn(B, degree * degree + hw - 1, device=cuda)
     h1 = h.clone().requires_grad_(True)
     s1, c1 = she.sigma_geo_cat(enc, h1, d)
     assert type(s1.grad_fn).__name__.startswith("_sigma_geo_cat")

@@ -16,7 +16,8 @@ pytestmark = pytest.mark.gpu
 
 LAMBDA = 0.1
 CAP = 512
-GRADIENT_CASES = [(1, 4, "mild"), (3, 4, "mild"), (5, 8, "mild"), (17, 5, "hard"), (64, 4, "hard"), (65, 10, "hard"), (130, 8, "hard"), (CAP, 10, "hard")]
+GRADIENT_CASES = [(1, 4, "mild"), (3, 4, "mild"), (5, 8, "mild"), (17, 5, "hard"), (64, 4, "hard"), (65, 10, "hard"), (130, 8, "hard"), (CAP, 10, "hard"),
+                  (33, 6, "hard"), (7, 7, "mild"), (66, 9, "hard")]      # (the kernel is compiled per basis count, 4 .. 10: these three had no case)
 RUN_CASES = [(1, 4, "mild"), (3, 4, "mild"), (5, 8, "mild"), (3, 4, "hard"), (17, 5, "hard"), (64, 4, "hard")]
 SHORT_CASES = [(130, 8, "hard"), (CAP, 10, "hard")]
 
