@@ -388,8 +388,7 @@ int pnr_background_forward(const pnr_background_args* a, pnr_stream_t stream) {
     for (uint32_t l = 0; l < kBgLevels; l++) { p.scale[l] = lp.scale[l]; p.resolution[l] = lp.resolution[l]; }
     p.packed = a->packed; p.out = a->out; p.coords_out = a->coords_out;
     const dim3 grid(cdiv(a->N, 256)), block(256);
-    if (a->table_dtype == PNR_DTYPE_F32) hipLaunchKernelGGL(k_background<float>, grid, block, 0, as_stream(stream), p);
-    else hipLaunchKernelGGL(k_background<__half>, grid, block, 0, as_stream(stream), p);
+    hipLaunchKernelGGL(a->table_dtype == PNR_DTYPE_F32 ? k_background<float> : k_background<__half>, grid, block, 0, as_stream(stream), p);
     return check_launch();
 }
 

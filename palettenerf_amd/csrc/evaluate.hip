@@ -366,8 +366,7 @@ int pnr_frame_metrics(const pnr_metrics_args* args, pnr_stream_t stream) {
     if (a.workspace_bytes < pnr_frame_metrics_workspace_bytes(a.H, a.W) || (reinterpret_cast<uintptr_t>(a.workspace) & 7u)) return PNR_ERR_INVALID;
     const uint64_t tiles = (uint64_t)cdiv(a.H, kMetTile) * cdiv(a.W, kMetTile);
     if (tiles > 0x7fffffffull || (uint64_t)a.H * a.W > 0x7fffffffull) return PNR_ERR_UNSUPPORTED;
-    static bool attr_set[kMaxDevices];
-    if (!ensure_dynamic_lds(k_frame_metrics, kMetLds, attr_set)) return PNR_ERR_LAUNCH;
+    if (!raise_lds<k_frame_metrics>(kMetLds)) return PNR_ERR_LAUNCH;
     MetricsLaunch L;
     L.a = a;
     L.tiles_x = cdiv(a.W, kMetTile);

@@ -147,6 +147,15 @@ int field_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups
     return PNR_OK;
 }
 
+// instantiations by PNR_FIELD_* precision (validated by the callers); the density has no F16X2 form
+typedef decltype(&k_nerf_field_fwd<0>) NerfFieldKernel;
+static NerfFieldKernel nerf_field_kernel(int precision) {
+    if (precision == PNR_FIELD_FP32) return k_nerf_field_fwd<0>;
+    return precision == PNR_FIELD_F16X2 ? k_nerf_field_fwd<2> : k_nerf_field_fwd<1>;
+}
+typedef decltype(&k_nerf_density_fwd<0>) NerfDensityKernel;
+static NerfDensityKernel nerf_density_kernel(int precision) { return precision == PNR_FIELD_FP32 ? k_nerf_density_fwd<0> : k_nerf_density_fwd<1>; }
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -178,13 +187,7 @@ int pnr_nerf_field_forward(const float* enc, const float* dirs, const float* pac
     if (precision != PNR_FIELD_FP32 && precision != PNR_FIELD_F16X3 && precision != PNR_FIELD_F16X2) return PNR_ERR_UNSUPPORTED;
     if (B == 0) return PNR_OK;
     if (!enc || !dirs || !packed || !sigmas || !rgbs) return PNR_ERR_INVALID;
-    const uint32_t grid = field_blocks(B);
-    if (precision == PNR_FIELD_FP32)
-        hipLaunchKernelGGL(k_nerf_field_fwd<0>, dim3(grid), dim3(kFieldThreads), 0, as_stream(stream), enc, dirs, packed, B, sigmas, rgbs, enc_scale);
-    else if (precision == PNR_FIELD_F16X2)
-        hipLaunchKernelGGL(k_nerf_field_fwd<2>, dim3(grid), dim3(kFieldThreads), 0, as_stream(stream), enc, dirs, packed, B, sigmas, rgbs, enc_scale);
-    else
-        hipLaunchKernelGGL(k_nerf_field_fwd<1>, dim3(grid), dim3(kFieldThreads), 0, as_stream(stream), enc, dirs, packed, B, sigmas, rgbs, enc_scale);
+    hipLaunchKernelGGL(nerf_field_kernel(precision), dim3(field_blocks(B)), dim3(kFieldThreads), 0, as_stream(stream), enc, dirs, packed, B, sigmas, rgbs, enc_scale);
     return check_launch();
 }
 
@@ -195,11 +198,8 @@ int pnr_nerf_density_forward(const float* enc, const float* packed, uint32_t B, 
     if (precision != PNR_FIELD_FP32 && precision != PNR_FIELD_F16X3) return PNR_ERR_UNSUPPORTED;
     if (B == 0) return PNR_OK;
     if (!enc || !packed || !sigmas) return PNR_ERR_INVALID;
-    const uint32_t grid = density_blocks(B);
-    if (precision == PNR_FIELD_FP32)
-        hipLaunchKernelGGL(k_nerf_density_fwd<0>, dim3(grid), dim3(kFieldThreads), 0, as_stream(stream), enc, packed, B, scale, sigmas, geo_feat, enc_scale);
-    else
-        hipLaunchKernelGGL(k_nerf_density_fwd<1>, dim3(grid), dim3(kFieldThreads), 0, as_stream(stream), enc, packed, B, scale, sigmas, geo_feat, enc_scale);
+    hipLaunchKernelGGL(nerf_density_kernel(precision), dim3(density_blocks(B)), dim3(kFieldThreads), 0, as_stream(stream), enc, packed, B, scale, sigmas, geo_feat,
+                       enc_scale);
     return check_launch();
 }
 

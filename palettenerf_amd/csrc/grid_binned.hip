@@ -556,8 +556,7 @@ int pnr_grid_encode_backward_binned(const float* grad, const float* inputs, cons
         }
     }
     if (ij.n) {
-        static bool img_attr[kMaxDevices] = {};
-        if (!ensure_dynamic_lds(k_coarse_image, kBinRows * 2 * 8, img_attr)) return PNR_ERR_LAUNCH;
+        if (!raise_lds<k_coarse_image>(kBinRows * 2 * 8)) return PNR_ERR_LAUNCH;
         const uint32_t G = kImgBlocks / ij.n;
         float* partial = reinterpret_cast<float*>(ws + lay.img);
         hipLaunchKernelGGL(k_coarse_image, dim3(G, ij.n), dim3(kImgThreads), kBinRows * 2 * 8, s, grad, inputs, offsets, B, lp, gridtype, align_corners != 0, ij, partial);
@@ -578,10 +577,9 @@ int pnr_grid_encode_backward_binned(const float* grad, const float* inputs, cons
     hipLaunchKernelGGL(k_bin_plan, dim3(1), dim3(1024), 0, s, offsets, L, counts, rec_off, cursor, jobs, n_jobs);
     const uint32_t nb_max = lay.bucket_bound;      // (an upper bound of any level's bucket count: the host does not know the levels' sizes, the offsets live on the device)
     const uint32_t stg_lds = ((3 * nb_max + 1 + 3) & ~3u) * 4 + kStgRecords * (8 + 2 + 2);
-    if (g_opt_scatter_staged && stg_lds <= 160 * 1024) {
-        static bool stg_attr[3][kMaxDevices] = {};
-        if (!ensure_dynamic_lds(k_bin_scatter_staged<0>, stg_lds, stg_attr[0]) || !ensure_dynamic_lds(k_bin_scatter_staged<1>, stg_lds, stg_attr[1]) ||
-            !ensure_dynamic_lds(k_bin_scatter_staged<2>, stg_lds, stg_attr[2])) return PNR_ERR_LAUNCH;
+    if (g_opt_scatter_staged && stg_lds <= kLdsCeiling) {
+        // (to the ceiling, not to stg_lds: that grows with the table, and a later call may bring a larger one)
+        if (!raise_lds<k_bin_scatter_staged<0>>() || !raise_lds<k_bin_scatter_staged<1>>() || !raise_lds<k_bin_scatter_staged<2>>()) return PNR_ERR_LAUNCH;
         const uint32_t gs = cdiv(B, kStgThreads);
         if (nc > ni) hipLaunchKernelGGL(k_bin_scatter_staged<1>, dim3(gs, nc - ni), dim3(kStgThreads), stg_lds, s, grad, inputs, offsets, B, lp, gridtype, ac, cursor, rec_row, rec_val, ni, nb_max);
         if (nm > nc) hipLaunchKernelGGL(k_bin_scatter_staged<2>, dim3(gs, nm - nc), dim3(kStgThreads), stg_lds, s, grad, inputs, offsets, B, lp, gridtype, ac, cursor, rec_row, rec_val, nc, nb_max);
@@ -594,8 +592,7 @@ int pnr_grid_encode_backward_binned(const float* grad, const float* inputs, cons
     if (nm < L) hipLaunchKernelGGL(k_bin_scatter<0>, dim3(gx, L - nm), dim3(kBinThreads), 2 * hist_bytes, s, grad, inputs, offsets, B, lp, gridtype, ac,
                                    cursor, rec_row, rec_val, nm);
     }
-    static bool attr_set[kMaxDevices] = {};
-    if (!ensure_dynamic_lds(k_bin_gather, kBinRows * 2 * 8, attr_set)) return PNR_ERR_LAUNCH;
+    if (!raise_lds<k_bin_gather>(kBinRows * 2 * 8)) return PNR_ERR_LAUNCH;
     const uint32_t gather_blocks = lay.job_bound < 256u ? lay.job_bound : 256u;     // (128 KiB of LDS each: one per CU)
     hipLaunchKernelGGL(k_bin_gather, dim3(gather_blocks), dim3(1024), kBinRows * 2 * 8, s, jobs, n_jobs, rec_row, rec_val, grad_embeddings);
     return check_launch();

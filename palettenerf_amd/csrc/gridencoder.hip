@@ -409,40 +409,38 @@ __global__ void __launch_bounds__(256) k_grid_input_bwd(const T* __restrict__ gr
     if constexpr (sizeof(T) == 4) grad_inputs[t] = r; else grad_inputs[t] = __float2half(r);
 }
 
-template <typename T, uint32_t D>
-static int launch_fwd_c(const float* inputs, const T* emb, const int32_t* offsets, T* outputs, uint32_t B, uint32_t C, uint32_t L,
-                        const LevelParams& lp, T* dy_dx, uint32_t gridtype, bool ac, hipStream_t s) {
-    const dim3 grid(cdiv(B, 256), L), block(256);
-    switch (C) {
-        case 1: hipLaunchKernelGGL((k_grid_fwd<T, D, 1>), grid, block, 0, s, inputs, emb, offsets, outputs, B, L, lp, dy_dx, gridtype, ac); break;
-        case 2: hipLaunchKernelGGL((k_grid_fwd<T, D, 2>), grid, block, 0, s, inputs, emb, offsets, outputs, B, L, lp, dy_dx, gridtype, ac); break;
-        case 4: hipLaunchKernelGGL((k_grid_fwd<T, D, 4>), grid, block, 0, s, inputs, emb, offsets, outputs, B, L, lp, dy_dx, gridtype, ac); break;
-        case 8: hipLaunchKernelGGL((k_grid_fwd<T, D, 8>), grid, block, 0, s, inputs, emb, offsets, outputs, B, L, lp, dy_dx, gridtype, ac); break;
-        default: return PNR_ERR_UNSUPPORTED;  // "GridEncoding: C must be 1, 2, 4, or 8." (gridencoder.cu:354)
-    }
-    return check_launch();
+// The lookup's instantiations, [D - 1][log2 C]: "GridEncoding: D must be 1, 2, 3, 4, or 5", "C must be 1, 2, 4, or 8" (gridencoder.cu:372, :354)
+static int log2_channels(uint32_t C) { return C == 1 ? 0 : C == 2 ? 1 : C == 4 ? 2 : C == 8 ? 3 : -1; }
+template <typename T> using GridFwdKernel = decltype(&k_grid_fwd<T, 1, 1>);
+template <typename T>
+static GridFwdKernel<T> grid_fwd_kernel(uint32_t D, uint32_t C) {
+#define ROW(DV) {k_grid_fwd<T, DV, 1>, k_grid_fwd<T, DV, 2>, k_grid_fwd<T, DV, 4>, k_grid_fwd<T, DV, 8>}
+    static const GridFwdKernel<T> table[5][4] = {ROW(1), ROW(2), ROW(3), ROW(4), ROW(5)};
+#undef ROW
+    const int c = log2_channels(C);
+    return D >= 1 && D <= 5 && c >= 0 ? table[D - 1][c] : nullptr;
+}
+template <typename T> using GridFwdD3C2Kernel = decltype(&k_grid_fwd_d3c2<T, true>);
+template <typename T>
+static GridFwdD3C2Kernel<T> grid_fwd_d3c2_kernel(int layout, int nt) {
+    if (layout == PNR_LAYOUT_ROWS) return k_grid_fwd_d3c2<T, true>;
+    if (nt == 1) return k_grid_fwd_d3c2<T, false, 1>;
+    if (nt == 2) return k_grid_fwd_d3c2<T, false, 2>;
+    return nt == 3 ? k_grid_fwd_d3c2<T, false, 3> : k_grid_fwd_d3c2<T, false>;
 }
 template <typename T>
 static int launch_fwd(const float* inputs, const T* emb, const int32_t* offsets, T* outputs, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
                       const LevelParams& lp, T* dy_dx, uint32_t gridtype, bool ac, int layout, hipStream_t s) {
+    const dim3 grid(cdiv(B, 256), L), block(256);
     if (D == 3 && C == 2 && !dy_dx && g_opt_grid_fast) {
-        const dim3 grid(cdiv(B, 256), L), block(256);
-        if (layout == PNR_LAYOUT_ROWS) hipLaunchKernelGGL((k_grid_fwd_d3c2<T, true>), grid, block, 0, s, inputs, emb, offsets, outputs, B, L, lp, gridtype, ac);
-        else if (g_opt_grid_nt == 1) hipLaunchKernelGGL((k_grid_fwd_d3c2<T, false, 1>), grid, block, 0, s, inputs, emb, offsets, outputs, B, L, lp, gridtype, ac);
-        else if (g_opt_grid_nt == 2) hipLaunchKernelGGL((k_grid_fwd_d3c2<T, false, 2>), grid, block, 0, s, inputs, emb, offsets, outputs, B, L, lp, gridtype, ac);
-        else if (g_opt_grid_nt == 3) hipLaunchKernelGGL((k_grid_fwd_d3c2<T, false, 3>), grid, block, 0, s, inputs, emb, offsets, outputs, B, L, lp, gridtype, ac);
-        else hipLaunchKernelGGL((k_grid_fwd_d3c2<T, false>), grid, block, 0, s, inputs, emb, offsets, outputs, B, L, lp, gridtype, ac);
+        hipLaunchKernelGGL(grid_fwd_d3c2_kernel<T>(layout, g_opt_grid_nt), grid, block, 0, s, inputs, emb, offsets, outputs, B, L, lp, gridtype, ac);
         return check_launch();
     }
     if (layout != PNR_LAYOUT_LEVELS) return PNR_ERR_UNSUPPORTED;
-    switch (D) {
-        case 1: return launch_fwd_c<T, 1>(inputs, emb, offsets, outputs, B, C, L, lp, dy_dx, gridtype, ac, s);
-        case 2: return launch_fwd_c<T, 2>(inputs, emb, offsets, outputs, B, C, L, lp, dy_dx, gridtype, ac, s);
-        case 3: return launch_fwd_c<T, 3>(inputs, emb, offsets, outputs, B, C, L, lp, dy_dx, gridtype, ac, s);
-        case 4: return launch_fwd_c<T, 4>(inputs, emb, offsets, outputs, B, C, L, lp, dy_dx, gridtype, ac, s);
-        case 5: return launch_fwd_c<T, 5>(inputs, emb, offsets, outputs, B, C, L, lp, dy_dx, gridtype, ac, s);
-        default: return PNR_ERR_UNSUPPORTED;  // "GridEncoding: D must be 1, 2, 3, 4, or 5." (gridencoder.cu:372)
-    }
+    const GridFwdKernel<T> kernel = grid_fwd_kernel<T>(D, C);
+    if (!kernel) return PNR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, inputs, emb, offsets, outputs, B, L, lp, dy_dx, gridtype, ac);
+    return check_launch();
 }
 
 // levels whose cells are wide compared with the sample spacing get the run-combining kernel (fp32 only)
@@ -452,37 +450,49 @@ static uint32_t count_coarse_levels(const LevelParams& lp, uint32_t L) {
     return n;
 }
 
-template <typename T, uint32_t D>
-static int launch_bwd_c(const T* grad, const float* inputs, const int32_t* offsets, T* gg, uint32_t B, uint32_t C, uint32_t L,
-                        const LevelParams& lp, uint32_t gridtype, bool ac, hipStream_t s) {
-    const uint32_t nc = (sizeof(T) == 4 || C % 2 == 0) ? count_coarse_levels(lp, L) : 0;
-    const dim3 block(256);
-    // (a half table with an odd C has no coarse levels, nc == 0 above: no run-combining instantiation for it)
-#define PNR_BWD(CV)                                                                                                                        \
-    if constexpr (sizeof(T) == 4 || CV % 2 == 0)                                                                                           \
-        if (nc) hipLaunchKernelGGL((k_grid_bwd<T, D, CV, true>), dim3(cdiv(B, 256), nc), block, 0, s, grad, inputs, offsets, gg, B, L, lp, gridtype, ac, 0u); \
-    if (nc < L) hipLaunchKernelGGL((k_grid_bwd<T, D, CV, false>), dim3(cdiv(B, 256), L - nc), block, 0, s, grad, inputs, offsets, gg, B, L, lp, gridtype, ac, nc)
-    switch (C) {
-        case 1: PNR_BWD(1); break;
-        case 2: PNR_BWD(2); break;
-        case 4: PNR_BWD(4); break;
-        case 8: PNR_BWD(8); break;
-        default: return PNR_ERR_UNSUPPORTED;
-    }
-#undef PNR_BWD
-    return check_launch();
+// The table gradient's instantiations, [COMBINE][D - 1][log2 C].  The hole: a half table with an odd C has no run-combining kernel (its half2 atomics
+// need pairs of channels) -- and no coarse levels either, nc == 0 in launch_bwd.
+template <typename T> using GridBwdKernel = decltype(&k_grid_bwd<T, 1, 2, false>);
+template <typename T, uint32_t D, uint32_t C>
+constexpr GridBwdKernel<T> grid_bwd_combining() {
+    if constexpr (sizeof(T) == 4 || C % 2 == 0) return k_grid_bwd<T, D, C, true>;
+    else return nullptr;
+}
+template <typename T>
+static GridBwdKernel<T> grid_bwd_kernel(uint32_t D, uint32_t C, bool combine) {
+#define ROW(DV) {k_grid_bwd<T, DV, 1, false>, k_grid_bwd<T, DV, 2, false>, k_grid_bwd<T, DV, 4, false>, k_grid_bwd<T, DV, 8, false>}
+#define ROW_COMBINING(DV) {grid_bwd_combining<T, DV, 1>(), k_grid_bwd<T, DV, 2, true>, k_grid_bwd<T, DV, 4, true>, k_grid_bwd<T, DV, 8, true>}
+    static const GridBwdKernel<T> table[2][5][4] = {{ROW(1), ROW(2), ROW(3), ROW(4), ROW(5)},
+                                                    {ROW_COMBINING(1), ROW_COMBINING(2), ROW_COMBINING(3), ROW_COMBINING(4), ROW_COMBINING(5)}};
+#undef ROW
+#undef ROW_COMBINING
+    const int c = log2_channels(C);
+    return D >= 1 && D <= 5 && c >= 0 ? table[combine][D - 1][c] : nullptr;
 }
 template <typename T>
 static int launch_bwd(const T* grad, const float* inputs, const int32_t* offsets, T* gg, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
                       const LevelParams& lp, uint32_t gridtype, bool ac, hipStream_t s) {
-    switch (D) {
-        case 1: return launch_bwd_c<T, 1>(grad, inputs, offsets, gg, B, C, L, lp, gridtype, ac, s);
-        case 2: return launch_bwd_c<T, 2>(grad, inputs, offsets, gg, B, C, L, lp, gridtype, ac, s);
-        case 3: return launch_bwd_c<T, 3>(grad, inputs, offsets, gg, B, C, L, lp, gridtype, ac, s);
-        case 4: return launch_bwd_c<T, 4>(grad, inputs, offsets, gg, B, C, L, lp, gridtype, ac, s);
-        case 5: return launch_bwd_c<T, 5>(grad, inputs, offsets, gg, B, C, L, lp, gridtype, ac, s);
-        default: return PNR_ERR_UNSUPPORTED;
+    const GridBwdKernel<T> plain = grid_bwd_kernel<T>(D, C, false), combining = grid_bwd_kernel<T>(D, C, true);
+    if (!plain) return PNR_ERR_UNSUPPORTED;
+    const uint32_t nc = combining ? count_coarse_levels(lp, L) : 0;
+    auto launch = [&](GridBwdKernel<T> kernel, uint32_t first, uint32_t levels) {   // levels [first, first + levels) through one of the two kernels
+        if (levels) hipLaunchKernelGGL(kernel, dim3(cdiv(B, 256), levels), dim3(256), 0, s, grad, inputs, offsets, gg, B, L, lp, gridtype, ac, first);
+    };
+    launch(combining, 0u, nc);
+    launch(plain, nc, L - nc);
+    return check_launch();
+}
+// pnr_grid_encode_backward behind its checks, for one element type
+template <typename T>
+static int encode_backward(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                           const LevelParams& lp, const void* dy_dx, void* grad_inputs, uint32_t gridtype, bool ac, hipStream_t s) {
+    int rc = launch_bwd<T>(static_cast<const T*>(grad), inputs, offsets, static_cast<T*>(grad_embeddings), B, D, C, L, lp, gridtype, ac, s);
+    if (rc == PNR_OK && dy_dx) {
+        hipLaunchKernelGGL(k_grid_input_bwd<T>, dim3(cdiv(B * D, 256)), dim3(256), 0, s, static_cast<const T*>(grad), static_cast<const T*>(dy_dx),
+                           static_cast<T*>(grad_inputs), B, D, C, L);
+        rc = check_launch();
     }
+    return rc;
 }
 
 }  // namespace pnr
@@ -537,26 +547,8 @@ int pnr_grid_encode_backward(const void* grad, const float* inputs, const void* 
     if (!grad || !inputs || !offsets || !grad_embeddings) return PNR_ERR_INVALID;
     if ((dy_dx == nullptr) != (grad_inputs == nullptr)) return PNR_ERR_INVALID;
     const LevelParams lp = make_level_params(L, S, H);
-    hipStream_t s = as_stream(stream);
-    int rc;
-    if (dtype == PNR_DTYPE_F32) {
-        rc = launch_bwd<float>(static_cast<const float*>(grad), inputs, offsets, static_cast<float*>(grad_embeddings), B, D, C, L, lp, gridtype,
-                               align_corners != 0, s);
-        if (rc == PNR_OK && dy_dx) {
-            hipLaunchKernelGGL(k_grid_input_bwd<float>, dim3(cdiv(B * D, 256)), dim3(256), 0, s, static_cast<const float*>(grad),
-                               static_cast<const float*>(dy_dx), static_cast<float*>(grad_inputs), B, D, C, L);
-            rc = check_launch();
-        }
-    } else {
-        rc = launch_bwd<__half>(static_cast<const __half*>(grad), inputs, offsets, static_cast<__half*>(grad_embeddings), B, D, C, L, lp,
-                                gridtype, align_corners != 0, s);
-        if (rc == PNR_OK && dy_dx) {
-            hipLaunchKernelGGL(k_grid_input_bwd<__half>, dim3(cdiv(B * D, 256)), dim3(256), 0, s, static_cast<const __half*>(grad),
-                               static_cast<const __half*>(dy_dx), static_cast<__half*>(grad_inputs), B, D, C, L);
-            rc = check_launch();
-        }
-    }
-    return rc;
+    const auto impl = dtype == PNR_DTYPE_F32 ? encode_backward<float> : encode_backward<__half>;
+    return impl(grad, inputs, offsets, grad_embeddings, B, D, C, L, lp, dy_dx, grad_inputs, gridtype, align_corners != 0, as_stream(stream));
 }
 
 }  // extern "C"

@@ -105,6 +105,15 @@ static uint32_t wgrad_blocks(uint32_t B) {
     return want < 1 ? 1 : (want > 512 ? 512 : want);
 }
 
+// The weight-gradient launch for one pair of element types; its instantiations, [in_dim > 32][out_dim > 32] (one or two 32-wide tiles on either side)
+template <typename TX, typename TY>
+static void launch_wgrad(const void* x, const void* dy, uint32_t B, uint32_t in_dim, uint32_t out_dim, float* partial, uint32_t blocks, hipStream_t s) {
+    typedef decltype(&k_linear_wgrad<TX, TY, 1, 1>) WgradKernel;
+    static const WgradKernel table[2][2] = {{k_linear_wgrad<TX, TY, 1, 1>, k_linear_wgrad<TX, TY, 1, 2>}, {k_linear_wgrad<TX, TY, 2, 1>, k_linear_wgrad<TX, TY, 2, 2>}};
+    hipLaunchKernelGGL(table[in_dim > 32][out_dim > 32], dim3(blocks), dim3(kLinThreads), 0, s, static_cast<const TX*>(x), static_cast<const TY*>(dy), B, in_dim, out_dim,
+                       partial);
+}
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -130,23 +139,9 @@ int pnr_linear_wgrad(const void* x, int x_dtype, const void* dy, int dy_dtype, u
     if (workspace_bytes < pnr_linear_wgrad_workspace_bytes(B, in_dim, out_dim)) return PNR_ERR_INVALID;
     const uint32_t blocks = wgrad_blocks(B);
     float* partial = static_cast<float*>(workspace);
-    const int ti = in_dim > 32 ? 2 : 1, to = out_dim > 32 ? 2 : 1;
-#define PNR_WG(TX, TY, TIV, TOV)                                                                                                  \
-    hipLaunchKernelGGL((k_linear_wgrad<TX, TY, TIV, TOV>), dim3(blocks), dim3(kLinThreads), 0, s, static_cast<const TX*>(x),       \
-                       static_cast<const TY*>(dy), B, in_dim, out_dim, partial)
-#define PNR_WG_T(TX, TY)                                                        \
-    do {                                                                        \
-        if (ti == 1 && to == 1) PNR_WG(TX, TY, 1, 1);                           \
-        else if (ti == 2 && to == 1) PNR_WG(TX, TY, 2, 1);                      \
-        else if (ti == 1 && to == 2) PNR_WG(TX, TY, 1, 2);                      \
-        else PNR_WG(TX, TY, 2, 2);                                              \
-    } while (0)
-    if (x_dtype == PNR_DTYPE_F32 && dy_dtype == PNR_DTYPE_F32) PNR_WG_T(float, float);
-    else if (x_dtype == PNR_DTYPE_F16 && dy_dtype == PNR_DTYPE_F16) PNR_WG_T(__half, __half);
-    else if (x_dtype == PNR_DTYPE_F32) PNR_WG_T(float, __half);
-    else PNR_WG_T(__half, float);
-#undef PNR_WG_T
-#undef PNR_WG
+    const bool x32 = x_dtype == PNR_DTYPE_F32, dy32 = dy_dtype == PNR_DTYPE_F32;
+    const auto launch = x32 ? (dy32 ? launch_wgrad<float, float> : launch_wgrad<float, __half>) : (dy32 ? launch_wgrad<__half, float> : launch_wgrad<__half, __half>);
+    launch(x, dy, B, in_dim, out_dim, partial, blocks, s);
     hipLaunchKernelGGL(k_linear_wgrad_reduce, dim3(cdiv(n, 32)), dim3(256), 0, s, partial, blocks, n, dw, accumulate);
     return check_launch();
 }

@@ -1046,6 +1046,36 @@ int mlp_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, 
     return PNR_OK;
 }
 
+// The stack kernels' instantiations, [n_layers - 2][input tiles - 1][output tiles - 1][hidden activation]: make_plan admits nothing outside these
+// bounds.  Every one takes its weights in dynamic LDS, so an entry carries the flags of its raised limit; a null kernel = no such instantiation.
+typedef decltype(&k_mlp_fwd<2, 1, 1, 0>) MlpFwdKernel;
+typedef decltype(&k_mlp_bwd<2, 1, 1, 0>) MlpBwdKernel;
+#ifdef PNR_MLP_MINI   /* compile-time experiments only: one instantiation per kernel, so that a resource-usage build takes seconds */
+#define STACK(K, NL, TI, TO) {{K<3, 1, 1, 0>, {}}, {K<3, 1, 1, 0>, {}}}
+#else
+#define STACK(K, NL, TI, TO) {{K<NL, TI, TO, 0>, {}}, {K<NL, TI, TO, 1>, {}}}
+#endif
+#define HOLE {{nullptr, {}}, {nullptr, {}}}
+#define ALL_STACKS(K) {{{STACK(K, 2, 1, 1), STACK(K, 2, 1, 2)}, {STACK(K, 2, 2, 1), STACK(K, 2, 2, 2)}}, \
+                       {{STACK(K, 3, 1, 1), STACK(K, 3, 1, 2)}, {STACK(K, 3, 2, 1), STACK(K, 3, 2, 2)}}}
+static LdsKernel<MlpFwdKernel> g_mlp_fwd[2][2][2][2] = ALL_STACKS(k_mlp_fwd);
+static LdsKernel<MlpFwdKernel> g_mlp_fwd_h[2][2][2][2] = ALL_STACKS(k_mlp_fwd_h);
+// The backward keeps both orientations of every layer in LDS: three layers with two tiles at both ends (166 944 bytes) never get past its LDS check ...
+static LdsKernel<MlpBwdKernel> g_mlp_bwd[2][2][2][2] = {{{STACK(k_mlp_bwd, 2, 1, 1), STACK(k_mlp_bwd, 2, 1, 2)}, {STACK(k_mlp_bwd, 2, 2, 1), STACK(k_mlp_bwd, 2, 2, 2)}},
+                                                        {{STACK(k_mlp_bwd, 3, 1, 1), STACK(k_mlp_bwd, 3, 1, 2)}, {STACK(k_mlp_bwd, 3, 2, 1), HOLE}}};
+// ... and the split-fp16 backward exists where it holds its tile without (much) scratch: two layers unless both ends are 64 wide, three layers with
+// 32-wide ends -- every stack of both fields; the wider instantiations would spill twice what the fp32 ones do, those stacks stay on k_mlp_bwd
+static LdsKernel<MlpBwdKernel> g_mlp_bwd_h[2][2][2][2] = {{{STACK(k_mlp_bwd_h, 2, 1, 1), STACK(k_mlp_bwd_h, 2, 1, 2)}, {STACK(k_mlp_bwd_h, 2, 2, 1), HOLE}},
+                                                          {{STACK(k_mlp_bwd_h, 3, 1, 1), HOLE}, {HOLE, HOLE}}};
+#undef ALL_STACKS
+#undef HOLE
+#undef STACK
+template <typename F>
+static LdsKernel<F>* mlp_kernel(LdsKernel<F> (&table)[2][2][2][2], const MlpPlan& p) {
+    LdsKernel<F>* k = &table[p.n_layers - 2][tiles32(p.dims[0]) - 1][tiles32(p.dims[p.n_layers]) - 1][p.act];
+    return k->fn ? k : nullptr;
+}
+
 }  // namespace pnr
 
 using namespace pnr;
@@ -1065,73 +1095,6 @@ int pnr_mlp_pack(const pnr_mlp_desc* desc, const float* w0, const float* w1, con
     hipLaunchKernelGGL(k_mlp_pack, dim3(2 * p.n_layers, kPackChunks), dim3(256), 0, as_stream(stream), p, ws, packed);
     return check_launch();
 }
-
-#define PNR_MLP_DISPATCH(KERNEL, NLV, TIV, TOV, ...)                                                                                           \
-    do {                                                                                                                                       \
-        if (p.act == 0) {                                                                                                                      \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL<NLV, TIV, TOV, 0>), hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                    (int)lds) != hipSuccess)                                                                                   \
-                return PNR_ERR_LAUNCH;                                                                                                         \
-            hipLaunchKernelGGL((KERNEL<NLV, TIV, TOV, 0>), dim3(grid), dim3(kMlpThreads), lds, s, __VA_ARGS__);                                \
-        } else {                                                                                                                               \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL<NLV, TIV, TOV, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                                    (int)lds) != hipSuccess)                                                                                   \
-                return PNR_ERR_LAUNCH;                                                                                                         \
-            hipLaunchKernelGGL((KERNEL<NLV, TIV, TOV, 1>), dim3(grid), dim3(kMlpThreads), lds, s, __VA_ARGS__);                                \
-        }                                                                                                                                      \
-    } while (0)
-#ifdef PNR_MLP_MINI   /* compile-time experiments only: one instantiation, so that a resource-usage build takes seconds */
-#define PNR_MLP_SWITCH(KERNEL, ...) do { hipLaunchKernelGGL((KERNEL<3, 1, 1, 0>), dim3(grid), dim3(kMlpThreads), lds, s, __VA_ARGS__); } while (0)
-#define PNR_MLP_SWITCH_BWD(KERNEL, ...) PNR_MLP_SWITCH(KERNEL, __VA_ARGS__)
-#define PNR_MLP_SWITCH_BWD_H(KERNEL, ...) PNR_MLP_SWITCH(KERNEL, __VA_ARGS__)
-#else
-// The backward keeps both orientations of every layer in LDS: three layers with two tiles at both ends (166 944 bytes) never get past its LDS check, so
-// that stack has no backward instantiation ...
-#define PNR_MLP_SWITCH_BWD(KERNEL, ...)                                                               \
-    do {                                                                                              \
-        const int ti = (int)tiles32(p.dims[0]), to = (int)tiles32(p.dims[p.n_layers]);                \
-        if (p.n_layers == 2) {                                                                        \
-            if (ti == 1 && to == 1) PNR_MLP_DISPATCH(KERNEL, 2, 1, 1, __VA_ARGS__);                   \
-            else if (ti == 1) PNR_MLP_DISPATCH(KERNEL, 2, 1, 2, __VA_ARGS__);                         \
-            else if (to == 1) PNR_MLP_DISPATCH(KERNEL, 2, 2, 1, __VA_ARGS__);                         \
-            else PNR_MLP_DISPATCH(KERNEL, 2, 2, 2, __VA_ARGS__);                                      \
-        } else {                                                                                      \
-            if (ti == 1 && to == 1) PNR_MLP_DISPATCH(KERNEL, 3, 1, 1, __VA_ARGS__);                   \
-            else if (ti == 1) PNR_MLP_DISPATCH(KERNEL, 3, 1, 2, __VA_ARGS__);                         \
-            else if (to == 1) PNR_MLP_DISPATCH(KERNEL, 3, 2, 1, __VA_ARGS__);                         \
-            else return PNR_ERR_UNSUPPORTED;                                                          \
-        }                                                                                             \
-    } while (0)
-// ... and the split-fp16 backward is instantiated for the stacks mlp_backward_impl sends to it (h_fits), no others
-#define PNR_MLP_SWITCH_BWD_H(KERNEL, ...)                                                             \
-    do {                                                                                              \
-        const int ti = (int)tiles32(p.dims[0]), to = (int)tiles32(p.dims[p.n_layers]);                \
-        if (p.n_layers == 2) {                                                                        \
-            if (ti == 1 && to == 1) PNR_MLP_DISPATCH(KERNEL, 2, 1, 1, __VA_ARGS__);                   \
-            else if (ti == 1) PNR_MLP_DISPATCH(KERNEL, 2, 1, 2, __VA_ARGS__);                         \
-            else if (to == 1) PNR_MLP_DISPATCH(KERNEL, 2, 2, 1, __VA_ARGS__);                         \
-            else return PNR_ERR_UNSUPPORTED;                                                          \
-        } else {                                                                                      \
-            if (ti == 1 && to == 1) PNR_MLP_DISPATCH(KERNEL, 3, 1, 1, __VA_ARGS__);                   \
-            else return PNR_ERR_UNSUPPORTED;                                                          \
-        }                                                                                             \
-    } while (0)
-#define PNR_MLP_SWITCH(KERNEL, ...)                                                                   \
-    do {                                                                                              \
-        const int ti = (int)tiles32(p.dims[0]), to = (int)tiles32(p.dims[p.n_layers]);                \
-        if (p.n_layers == 2) {                                                                        \
-            if (ti == 1 && to == 1) PNR_MLP_DISPATCH(KERNEL, 2, 1, 1, __VA_ARGS__);                   \
-            else if (ti == 1) PNR_MLP_DISPATCH(KERNEL, 2, 1, 2, __VA_ARGS__);                         \
-            else if (to == 1) PNR_MLP_DISPATCH(KERNEL, 2, 2, 1, __VA_ARGS__);                         \
-            else PNR_MLP_DISPATCH(KERNEL, 2, 2, 2, __VA_ARGS__);                                      \
-        } else {                                                                                      \
-            if (ti == 1 && to == 1) PNR_MLP_DISPATCH(KERNEL, 3, 1, 1, __VA_ARGS__);                   \
-            else if (ti == 1) PNR_MLP_DISPATCH(KERNEL, 3, 1, 2, __VA_ARGS__);                         \
-            else if (to == 1) PNR_MLP_DISPATCH(KERNEL, 3, 2, 1, __VA_ARGS__);                         \
-            else PNR_MLP_DISPATCH(KERNEL, 3, 2, 2, __VA_ARGS__);                                      \
-        }                                                                                             \
-    } while (0)
-#endif
 
 // lm_levels: 0 = x is row-major [B, dims[0]]; 16 = x is a level-major encoder output [16][B][2] followed by x_tail [B, dims[0] - 32]
 // The launches move their tiles as 16-byte requests: every activation array must start on a 16-byte boundary (torch allocations do; a view that starts inside one may
@@ -1162,12 +1125,12 @@ static int mlp_forward_impl(const pnr_mlp_desc* desc, const float* packed, const
     if ((uint64_t)B * 64 >= (1ull << 32)) return PNR_ERR_UNSUPPORTED;   // element indices are 32-bit
     if (int rc = plan_sources(p, lm_levels, x_tail)) return rc;
     const size_t lds = ((size_t)p.wt_off[0] + kMlpWaves * kStageFloats) * 4;
-    if (lds > 160 * 1024) return PNR_ERR_UNSUPPORTED;
+    if (lds > kLdsCeiling) return PNR_ERR_UNSUPPORTED;
     if (!arrays_ok({x, x_tail, y}, B, p)) return PNR_ERR_ALIGNMENT;
-    hipStream_t s = as_stream(stream);
-    const uint32_t grid = mlp_fwd_blocks(B);
-    if (g_opt_mlp_f16x3) PNR_MLP_SWITCH(k_mlp_fwd_h, p, packed, x, x_tail, B, y);
-    else PNR_MLP_SWITCH(k_mlp_fwd, p, packed, x, x_tail, B, y);
+    LdsKernel<MlpFwdKernel>* kernel = mlp_kernel(g_opt_mlp_f16x3 ? g_mlp_fwd_h : g_mlp_fwd, p);
+    if (!kernel) return PNR_ERR_UNSUPPORTED;
+    if (!kernel->raise_lds()) return PNR_ERR_LAUNCH;
+    hipLaunchKernelGGL(kernel->fn, dim3(mlp_fwd_blocks(B)), dim3(kMlpThreads), lds, as_stream(stream), p, packed, x, x_tail, B, y);
     return check_launch();
 }
 
@@ -1201,21 +1164,19 @@ static int mlp_backward_impl(const pnr_mlp_desc* desc, const float* packed, cons
     if (!p.out_act) y = nullptr;
     if ((uint64_t)B * 64 >= (1ull << 32)) return PNR_ERR_UNSUPPORTED;   // element indices are 32-bit
     if (workspace_bytes < pnr_mlp_backward_workspace_bytes(desc, B)) return PNR_ERR_INVALID;
-    const size_t lds = ((size_t)p.packed_floats + kMlpWaves * 2 * kStageFloats) * 4;
-    if (lds > 160 * 1024 || p.dw_floats > (uint32_t)(kMlpWaves * 2 * kStageFloats)) return PNR_ERR_UNSUPPORTED;
-    const uint32_t blocks = mlp_blocks(B), grid = blocks;
+    size_t lds = ((size_t)p.packed_floats + kMlpWaves * 2 * kStageFloats) * 4;
+    if (lds > kLdsCeiling || p.dw_floats > (uint32_t)(kMlpWaves * 2 * kStageFloats)) return PNR_ERR_UNSUPPORTED;
+    const uint32_t grid = mlp_blocks(B);
     float* partial = static_cast<float*>(workspace);
     if (!arrays_ok({x, x_tail, y, dy, dx}, B, p)) return PNR_ERR_ALIGNMENT;
-    // the split-fp16 backward where it holds its tile without (much) scratch: two layers unless both ends are 64 wide, three layers with 32-wide ends --
-    // every stack of both fields; the wider instantiations spill twice what the fp32 ones do and stay on those
-    const uint32_t ti = tiles32(p.dims[0]), to = tiles32(p.dims[p.n_layers]);
-    const bool h_fits = p.n_layers == 2 ? !(ti == 2 && to == 2) : (ti == 1 && to == 1);
-    const size_t lds_h = lds + (size_t)kMlpWaves * 33 * (32 * ti + 1) * 4;       // + the X tiles of k_mlp_bwd_h
-    if (g_opt_mlp_f16x3 && h_fits && lds_h <= 160 * 1024) {
-        const size_t lds_fp32 = lds;
-        (void)lds_fp32;
-        { const size_t lds = lds_h; PNR_MLP_SWITCH_BWD_H(k_mlp_bwd_h, p, packed, x, x_tail, dy, y, B, dx, partial); }
-    } else PNR_MLP_SWITCH_BWD(k_mlp_bwd, p, packed, x, x_tail, dy, y, B, dx, partial);
+    // the split-fp16 backward where there is one and its X tiles fit behind the rest
+    const size_t lds_h = lds + (size_t)kMlpWaves * 33 * (32 * tiles32(p.dims[0]) + 1) * 4;
+    LdsKernel<MlpBwdKernel>* kernel = g_opt_mlp_f16x3 && lds_h <= kLdsCeiling ? mlp_kernel(g_mlp_bwd_h, p) : nullptr;
+    if (kernel) lds = lds_h;
+    else kernel = mlp_kernel(g_mlp_bwd, p);
+    if (!kernel) return PNR_ERR_UNSUPPORTED;
+    if (!kernel->raise_lds()) return PNR_ERR_LAUNCH;
+    hipLaunchKernelGGL(kernel->fn, dim3(grid), dim3(kMlpThreads), lds, s, p, packed, x, x_tail, dy, y, B, dx, partial);
     hipLaunchKernelGGL(k_mlp_dw_reduce, dim3(cdiv(p.dw_floats, 32)), dim3(256), 0, s, partial, grid, p, gr);
     return check_launch();
 }

@@ -1021,6 +1021,32 @@ int pnr_palette_field_stages_aux(uint32_t num_basis, uint32_t clip_dim, int pred
 
 }  // extern "C"
 
+// The field kernel's instantiations.  An entry holds the kernel (with its dynamic-LDS flags: every one takes 100 KiB and more) and the block size that goes
+// with its WAVES; nullptr = no such instantiation.  `watch`: the fp16 kernel that watches its split operands for overflow; nb4 / wide / x2 as the caller
+// derives them (nb4 and x2 imply fp16 and no watch, wide implies nb4).
+typedef void (*PalKernel)(PalArgs);
+struct PalEntry { LdsKernel<PalKernel> kernel; uint32_t threads; };
+static PalEntry* palette_field_kernel(bool fp16, bool watch, int edit_mode, bool nb4, bool wide, bool x2) {
+#define K(PREC, EDIT, CHECK, NB, WAVES) {{k_palette_field_fwd<PREC, EDIT, CHECK, NB, WAVES>, {}}, WAVES * 64}
+#define HOLE {{nullptr, {}}, 0}
+    // any number of bases, 8 waves: [fp32 | fp16 | fp16 watched][edit mode] (the network-heads row, mode 3, is never watched)
+    static PalEntry general[3][4] = {{K(0, 0, false, 0, 8), K(0, 1, false, 0, 8), K(0, 2, false, 0, 8), K(0, 3, false, 0, 8)},
+                                     {K(1, 0, false, 0, 8), K(1, 1, false, 0, 8), K(1, 2, false, 0, 8), K(1, 3, false, 0, 8)},
+                                     {K(1, 0, true, 0, 8), K(1, 1, true, 0, 8), K(1, 2, true, 0, 8), HOLE}};
+    // the shipped default of 4 bases (main_palette.py:76), specialised epilogue: [edit mode][wide]; mode 3 has the wide form only
+    static PalEntry four[4][2] = {{K(1, 0, false, 4, 8), K(1, 0, false, 4, PNR_PAL_WIDE_WAVES)},
+                                  {K(1, 1, false, 4, 8), K(1, 1, false, 4, PNR_PAL_WIDE_WAVES)},
+                                  {K(1, 2, false, 4, 8), K(1, 2, false, 4, PNR_PAL_WIDE_WAVES)},
+                                  {HOLE, K(1, 3, false, 4, PNR_PAL_WIDE_WAVES)}};
+    static PalEntry four_x2[2] = {K(2, 0, false, 4, 8), K(2, 0, false, 4, PNR_PAL_WIDE_WAVES)};   // [wide]; F16X2 exists without an edit head only
+#undef K
+#undef HOLE
+    PalEntry* e = &general[fp16 ? (watch ? 2 : 1) : 0][edit_mode];
+    if (x2) e = &four_x2[wide];
+    else if (nb4 && four[edit_mode][wide].kernel.fn) e = &four[edit_mode][wide];   // (mode 3 on 8 waves: the general kernel)
+    return e->kernel.fn ? e : nullptr;
+}
+
 // internal (frame.hip): the field launch with the wide-kernel switch given by the caller -- a frame call keeps the value its submit half read
 int pnr_internal_palette_field_forward(const pnr_palette_field_args* a, pnr_stream_t stream, int waves12) {
     if (!a) return PNR_ERR_INVALID;
@@ -1052,7 +1078,6 @@ int pnr_internal_palette_field_forward(const pnr_palette_field_args* a, pnr_stre
     const uint32_t waves = wide ? (uint32_t)PNR_PAL_WIDE_WAVES : 8u;
     const uint32_t ntiles = cdiv(rows_ub ? rows_ub : 1, 28);   // wave tiles (a wave tile holds 28 ... 32 rows when it holds whole rays): dealt wave-major, see the kernel
     const uint32_t grid = ntiles < 256u ? ntiles : 256u;
-    constexpr uint32_t kLdsLimit = 160 * 1024;
     // staging slab for coalesced aux rows (8-wave kernels): 8 waves x 32 rows x (aux_stride + 3) floats, when it fits next to the weights.  The wide kernels
     // keep their rows in registers: `stage_stride` only tells them that the fused tail is available, their LDS holds 96 + 576 floats per wave behind the weights (per-row weights; the rows of up to 16 rays with 2 .. 8 samples each)
     const bool stages = wide || (a->aux_stride == pnr_palette_aux_channels(a->num_basis, a->clip_dim) && pnr_palette_field_stages_aux(a->num_basis, a->clip_dim, pp.pred_clip));
@@ -1091,35 +1116,10 @@ int pnr_internal_palette_field_forward(const pnr_palette_field_args* a, pnr_stre
     ka.rays_alive = fuse ? a->rays_alive : nullptr; ka.weights_sum = fuse ? a->weights_sum : nullptr; ka.aux_map = fuse ? a->aux_map : nullptr;
     ka.T_thresh = a->T_thresh; ka.xyzs = a->xyzs; ka.ep = ep_dev; ka.overflow_flag = a->overflow_flag; ka.tile_counter = static_cast<uint32_t*>(a->tile_counter);
     ka.rs = rs;
-    static bool attr_set[4][4][kMaxDevices] = {};   // [PREC + 2 * CHECK][EDIT]
-#define PNR_LAUNCH_PAL(PREC, EDIT, CHECK) PNR_LAUNCH_PAL_NB(PREC, EDIT, CHECK, 0, 8, attr_set[PREC + (CHECK ? 2 : 0)][EDIT])
-#define PNR_LAUNCH_PAL_NB(PREC, EDIT, CHECK, NB, WAVES, FLAGS)                                                                                 \
-    do {                                                                                                                                       \
-        if (!ensure_dynamic_lds(k_palette_field_fwd<PREC, EDIT, CHECK, NB, WAVES>, kLdsLimit, FLAGS)) return PNR_ERR_LAUNCH;                   \
-        hipLaunchKernelGGL((k_palette_field_fwd<PREC, EDIT, CHECK, NB, WAVES>), dim3(grid), dim3(WAVES * 64), lds, s, ka);                     \
-    } while (0)
-    if (fp16 && a->overflow_flag) {   // the instantiation that watches its split operands
-        if (edit_mode == 0) PNR_LAUNCH_PAL(1, 0, true); else if (edit_mode == 1) PNR_LAUNCH_PAL(1, 1, true); else PNR_LAUNCH_PAL(1, 2, true);
-    } else if (fp16) {
-        static bool attr_nb4[8][kMaxDevices] = {};
-        // the shipped default of 4 bases (main_palette.py:76): specialised epilogue, 12-wave workgroups when the staging fits
-        if (x2 && wide) PNR_LAUNCH_PAL_NB(2, 0, false, 4, PNR_PAL_WIDE_WAVES, attr_nb4[6]);
-        else if (x2) PNR_LAUNCH_PAL_NB(2, 0, false, 4, 8, attr_nb4[7]);
-        else if (edit_mode == 3 && nb4 && wide) { static bool attr_heads[kMaxDevices] = {}; PNR_LAUNCH_PAL_NB(1, 3, false, 4, PNR_PAL_WIDE_WAVES, attr_heads); }
-        else if (edit_mode == 3) PNR_LAUNCH_PAL(1, 3, false);
-        else if (nb4 && wide && edit_mode == 0) PNR_LAUNCH_PAL_NB(1, 0, false, 4, PNR_PAL_WIDE_WAVES, attr_nb4[0]);
-        else if (nb4 && wide && edit_mode == 1) PNR_LAUNCH_PAL_NB(1, 1, false, 4, PNR_PAL_WIDE_WAVES, attr_nb4[1]);
-        else if (nb4 && wide) PNR_LAUNCH_PAL_NB(1, 2, false, 4, PNR_PAL_WIDE_WAVES, attr_nb4[2]);
-        else if (nb4 && edit_mode == 0) PNR_LAUNCH_PAL_NB(1, 0, false, 4, 8, attr_nb4[3]);
-        else if (nb4 && edit_mode == 1) PNR_LAUNCH_PAL_NB(1, 1, false, 4, 8, attr_nb4[4]);
-        else if (nb4) PNR_LAUNCH_PAL_NB(1, 2, false, 4, 8, attr_nb4[5]);
-        else if (edit_mode == 0) PNR_LAUNCH_PAL(1, 0, false); else if (edit_mode == 1) PNR_LAUNCH_PAL(1, 1, false); else PNR_LAUNCH_PAL(1, 2, false);
-    } else {
-        if (edit_mode == 0) PNR_LAUNCH_PAL(0, 0, false); else if (edit_mode == 1) PNR_LAUNCH_PAL(0, 1, false); else if (edit_mode == 2) PNR_LAUNCH_PAL(0, 2, false);
-        else PNR_LAUNCH_PAL(0, 3, false);
-    }
-#undef PNR_LAUNCH_PAL
-#undef PNR_LAUNCH_PAL_NB
+    PalEntry* entry = palette_field_kernel(fp16, fp16 && a->overflow_flag, edit_mode, nb4, wide, x2);
+    if (!entry) return PNR_ERR_UNSUPPORTED;
+    if (!entry->kernel.raise_lds()) return PNR_ERR_LAUNCH;
+    hipLaunchKernelGGL(entry->kernel.fn, dim3(grid), dim3(entry->threads), lds, s, ka);
     if (edit_slot >= 0 && hipEventRecord(g_edit_ring[current_device()].used[edit_slot], s) != hipSuccess) return PNR_ERR_LAUNCH;
     return check_launch();
 }

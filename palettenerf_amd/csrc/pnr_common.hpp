@@ -33,14 +33,28 @@ int occupancy_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgr
 // One process may drive several GPUs: function attributes and events belong to a device, so one-time set-up is tracked per device id.
 constexpr int kMaxDevices = 64;
 inline int current_device() { int d = 0; if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) d = 0; return d; }
-// raise a kernel's dynamic-LDS limit once per device; false = the runtime refused
-template <typename K>
-inline bool ensure_dynamic_lds(K kernel, uint32_t bytes, bool* done /* [kMaxDevices] */) {
-    const int d = current_device();
-    if (done[d]) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return false;
-    done[d] = true;
-    return true;
+// Host launch path.  An entry point with several instantiations of its kernel has one selector, `<entry>_kernel(run-time arguments)`: a pure function
+// that reads the kernel out of a static table (or a short chain of returns) -- the table IS the set of compiled instantiations, nullptr = there is none
+// (PNR_ERR_UNSUPPORTED) -- and after it one launch statement.  A kernel that takes more dynamic LDS than the 64 KiB default is held as an LdsKernel:
+// the once-per-device "limit raised" flags live beside the pointer, and the limit goes to a fixed ceiling per kernel (all of a gfx950 workgroup's
+// LDS, or the kernel's own constant), never to the size one call happened to ask for.
+constexpr uint32_t kLdsCeiling = 160 * 1024;
+template <typename F>
+struct LdsKernel {
+    F fn;
+    bool raised[kMaxDevices];
+    bool raise_lds(uint32_t ceiling = kLdsCeiling) {   // false = the runtime refused
+        const int d = current_device();
+        if (raised[d]) return true;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ceiling) != hipSuccess) return false;
+        return raised[d] = true;
+    }
+};
+// ... and for a kernel named in the source, the same keyed on the kernel itself: raise_lds<k_foo<1>>(ceiling)
+template <auto K>
+inline bool raise_lds(uint32_t ceiling = kLdsCeiling) {
+    static LdsKernel<decltype(K)> kernel = {K, {}};
+    return kernel.raise_lds(ceiling);
 }
 
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(hi, fmaxf(lo, x)); }

@@ -94,8 +94,7 @@ extern "C" int pnr_present_frame(const pnr_present_args* args, pnr_stream_t stre
     const int rv = (quads && (src & 15u) == 0 && (a.clip_stride & 3u) == 0) ? 4 : ((quads && (src & 7u) == 0 && (a.clip_stride & 1u) == 0) ? 2 : 1);
     const int wide_store = (quads && (reinterpret_cast<uintptr_t>(a.out_clip) & 15u) == 0) ? 1 : 0;
     const dim3 grid(cdiv((uint32_t)n_dst * 8, kPresentBlock)), block(kPresentBlock);
-    if (rv == 4) hipLaunchKernelGGL((k_present_frame<8, 4>), grid, block, 0, s, a, scale_y, scale_x, wide_store);
-    else if (rv == 2) hipLaunchKernelGGL((k_present_frame<8, 2>), grid, block, 0, s, a, scale_y, scale_x, wide_store);
-    else hipLaunchKernelGGL((k_present_frame<8, 1>), grid, block, 0, s, a, scale_y, scale_x, wide_store);
+    const auto kernel = rv == 4 ? k_present_frame<8, 4> : (rv == 2 ? k_present_frame<8, 2> : k_present_frame<8, 1>);   // floats per read of a feature row
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, a, scale_y, scale_x, wide_store);
     return check_launch();
 }

@@ -627,6 +627,32 @@ static bool mip_usable(const void* mip, uint32_t C, uint32_t H) {
     return mip && (H % 4) == 0 && pnr_occupancy_mip_bytes(C, H) <= 64 * 1024;
 }
 
+// The march kernels' instantiations, [mip][pow2]: the occupancy mip staged in LDS or not, cell sizes that are powers of two or not
+#define ROW(K, MIPV) {K<MIPV, false>, K<MIPV, true>}
+typedef decltype(&k_march_rays<false, false>) MarchRaysKernel;
+static MarchRaysKernel march_rays_kernel(bool mip, bool pow2) {
+    static const MarchRaysKernel table[2][2] = {ROW(k_march_rays, false), ROW(k_march_rays, true)};
+    return table[mip][pow2];
+}
+typedef decltype(&k_march_train_count<false, false>) TrainCountKernel;
+static TrainCountKernel march_train_count_kernel(bool mip, bool pow2) {
+    static const TrainCountKernel table[2][2] = {ROW(k_march_train_count, false), ROW(k_march_train_count, true)};
+    return table[mip][pow2];
+}
+typedef decltype(&k_march_train_write<false, false>) TrainWriteKernel;
+static TrainWriteKernel march_train_write_kernel(bool mip, bool pow2) {
+    static const TrainWriteKernel table[2][2] = {ROW(k_march_train_write, false), ROW(k_march_train_write, true)};
+    return table[mip][pow2];
+}
+#undef ROW
+typedef decltype(&k_march_train_count_coop<false, false, 1>) TrainCountCoopKernel;
+static TrainCountCoopKernel march_train_count_coop_kernel(bool mip, bool pow2, bool four) {   // [mip][pow2][one ray per wave | four]
+#define ROW(MIPV, P2V) {k_march_train_count_coop<MIPV, P2V, 1>, k_march_train_count_coop<MIPV, P2V, 4>}
+    static const TrainCountCoopKernel table[2][2][2] = {{ROW(false, false), ROW(false, true)}, {ROW(true, false), ROW(true, true)}};
+#undef ROW
+    return table[mip][pow2][four];
+}
+
 int pnr_march_rays_train_mip(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma, uint32_t max_steps,
                              uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears, const float* fars, float* xyzs, float* dirs,
                              float* deltas, int32_t* rays, int32_t* counter, const float* noises, void* scratch, const void* mip,
@@ -647,30 +673,19 @@ int pnr_march_rays_train_mip(const float* rays_o, const float* rays_d, const uin
     // 726 -> 256 (lego, 0), 507 -> 235 (slab, 0); 40 000 rays 704 -> 441 and 760 -> 695 with a constant step, but 247 -> 300 and 232 -> 239 with a growing one
     // (its windows are walked point by point and there are enough waves already): cooperative for training-sized batches or a constant step
     const bool coop_count = p.coop != 0 && g_opt_train_coop != 0 && (uint64_t)N * max_steps < (1ull << 31) && (dt_gamma == 0.0f || N <= 16384u);
-#define PNR_LAUNCH_TRAIN(MIPV, P2V)                                                                                                           \
-    if (coop_count) {                                                                                                                          \
-        if (N <= 8192u)                                                                                                                        \
-            hipLaunchKernelGGL((k_march_train_count_coop<MIPV, P2V, 1>), dim3(cdiv(N, kBlock / PNR_WAVE)), dim3(kBlock), lds, s, rays_o,       \
-                               rays_d, grid, p, N, nears, fars, noises, sc + kScanHdr + nb, m, t_store);                                       \
-        else                                                                                                                                   \
-            hipLaunchKernelGGL((k_march_train_count_coop<MIPV, P2V, 4>), dim3(cdiv(N, (kBlock / PNR_WAVE) * 4)), dim3(kBlock), lds, s, rays_o, \
-                               rays_d, grid, p, N, nears, fars, noises, sc + kScanHdr + nb, m, t_store);                                       \
-        hipLaunchKernelGGL(k_chunk_sums, dim3(nb), dim3(kBlock), 0, s, sc, N);                                                                 \
-    } else                                                                                                                                     \
-        hipLaunchKernelGGL((k_march_train_count<MIPV, P2V>), dim3(nb), dim3(kBlock), lds, s, rays_o, rays_d, grid, p, N, nears, fars, noises, sc, m, \
-                           t_store);                                                                                                           \
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, sc, nb, counter, N, (int32_t*)nullptr);                                    \
-    if (t_store)                                                                                                                               \
-        hipLaunchKernelGGL(k_march_train_emit, dim3(nb, 16), dim3(kBlock), 0, s, rays_o, rays_d, p, N, M, nears, noises, t_store, xyzs, dirs, deltas, \
-                           rays, sc);                                                                                                          \
-    else                                                                                                                                       \
-        hipLaunchKernelGGL((k_march_train_write<MIPV, P2V>), dim3(nb), dim3(kBlock), lds, s, rays_o, rays_d, grid, p, N, M, nears, fars, noises, \
-                           xyzs, dirs, deltas, rays, sc, m)
-    if (use_mip && pow2) { PNR_LAUNCH_TRAIN(true, true); }
-    else if (use_mip) { PNR_LAUNCH_TRAIN(true, false); }
-    else if (pow2) { PNR_LAUNCH_TRAIN(false, true); }
-    else { PNR_LAUNCH_TRAIN(false, false); }
-#undef PNR_LAUNCH_TRAIN
+    if (coop_count) {
+        const uint32_t rays_per_wave = N <= 8192u ? 1u : 4u;
+        hipLaunchKernelGGL(march_train_count_coop_kernel(use_mip, pow2, rays_per_wave == 4u), dim3(cdiv(N, (kBlock / PNR_WAVE) * rays_per_wave)), dim3(kBlock), lds, s,
+                           rays_o, rays_d, grid, p, N, nears, fars, noises, sc + kScanHdr + nb, m, t_store);
+        hipLaunchKernelGGL(k_chunk_sums, dim3(nb), dim3(kBlock), 0, s, sc, N);
+    } else
+        hipLaunchKernelGGL(march_train_count_kernel(use_mip, pow2), dim3(nb), dim3(kBlock), lds, s, rays_o, rays_d, grid, p, N, nears, fars, noises, sc, m, t_store);
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, sc, nb, counter, N, (int32_t*)nullptr);
+    if (t_store)
+        hipLaunchKernelGGL(k_march_train_emit, dim3(nb, 16), dim3(kBlock), 0, s, rays_o, rays_d, p, N, M, nears, noises, t_store, xyzs, dirs, deltas, rays, sc);
+    else
+        hipLaunchKernelGGL(march_train_write_kernel(use_mip, pow2), dim3(nb), dim3(kBlock), lds, s, rays_o, rays_d, grid, p, N, M, nears, fars, noises, xyzs, dirs,
+                           deltas, rays, sc, m);
     return check_launch();
 }
 
@@ -717,14 +732,8 @@ int pnr_march_rays_fill(uint32_t n_alive, uint32_t n_step, const int32_t* rays_a
     const dim3 g(grid_dim), b(kBlock);
     hipStream_t s = as_stream(stream);
     const uint32_t* m = static_cast<const uint32_t*>(mip);
-    if (use_mip && pow2)
-        hipLaunchKernelGGL((k_march_rays<true, true>), g, b, lds, s, n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, p, grid, fars, xyzs, dirs, deltas, noises, m, fill_rows);
-    else if (use_mip)
-        hipLaunchKernelGGL((k_march_rays<true, false>), g, b, lds, s, n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, p, grid, fars, xyzs, dirs, deltas, noises, m, fill_rows);
-    else if (pow2)
-        hipLaunchKernelGGL((k_march_rays<false, true>), g, b, lds, s, n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, p, grid, fars, xyzs, dirs, deltas, noises, m, fill_rows);
-    else
-        hipLaunchKernelGGL((k_march_rays<false, false>), g, b, lds, s, n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, p, grid, fars, xyzs, dirs, deltas, noises, m, fill_rows);
+    hipLaunchKernelGGL(march_rays_kernel(use_mip, pow2), g, b, lds, s, n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, p, grid, fars, xyzs, dirs, deltas, noises, m,
+                       fill_rows);
     return check_launch();
 }
 

@@ -124,11 +124,14 @@ __global__ void __launch_bounds__(256) k_sh_cat_fwd(const float* __restrict__ in
     for (uint32_t i = quads * 4 + threadIdx.x; i < total; i += 256) dst[i] = tile[i];
 }
 
-template <int DEG>
-static int launch_sh_cat(const float* inputs, const float* tail, uint32_t t, float* outputs, uint32_t B, hipStream_t s, uint32_t tail_stride = 0, uint32_t tail_off = 0,
-                         float* sigma = nullptr) {
-    hipLaunchKernelGGL((k_sh_cat_fwd<DEG>), dim3(cdiv(B, 256)), dim3(256), 256 * (DEG * DEG + t) * sizeof(float), s, inputs, tail, t, outputs, B,
-                       tail_stride ? tail_stride : t, tail_off, sigma);
+// instantiations by degree; C == 8 has no room for a tail (64 + t > 64 floats of the LDS tile), so the callers' checks never let it reach this table
+typedef decltype(&k_sh_cat_fwd<1>) ShCatKernel;
+static int launch_sh_cat(uint32_t C, const float* inputs, const float* tail, uint32_t t, float* outputs, uint32_t B, hipStream_t s, uint32_t tail_stride = 0,
+                         uint32_t tail_off = 0, float* sigma = nullptr) {
+    static const ShCatKernel table[7] = {k_sh_cat_fwd<1>, k_sh_cat_fwd<2>, k_sh_cat_fwd<3>, k_sh_cat_fwd<4>, k_sh_cat_fwd<5>, k_sh_cat_fwd<6>, k_sh_cat_fwd<7>};
+    if (C < 1 || C > 7) return PNR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(table[C - 1], dim3(cdiv(B, 256)), dim3(256), 256 * (C * C + t) * sizeof(float), s, inputs, tail, t, outputs, B, tail_stride ? tail_stride : t,
+                       tail_off, sigma);
     return check_launch();
 }
 // grad_h[b] = [dsigma[b] * exp(clamp(h[b][0], -15, 15)), dout[b][C2 : C2 + hw - 1]]: trunc_exp's backward (activation.py:14-17) and the column slice, one pass
@@ -144,12 +147,12 @@ __global__ void __launch_bounds__(256) k_sigma_geo_cat_bwd(const float* __restri
     grad_h[i] = v;
 }
 
-template <int DEG>
-static int launch_sh(const float* inputs, float* outputs, uint32_t B, uint32_t D, float* dy_dx, hipStream_t s) {
-    const dim3 grid(cdiv(B, 256)), block(256);
-    if (dy_dx) hipLaunchKernelGGL((k_sh_fwd<DEG, true>), grid, block, 0, s, inputs, outputs, B, D, dy_dx);
-    else hipLaunchKernelGGL((k_sh_fwd<DEG, false>), grid, block, 0, s, inputs, outputs, B, D, dy_dx);
-    return check_launch();
+typedef decltype(&k_sh_fwd<1, false>) ShKernel;
+static ShKernel sh_kernel(uint32_t C, bool with_dy_dx) {   // [degree - 1][with dy_dx]
+#define ROW(DEG) {k_sh_fwd<DEG, false>, k_sh_fwd<DEG, true>}
+    static const ShKernel table[8][2] = {ROW(1), ROW(2), ROW(3), ROW(4), ROW(5), ROW(6), ROW(7), ROW(8)};
+#undef ROW
+    return C >= 1 && C <= 8 ? table[C - 1][with_dy_dx] : nullptr;
 }
 
 }  // namespace pnr
@@ -162,16 +165,7 @@ int pnr_sigma_geo_cat_forward(const float* h, uint32_t hw, const float* dirs, ui
     if (C < 1 || C > 8 || hw < 2 || C * C + hw - 1 > 64) return PNR_ERR_UNSUPPORTED;
     if (B == 0) return PNR_OK;
     if (!h || !dirs || !sigma || !out) return PNR_ERR_INVALID;
-    hipStream_t s = as_stream(stream);
-    switch (C) {
-        case 1: return launch_sh_cat<1>(dirs, h, hw - 1, out, B, s, hw, 1, sigma);
-        case 2: return launch_sh_cat<2>(dirs, h, hw - 1, out, B, s, hw, 1, sigma);
-        case 3: return launch_sh_cat<3>(dirs, h, hw - 1, out, B, s, hw, 1, sigma);
-        case 4: return launch_sh_cat<4>(dirs, h, hw - 1, out, B, s, hw, 1, sigma);
-        case 5: return launch_sh_cat<5>(dirs, h, hw - 1, out, B, s, hw, 1, sigma);
-        case 6: return launch_sh_cat<6>(dirs, h, hw - 1, out, B, s, hw, 1, sigma);
-        default: return launch_sh_cat<7>(dirs, h, hw - 1, out, B, s, hw, 1, sigma);   // C == 8 has no room for a tail
-    }
+    return launch_sh_cat(C, dirs, h, hw - 1, out, B, as_stream(stream), hw, 1, sigma);
 }
 
 int pnr_sigma_geo_cat_backward(const float* h, uint32_t hw, const float* dsigma, const float* dout, uint32_t C, uint32_t B, float* grad_h, pnr_stream_t stream) {
@@ -190,33 +184,15 @@ int pnr_sh_encode_forward(const float* inputs, float* outputs, uint32_t B, uint3
     if (C < 1 || C > 8) return PNR_ERR_UNSUPPORTED; // degree in [1, 8] (sphere_harmonics.py:70)
     if (B == 0) return PNR_OK;
     if (!inputs || !outputs) return PNR_ERR_INVALID;
-    hipStream_t s = as_stream(stream);
-    switch (C) {
-        case 1: return launch_sh<1>(inputs, outputs, B, D, dy_dx, s);
-        case 2: return launch_sh<2>(inputs, outputs, B, D, dy_dx, s);
-        case 3: return launch_sh<3>(inputs, outputs, B, D, dy_dx, s);
-        case 4: return launch_sh<4>(inputs, outputs, B, D, dy_dx, s);
-        case 5: return launch_sh<5>(inputs, outputs, B, D, dy_dx, s);
-        case 6: return launch_sh<6>(inputs, outputs, B, D, dy_dx, s);
-        case 7: return launch_sh<7>(inputs, outputs, B, D, dy_dx, s);
-        default: return launch_sh<8>(inputs, outputs, B, D, dy_dx, s);
-    }
+    hipLaunchKernelGGL(sh_kernel(C, dy_dx != nullptr), dim3(cdiv(B, 256)), dim3(256), 0, as_stream(stream), inputs, outputs, B, D, dy_dx);
+    return check_launch();
 }
 
 int pnr_sh_encode_cat_forward(const float* inputs, const float* tail, uint32_t tail_cols, float* outputs, uint32_t B, uint32_t C, pnr_stream_t stream) {
     if (C < 1 || C > 8 || tail_cols == 0 || C * C + tail_cols > 64) return PNR_ERR_UNSUPPORTED;   // one LDS tile of 256 x 64 floats at most
     if (B == 0) return PNR_OK;
     if (!inputs || !tail || !outputs) return PNR_ERR_INVALID;
-    hipStream_t s = as_stream(stream);
-    switch (C) {
-        case 1: return launch_sh_cat<1>(inputs, tail, tail_cols, outputs, B, s);
-        case 2: return launch_sh_cat<2>(inputs, tail, tail_cols, outputs, B, s);
-        case 3: return launch_sh_cat<3>(inputs, tail, tail_cols, outputs, B, s);
-        case 4: return launch_sh_cat<4>(inputs, tail, tail_cols, outputs, B, s);
-        case 5: return launch_sh_cat<5>(inputs, tail, tail_cols, outputs, B, s);
-        case 6: return launch_sh_cat<6>(inputs, tail, tail_cols, outputs, B, s);
-        default: return launch_sh_cat<7>(inputs, tail, tail_cols, outputs, B, s);   // C == 8 has no room for a tail (64 + t > 64)
-    }
+    return launch_sh_cat(C, inputs, tail, tail_cols, outputs, B, as_stream(stream));
 }
 
 int pnr_sh_encode_backward(const float* grad, const float* inputs, uint32_t B, uint32_t D, uint32_t C, const float* dy_dx, float* grad_inputs,

@@ -244,8 +244,7 @@ __global__ void __launch_bounds__(64) k_stylizer_fit(const pnr_stylizer_fit_args
 
 template <int NB>
 int stylizer_launch(const pnr_stylizer_fit_args& a, uint32_t bytes, hipStream_t stream) {
-    static bool attr_set[kMaxDevices] = {};
-    if (!ensure_dynamic_lds(k_stylizer_fit<NB>, kStyLdsLimit, attr_set)) return PNR_ERR_LAUNCH;
+    if (!raise_lds<k_stylizer_fit<NB>>(kStyLdsLimit)) return PNR_ERR_LAUNCH;
     hipLaunchKernelGGL(k_stylizer_fit<NB>, dim3(1), dim3(64), bytes, stream, a);
     return check_launch();
 }

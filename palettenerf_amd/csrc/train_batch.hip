@@ -138,10 +138,12 @@ __global__ void __launch_bounds__(kBatchBlock) k_error_map_update(float* __restr
     *m = 0.1f * *m + 0.9f * loss_ray[r];                                                            // palette/utils.py:595-596
 }
 
-template <int FMT>
-void launch_batch(const pnr_train_batch_args& a, uint32_t blocks, int vec, hipStream_t s) {
-    if (a.C == 4) hipLaunchKernelGGL((k_train_batch<FMT, 4>), dim3(blocks), dim3(kBatchBlock), 0, s, a, vec);
-    else hipLaunchKernelGGL((k_train_batch<FMT, 3>), dim3(blocks), dim3(kBatchBlock), 0, s, a, vec);
+typedef decltype(&k_train_batch<PNR_IMAGE_FP32, 3>) TrainBatchKernel;
+TrainBatchKernel train_batch_kernel(int image_format, uint32_t C) {   // [image format][C == 4]; both validated (or defaulted) by the caller
+#define ROW(FMT) {k_train_batch<FMT, 3>, k_train_batch<FMT, 4>}
+    static const TrainBatchKernel table[3][2] = {ROW(PNR_IMAGE_FP32), ROW(PNR_IMAGE_FP16), ROW(PNR_IMAGE_UINT8)};
+#undef ROW
+    return table[image_format == PNR_IMAGE_FP32 ? 0 : image_format == PNR_IMAGE_FP16 ? 1 : 2][C == 4];
 }
 
 }  // namespace
@@ -190,9 +192,7 @@ int pnr_train_batch(const pnr_train_batch_args* args, pnr_stream_t stream) {
     if (!a.rays_o && !a.gt_clip && !a.pixels && !colour) return PNR_OK;
     const uintptr_t base = reinterpret_cast<uintptr_t>(a.images);
     const int vec = a.image_format == PNR_IMAGE_FP32 ? (base & 15u) == 0 : (a.image_format == PNR_IMAGE_FP16 ? (base & 7u) == 0 : (base & 3u) == 0);
-    if (a.image_format == PNR_IMAGE_FP32) launch_batch<PNR_IMAGE_FP32>(a, (uint32_t)blocks, vec, as_stream(stream));
-    else if (a.image_format == PNR_IMAGE_FP16) launch_batch<PNR_IMAGE_FP16>(a, (uint32_t)blocks, vec, as_stream(stream));
-    else launch_batch<PNR_IMAGE_UINT8>(a, (uint32_t)blocks, vec, as_stream(stream));
+    hipLaunchKernelGGL(train_batch_kernel(a.image_format, a.C), dim3((uint32_t)blocks), dim3(kBatchBlock), 0, as_stream(stream), a, vec);
     return check_launch();
 }
 

@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Is the gfx950 device code of every csrc/*.hip the same at two revisions?  Each unit is compiled device-only to assembly text with the
-product's flags (build.FLAGS, the unit's UNIT_FLAGS) and the two texts are compared byte for byte.  A unit whose text differs gets a per-kernel
-summary of what decides occupancy -- vector registers, scratch, LDS -- and of the instruction count, old against new.  No GPU is needed.
-usage: isa_identity.py [OLD [NEW]]   (git revisions; default HEAD~1 against the working tree).  Exit status 1 if any unit differs."""
+product's flags (build.FLAGS, the unit's UNIT_FLAGS) and the two texts are compared byte for byte.  Host code that names a template's
+instantiations in another order makes the compiler emit the same kernels in another order, with other function numbers in their local labels:
+a unit whose text differs is therefore compared kernel by kernel (same_code), and "same kernels, same code (order differs)" is reported apart
+from a real difference.  A unit that really differs gets a per-kernel summary of what decides occupancy -- vector registers, scratch, LDS --
+and of the instruction count, old against new.  No GPU is needed.
+usage: isa_identity.py [OLD [NEW]]   (git revisions; default HEAD~1 against the working tree).  Exit status 0 only if every unit is
+byte-identical or same-code."""
 import concurrent.futures
 import io
 import os
@@ -45,6 +49,35 @@ def first_difference(a, b):
     la, lb = a.split(b"\n"), b.split(b"\n")
     n = next((i for i, (x, y) in enumerate(zip(la, lb)) if x != y), min(len(la), len(lb)))
     return f"line {n + 1}: {(la[n] if n < len(la) else b'<end of file>').decode(errors='replace').strip()!r} -> {(lb[n] if n < len(lb) else b'<end of file>').decode(errors='replace').strip()!r}"
+
+
+# a local label carries the number of its function within the unit (.LBB3_2: block 2 of function 3), which moves when the emission order does
+LOCAL_LABEL = re.compile(rb"\.(LBB|Lfunc_begin|Lfunc_end|LJTI|Ltmp)\d+")
+
+
+def kernel_code(text):
+    """{kernel symbol: its code} of one unit's assembly text.  A kernel's code is the text from its label to the .end_amdhsa_kernel of its
+    descriptor (instructions, jump tables, every .amdhsa_ field) without `;` comments and blank lines, the function number of local labels
+    replaced by a placeholder."""
+    lines = text.split(b"\n")
+    label = {m.group(1): i for i, ln in enumerate(lines) if (m := re.match(rb"(\w+):", ln))}
+    out = {}
+    for i, ln in enumerate(lines):
+        m = re.match(rb"\s*\.amdhsa_kernel (\w+)", ln)
+        if not m or m.group(1) not in label:
+            continue
+        end = next(j for j in range(i, len(lines)) if lines[j].strip() == b".end_amdhsa_kernel")
+        body = (LOCAL_LABEL.sub(rb".\1#", ln.split(b";")[0]).rstrip() for ln in lines[label[m.group(1)]:end + 1])
+        out[m.group(1).decode()] = b"\n".join(ln for ln in body if ln.strip())
+    return out
+
+
+def same_code(old_text, new_text):
+    """(True, []) if both texts hold the same kernels with the same code, else (False, [what differs, one line per kernel])."""
+    old, new = kernel_code(old_text), kernel_code(new_text)
+    why = [f"only in old: {k}" for k in sorted(set(old) - set(new))] + [f"only in new: {k}" for k in sorted(set(new) - set(old))]
+    why += [f"{k}: " + first_difference(old[k], new[k]) for k in sorted(set(old) & set(new)) if old[k] != new[k]]
+    return not why, why
 
 
 FIELDS = ("next_free_vgpr", "private_segment_fixed_size", "group_segment_fixed_size")
@@ -108,9 +141,13 @@ def main():
         elif text["old", u] == text["new", u]:
             verdict = "identical"
         else:
-            verdict, differ = "differs: " + first_difference(text["old", u], text["new", u]), differ + 1
+            same, why = same_code(text["old", u], text["new", u])
+            n = len(kernel_code(text["new", u]))
+            verdict = f"same kernels, same code (order differs; {n} kernels)" if same else "differs: " + first_difference(text["old", u], text["new", u])
         print(f"{u:16s} {verdict}")
         if verdict.startswith("differs"):
+            differ += 1
+            print("".join(f"    {w}\n" for w in why), end="")
             summary(text["old", u], text["new", u])
     return 1 if differ else 0
 

@@ -12,8 +12,14 @@ batch has: exact zeros behind each ray's stopping sample and scattered among the
 The non-staged scatter (k_bin_scatter<0/1/2>) is what the host takes by itself when the staged kernel's LDS would exceed 160 KiB: more than ~5460
 buckets, a table of ~45 M rows -- too large for a quick test.  The same kernels run here through the option scatter_staged = 0.
 
+The staged scatter's dynamic LDS grows with the table (its per-bucket counters: 12 bytes per possible bucket), and a kernel's dynamic-LDS limit is
+raised once per process and device: test_binned_small_table_then_a_larger_one_in_a_fresh_process runs a small table first and a larger one after it.
+
 Every GPU test prints its worst error / bound ratio per case and option set (pytest -s shows them).  The last test needs no device: it checks that the
 constructions above are what they claim to be, that the fp32 oracle stays inside the bound on them and that a gradient lacking one sample does not."""
+import os
+import subprocess
+import sys
 from contextlib import contextmanager
 
 import numpy as np
@@ -101,7 +107,11 @@ def test_binned_table_gradient_against_float64(cuda, name, monkeypatch):
 
 def _abi(cuda, name, x, g, out, short=0, rows_used=None):
     """pnr_grid_encode_backward_binned straight through the C ABI, adding into `out` (a device tensor); -> the return code"""
-    L, H, pls, offsets, gridtype, ac = gr.binned_case(name)
+    return _abi_case(cuda, gr.binned_case(name), x, g, out, short, rows_used)
+
+
+def _abi_case(cuda, case, x, g, out, short=0, rows_used=None):
+    L, H, pls, offsets, gridtype, ac = case
     lib = _lib.load()
     B = x.shape[0] if rows_used is None else rows_used
     rows = int(offsets[-1])
@@ -158,6 +168,46 @@ def test_binned_adds_into_the_gradient_buffer(cuda, name):
         r = _check(fails, f"{name} accumulate {_label(off)}", host(out), gt, bound, n, before)
         print(f"binned table gradient {name} added to a filled buffer [{_label(off)}]: worst error / bound = {r:.3f}")
     assert not fails, "\n".join(fails)
+
+
+# (levels, rows per level), in the order of the calls: total rows / 8192 + L = 3 possible buckets, then 36 -- the staged scatter's LDS is 96 KiB + 12 bytes
+# per possible bucket + 16, above the 64 KiB default either way, and larger for the second table.  H = 16, per_level_scale = 2: level 0 is an LDS image,
+# the levels behind it go through the staged scatter (17^3 cells are hashed into 4096 rows and lie inside 65536; from 65^3 on both tables are hashed).
+LDS_ORDER_TABLES = ((2, 4096), (4, 1 << 16))
+LDS_ORDER_POINTS = 4096
+
+
+def _small_table_then_a_larger_one():
+    """(the child process) both table gradients through the ABI, each against the float64 reference and its bound; -> the exit status"""
+    if not torch.cuda.is_available():
+        print("no GPU is visible")
+        return 2
+    cuda = torch.device("cuda:0")
+    fails = []
+    for L, rows in LDS_ORDER_TABLES:
+        offsets = (np.arange(L + 1) * rows).astype(np.int32)
+        rng = np.random.default_rng(rows)
+        x, g = rng.random((LDS_ORDER_POINTS, 3)).astype(np.float32), rng.standard_normal((LDS_ORDER_POINTS, L * 2)).astype(np.float32)
+        gt, mag, n = gr.GridReference(x, offsets, 2.0, 16).table_grad(g)
+        out = torch.zeros(L * rows, 2, device=cuda)
+        tag = f"L = {L}, {rows} rows per level"
+        rc = _abi_case(cuda, (L, 16, 2.0, offsets, 0, False), x, g, out)
+        if rc != 0:
+            fails.append(f"{tag}: pnr_grid_encode_backward_binned returned {rc}")
+        r = _check(fails, tag, host(out), gt, gr.table_grad_bound(3, mag, n), n)
+        print(f"binned table gradient, {tag}: return code {rc}, worst error / bound = {r:.3f}")
+    print("\n".join(fails))
+    return 1 if fails else 0
+
+
+@pytest.mark.gpu
+def test_binned_small_table_then_a_larger_one_in_a_fresh_process(cuda):
+    """the dynamic-LDS limit of the staged scatter does not depend on which table a process brings first (a fresh process: the flags are process-wide)"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-m", "tests.test_gpu_grid_binned"], cwd=root, capture_output=True, text=True, timeout=120)
+    print(out.stdout)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert out.stdout.count("worst error / bound") == len(LDS_ORDER_TABLES)
 
 
 # ------------------------------------------------------------------------------------------ no device
@@ -269,3 +319,7 @@ def test_binned_constructions_are_what_they_claim():
             assert (np.signbit(g3) & (g3 == 0)).sum() >= 40
             assert not ref.inr[[100, 200, 500, 600]].any() and ref.inr[[400, 401]].all()
     print("fp32 oracle, worst error / bound: " + ", ".join(f"{k} {v:.3f}" for k, v in worst_oracle.items()))
+
+
+if __name__ == "__main__":
+    sys.exit(_small_table_then_a_larger_one())

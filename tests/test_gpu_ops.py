@@ -1500,7 +1500,7 @@ def test_fused_density_matches_the_torch_sigma_net(cuda, kind, precision):
     assert torch.equal(got["sigma"], d(x)[0]) or precision == 0
 
 
-# One stack per instantiation the MLP dispatcher (csrc/mlp.hip: PNR_MLP_SWITCH) can be asked for through run_mlp: layers {2, 3} x input tiles of 32
+# One stack per instantiation the MLP's kernel tables (csrc/mlp.hip: g_mlp_fwd ... g_mlp_bwd_h) can be asked for through run_mlp: layers {2, 3} x input tiles of 32
 # {1, 2} x output tiles {1, 2} x hidden activation {relu, elu}, every width odd or short of its tile somewhere.  Three layers with two tiles at both
 # ends do not fit the backward's LDS (mlp.fusable refuses them; test_fused_mlp_widest_stack_forward_through_the_c_abi has their forward).
 MLP_STACKS = [((20, 48, 9), "relu"), ((20, 48, 9), "elu"), ((9, 33, 50), "relu"), ((9, 33, 50), "elu"), ((40, 64, 17), "relu"), ((40, 64, 17), "elu"),
