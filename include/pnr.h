@@ -1216,6 +1216,76 @@ typedef struct pnr_stylizer_fit_args {
 } pnr_stylizer_fit_args;
 int pnr_stylizer_fit(const pnr_stylizer_fit_args* args, pnr_stream_t stream);
 
+/* ---- coloured mesh export: analytic normals and the vertex block on the device (additive, ABI 10; csrc/normals.hip) ----
+ * MI355X-first addition, no counterpart in the reference (its save_mesh writes bare geometry).
+ *
+ * pnr_density_gradient: for n world-space points of the shipped density field (the field of pnr_lattice_density: 16 levels x 2 features, fp32
+ * table, D = 3, hash or tiled, align_corners false; sigma_net 32 -> 64 (ReLU) -> 16, bias-free)
+ *   logit [n]     sigma_net(encoder((p + bound) / (2 bound)))[0]: density()['sigma'] = exp(logit)
+ *   grad [n,3]    d logit / d p in world coordinates (the 1 / (2 bound) of the encoder's input folded in).  The gradient of the LOGIT: grad sigma =
+ *                 sigma grad logit has the same direction, and nothing overflows.
+ *   normal [n,3]  -grad / |grad|: out of the dense region, the side pnr_mesh_emit's triangles are counter-clockwise from.
+ * Each output is optional by a NULL pointer; at least one must be given.  sigma0 [64,32] and sigma1 [16,64] are the RAW row-major weight
+ * matrices (only row 0 of sigma1 is read): an optimiser step or an EMA swap needs no pack launch and invalidates nothing.
+ *   Cell path     the cell of a point on each level is grid_core.hpp's: unit_cube_of, grid_cell<3>, corner_rows<3, 1>, and the level's value is
+ *                 cell_interp's chain -- the gradient belongs to the trilinear piece the forward value comes from everywhere else in the library.
+ *                 Along axis d on level l:  scale_l * sum over the four corner pairs (x-lowest first) of w(other two axes) * (right - left),
+ *                 w = the product of the other two axes' factors, lower axis first; an fmaf chain from 0.
+ *   sigma_net     hidden pre-activations z_k are plain fp32 fmaf chains over the 32 inputs in order (not the split-fp16 path, not the matrix
+ *                 cores); the ReLU derivative is z_k > 0 (strict), as torch's.  logit = the chain over k of w1[0][k] * max(z_k, 0).
+ *                 `logit` is therefore NOT promised bit-equal to the matrix-core density path (nerf_density_tile<0>: pnr_lattice_density,
+ *                 pnr_nerf_density_forward): the same products, another order of the sums.
+ *   Outside       a point outside the box reads zero from the encoder: logit = 0, grad = 0, normal = 0.  |grad| zero or not finite: normal = 0.
+ *   Order         one lane per point, every sum in a fixed order, no atomics, no scratch, no workspace: a row's result does not depend on n, on
+ *                 its position in the batch or on how the caller chunks the call -- reproducible bit for bit.  The [n, 16 * 3 * 2] Jacobian
+ *                 never goes to memory.  ONE launch of ceil(n / 256) workgroups, whatever n is (no capped grid, no tile loop).
+ * PNR_ERR_UNSUPPORTED: another architecture (num_levels != 16, gridtype > 1, bound <= 0).  PNR_ERR_INVALID: a NULL struct or required pointer
+ * (with n > 0: points), all three outputs NULL.  n = 0 is PNR_OK.  All before any launch. */
+typedef struct pnr_density_gradient_args {
+    const float* points;               /* [n,3] world space */
+    uint32_t n;
+    float bound;
+    const float* embeddings;           /* fp32 hash table [rows, 2] */
+    const int32_t* offsets;
+    uint32_t num_levels;
+    float S;
+    uint32_t base_resolution, gridtype;
+    const float* sigma0;               /* [64,32] row-major, raw */
+    const float* sigma1;               /* [16,64] row-major, raw; row 0 is read */
+    float* logit;                      /* [n]   optional */
+    float* grad;                       /* [n,3] optional */
+    float* normal;                     /* [n,3] optional */
+} pnr_density_gradient_args;
+int pnr_density_gradient(const pnr_density_gradient_args* args, pnr_stream_t stream);
+
+/* pnr_mesh_vertex_records: the vertex block of a binary little-endian PLY on the device -- the host reads back final bytes.
+ *   vertices [nv,3]   pnr_mesh_emit's lattice-index vertices
+ *   world [nv,3]      fp32( (double)v / (n - 1) * (double)(box_max - box_min) + (double)box_min ), box_max - box_min subtracted in fp32 first:
+ *                     extract_geometry's float64 vertices rounded once to fp32, the rounding write_ply applies -- a coloured file's x y z equal
+ *                     the plain file's bit for bit.  Optional.
+ *   records [nv, record_bytes]   x y z (f4) | nx ny nz (f4, with `normal`) | red green blue alpha (u1, alpha 255, with `rgb`) | extra[0 .. extra_channels) (f4)
+ *                     record_bytes = 12 + (normal ? 12 : 0) + (rgb ? 4 : 0) + 4 extra_channels.  Optional.
+ *   colour bytes      (uint8)(int)(s(clamp(c, 0, 1)) * 255.0f), s = the linear -> sRGB curve of pnr_image_to_uint8 when linear_to_srgb, else the identity.
+ * normal [nv,3], rgb [nv,3] contiguous; extra rows of extra_stride floats (>= extra_channels).  One lane per 32-bit word of the output.
+ * nv = 0 is PNR_OK.  PNR_ERR_INVALID: a NULL struct or vertex pointer, an n[d] < 2, neither output, extra_channels without `extra` or a stride below the
+ * channel count, records not 4-byte aligned; PNR_ERR_UNSUPPORTED: 2^32 or more output words.  All before any launch.
+ * pnr_mesh_vertex_record_bytes: host only, the record_bytes above. */
+typedef struct pnr_vertex_records_args {
+    const float* vertices;             /* [nv,3] */
+    uint32_t nv;
+    float box_min[3], box_max[3];
+    uint32_t n[3];
+    const float* normal;               /* [nv,3] optional */
+    const float* rgb;                  /* [nv,3] optional */
+    int linear_to_srgb;
+    const float* extra;                /* [nv, extra_channels] optional */
+    uint32_t extra_channels, extra_stride;
+    float* world;                      /* [nv,3] out, optional */
+    uint8_t* records;                  /* [nv, record_bytes] out, optional; 4-byte aligned */
+} pnr_vertex_records_args;
+uint32_t pnr_mesh_vertex_record_bytes(int has_normal, int has_rgb, uint32_t extra_channels);
+int pnr_mesh_vertex_records(const pnr_vertex_records_args* args, pnr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,11 +136,14 @@ SIGNATURES = {
     "pnr_train_batch": [_ptr, _ptr],
     "pnr_error_map_update": [_ptr, _u32, _ptr, _ptr, _ptr, _u32, _u32, _ptr],
     "pnr_stylizer_fit": [_ptr, _ptr],
+    "pnr_density_gradient": [_ptr, _ptr],
+    "pnr_mesh_vertex_record_bytes": [_int, _int, _u32],
+    "pnr_mesh_vertex_records": [_ptr, _ptr],
 }
 _RESTYPES = {"pnr_frame_metrics_workspace_bytes": _u64, "pnr_mesh_workspace_bytes": _u64, "pnr_lattice_density_workspace_bytes": _u64, "pnr_occupancy_workspace_bytes": _u64, "pnr_occupancy_samples": _u32, "pnr_adam_max_tensors": _u32, "pnr_error_string": ctypes.c_char_p, "pnr_scan_scratch_bytes": _u64, "pnr_nerf_field_packed_bytes": _u64, "pnr_occupancy_mip_bytes": _u64, "pnr_nerf_frame_workspace_bytes": _u64, "pnr_palette_field_packed_bytes": _u64, "pnr_palette_frame_workspace_bytes": _u64,
              "pnr_palette_aux_channels": _u32, "pnr_linear_wgrad_workspace_bytes": _u64, "pnr_grid_backward_binned_workspace_bytes": _u64,
              "pnr_palette_train_shade_workspace_bytes": _u64, "pnr_train_loss_workspace_bytes": _u64, "pnr_mlp_packed_bytes": _u64, "pnr_mlp_backward_workspace_bytes": _u64,
-             "pnr_background_packed_bytes": _u64, "pnr_background_backward_workspace_bytes": _u64}
+             "pnr_background_packed_bytes": _u64, "pnr_background_backward_workspace_bytes": _u64, "pnr_mesh_vertex_record_bytes": _u32}
 
 class AdamTensor(ctypes.Structure):
     """Mirror of `pnr_adam_tensor` (include/pnr.h)."""
@@ -191,6 +194,18 @@ class LatticeDensityArgs(ctypes.Structure):
     _fields_ = [("box_min", _f32 * 3), ("box_max", _f32 * 3), ("n", _u32 * 3), ("bound", _f32), ("embeddings", _ptr), ("offsets", _ptr),
                 ("num_levels", _u32), ("S", _f32), ("base_resolution", _u32), ("gridtype", _u32), ("packed_sigma_net", _ptr), ("workspace", _ptr),
                 ("workspace_bytes", _u64), ("u", _ptr)]
+
+
+class DensityGradientArgs(ctypes.Structure):
+    """Mirror of `pnr_density_gradient_args` (include/pnr.h)."""
+    _fields_ = [("points", _ptr), ("n", _u32), ("bound", _f32), ("embeddings", _ptr), ("offsets", _ptr), ("num_levels", _u32), ("S", _f32),
+                ("base_resolution", _u32), ("gridtype", _u32), ("sigma0", _ptr), ("sigma1", _ptr), ("logit", _ptr), ("grad", _ptr), ("normal", _ptr)]
+
+
+class VertexRecordsArgs(ctypes.Structure):
+    """Mirror of `pnr_vertex_records_args` (include/pnr.h)."""
+    _fields_ = [("vertices", _ptr), ("nv", _u32), ("box_min", _f32 * 3), ("box_max", _f32 * 3), ("n", _u32 * 3), ("normal", _ptr), ("rgb", _ptr),
+                ("linear_to_srgb", _int), ("extra", _ptr), ("extra_channels", _u32), ("extra_stride", _u32), ("world", _ptr), ("records", _ptr)]
 
 
 class NerfFrameArgs(ctypes.Structure):
