@@ -1286,6 +1286,87 @@ typedef struct pnr_vertex_records_args {
 uint32_t pnr_mesh_vertex_record_bytes(int has_normal, int has_rgb, uint32_t extra_channels);
 int pnr_mesh_vertex_records(const pnr_vertex_records_args* args, pnr_stream_t stream);
 
+/* ---- palette extraction, front end: histograms and k-means on the device (additive, ABI 10; csrc/extract.hip) ----
+ * PaletteTrainer.extract_palette (palette/utils.py:1135-1200) into palette_extraction as far as run_kmeans' return (:167-226).  The hull
+ * simplification and the weight LUT stay with the reference's CPU package; `centers` / `center_weights` below are exactly their input.
+ *
+ * pnr_extract_accumulate: ONE launch folds one rendered view of H x W pixels into both colour histograms.  Per pixel i (row-major):
+ *   valid = weights_sum[i] > thresh            strict; a NaN is not valid (:1185)
+ *   p     = the first three channels of the ground-truth pixel (alpha is not read), srgb_to_linear'ed first when `linear` (:1169-1170;
+ *           pnr_train_batch's curve and pixel conversion: fp32 as stored, fp16 exactly, uint8 as u / 255)
+ *   c     = p + 0.05f;  c = c / sqrtf((c0 c0 + c1 c1) + c2 c2)                                   (:1172-1173)
+ *   bin   = the reference's RGB_to_bin_index at 3 and at 5 bits per channel from the same c (palette/src/bindings.cpp:40-50):
+ *           per channel uint32(fmaxf(0, fminf(0.999f, c)) * 2^bpc), r most significant
+ * counts_coarse [512], counts_fine [32 768] and total [1] are 64-bit integer counts and are ACCUMULATED into: the caller zeroes them once.
+ * The extraction's sample weights are all 1 (:190), so the counts are exact, independent of arrival order and of the launch shape:
+ * bit-reproducible (integer atomics only).  Launch shape: min(256, ceil(H W / 1024)) workgroups of 1024 lanes striding over the view, both
+ * tables private in LDS, one 64-bit atomic per non-zero bin and workgroup at the end (pnr_launch_geometry("pnr_extract_accumulate", H W)).
+ * pixels: the view's first pixel; row_stride_bytes between rows (0 = W * channels * element size).
+ * Order of the checks, all before any launch: NULL args -> PNR_ERR_INVALID; an unknown image_format or channels other than 3 or 4 ->
+ * PNR_ERR_UNSUPPORTED; H W == 0 -> PNR_OK, nothing touched; a NULL pointer, a row stride below the row or not a multiple of the element size,
+ * a base not aligned to the element -> PNR_ERR_INVALID. */
+#define PNR_EXTRACT_COARSE_BINS 512
+#define PNR_EXTRACT_FINE_BINS 32768
+typedef struct pnr_extract_accumulate_args {
+    uint32_t H, W;
+    const float* weights_sum;           /* [H W]: the frame call's output, read where it lies */
+    const void* pixels;                 /* [H, W, channels] with a row stride */
+    int image_format;                   /* PNR_IMAGE_* */
+    uint32_t channels;                  /* 3 or 4 */
+    uint64_t row_stride_bytes;
+    int linear;
+    float thresh;                       /* the reference's 0.5 */
+    uint64_t* counts_coarse;            /* [512]    in/out */
+    uint64_t* counts_fine;              /* [32768]  in/out */
+    uint64_t* total;                    /* [1]      in/out: valid samples */
+} pnr_extract_accumulate_args;
+int pnr_extract_accumulate(const pnr_extract_accumulate_args* args, pnr_stream_t stream);
+
+/* pnr_extract_kmeans: the rest of palette_extraction up to run_kmeans' return, ONE launch of one workgroup.
+ *   points    the P non-empty fine bins in ascending code order, (code_channel + 0.5) / 32; weight count / total       (:217-222)
+ *   init      the centres (code_channel + 0.5) / 8 of the K coarse bins with count / total > tau, ascending             (:209-215)
+ *   Lloyd     scikit-learn's _kmeans_single_lloyd for KMeans(n_clusters=K, init=array): labels = argmin over the CURRENT centres of
+ *             ((x0-c0)^2 + (x1-c1)^2) + (x2-c2)^2, a tie to the lowest index; new centres = weighted sums times 1 / weight; stop when the
+ *             labels equal the previous iteration's (PNR_EXTRACT_STOP_LABELS), else when the summed squared centre shift is
+ *             <= tol * mean(var(points, axis=0)) (unweighted; PNR_EXTRACT_STOP_SHIFT), else after max_iter iterations (PNR_EXTRACT_STOP_CAP);
+ *             unless the labels stopped it, one more labelling with the final centres.  center_weights[k] = the weight labelled k.
+ *   out       centers [K,3] and center_weights [K] by descending weight, ties to the lower cluster index (:159-165); both buffers hold
+ *             PNR_EXTRACT_MAX_K rows.  labels [P] (optional, a debug output): the final label of every point, BEFORE the sort.
+ *   info [8]  K, P, iterations run, the stop rule, the status, 0, 0, 0.
+ * float64 throughout, no atomics, every sum in a fixed order (csrc/extract.hip): two runs give the same bits.  scikit-learn's float32
+ * rounding (it works in the dtype of bin_centers_fine) and its centring of the points are not imitated.
+ * K and P are known on the device only, so what depends on them is answered in info[4], not in the return value:
+ *   PNR_EXTRACT_NO_CENTER (K = 0), PNR_EXTRACT_TOO_MANY (K > PNR_EXTRACT_MAX_K), PNR_EXTRACT_FEW_POINTS (P < K): nothing else is written.
+ *   PNR_EXTRACT_EMPTIED: a cluster lost all its points in iteration info[2] (0-based).  scikit-learn's relocation is NOT done here: centers
+ *   holds the centres that iteration started from, in cluster order, center_weights zeros, and the caller finishes on the host.
+ * PNR_ERR_INVALID before any launch: a NULL struct or pointer (labels excepted), a workspace below pnr_extract_kmeans_workspace_bytes() or
+ * not 8-byte aligned, max_iter == 0, tau or tol negative or NaN. */
+#define PNR_EXTRACT_MAX_K 128
+#define PNR_EXTRACT_STOP_CAP 0
+#define PNR_EXTRACT_STOP_LABELS 1
+#define PNR_EXTRACT_STOP_SHIFT 2
+#define PNR_EXTRACT_OK 0
+#define PNR_EXTRACT_EMPTIED 1
+#define PNR_EXTRACT_NO_CENTER 2
+#define PNR_EXTRACT_TOO_MANY 3
+#define PNR_EXTRACT_FEW_POINTS 4
+typedef struct pnr_extract_kmeans_args {
+    const uint64_t* counts_coarse;      /* [512] */
+    const uint64_t* counts_fine;        /* [32768] */
+    const uint64_t* total;              /* [1] */
+    double tau;                         /* the reference's 8e-3 */
+    double tol;                         /* scikit-learn's 1e-4 */
+    uint32_t max_iter;                  /* scikit-learn's 300 */
+    void* workspace;
+    uint64_t workspace_bytes;
+    double* centers;                    /* [PNR_EXTRACT_MAX_K,3] out */
+    double* center_weights;             /* [PNR_EXTRACT_MAX_K]   out */
+    int32_t* info;                      /* [8] out */
+    int32_t* labels;                    /* [32768] out, optional */
+} pnr_extract_kmeans_args;
+uint64_t pnr_extract_kmeans_workspace_bytes(void);
+int pnr_extract_kmeans(const pnr_extract_kmeans_args* args, pnr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

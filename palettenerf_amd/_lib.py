@@ -139,11 +139,14 @@ SIGNATURES = {
     "pnr_density_gradient": [_ptr, _ptr],
     "pnr_mesh_vertex_record_bytes": [_int, _int, _u32],
     "pnr_mesh_vertex_records": [_ptr, _ptr],
+    "pnr_extract_accumulate": [_ptr, _ptr],
+    "pnr_extract_kmeans_workspace_bytes": [],
+    "pnr_extract_kmeans": [_ptr, _ptr],
 }
 _RESTYPES = {"pnr_frame_metrics_workspace_bytes": _u64, "pnr_mesh_workspace_bytes": _u64, "pnr_lattice_density_workspace_bytes": _u64, "pnr_occupancy_workspace_bytes": _u64, "pnr_occupancy_samples": _u32, "pnr_adam_max_tensors": _u32, "pnr_error_string": ctypes.c_char_p, "pnr_scan_scratch_bytes": _u64, "pnr_nerf_field_packed_bytes": _u64, "pnr_occupancy_mip_bytes": _u64, "pnr_nerf_frame_workspace_bytes": _u64, "pnr_palette_field_packed_bytes": _u64, "pnr_palette_frame_workspace_bytes": _u64,
              "pnr_palette_aux_channels": _u32, "pnr_linear_wgrad_workspace_bytes": _u64, "pnr_grid_backward_binned_workspace_bytes": _u64,
              "pnr_palette_train_shade_workspace_bytes": _u64, "pnr_train_loss_workspace_bytes": _u64, "pnr_mlp_packed_bytes": _u64, "pnr_mlp_backward_workspace_bytes": _u64,
-             "pnr_background_packed_bytes": _u64, "pnr_background_backward_workspace_bytes": _u64, "pnr_mesh_vertex_record_bytes": _u32}
+             "pnr_background_packed_bytes": _u64, "pnr_background_backward_workspace_bytes": _u64, "pnr_mesh_vertex_record_bytes": _u32, "pnr_extract_kmeans_workspace_bytes": _u64}
 
 class AdamTensor(ctypes.Structure):
     """Mirror of `pnr_adam_tensor` (include/pnr.h)."""
@@ -335,6 +338,23 @@ class StylizerFitArgs(ctypes.Structure):
                 + [(n, _ptr) for n in ("radiance", "omega", "offsets", "palette", "target", "view_dep", "dI", "dP", "ddelta", "mom_dI", "mom_dP",
                                        "mom_ddelta")]
                 + [("has_momentum", _int), ("lr", _ptr), ("momentum", _f32), ("lambda_arap", _f32), ("trace", _ptr)])
+
+
+EXTRACT_COARSE_BINS, EXTRACT_FINE_BINS, EXTRACT_MAX_K = 512, 32768, 128   # PNR_EXTRACT_*
+EXTRACT_STOP = ("max_iter", "labels", "shift")                             # PNR_EXTRACT_STOP_CAP, _LABELS, _SHIFT
+EXTRACT_OK, EXTRACT_EMPTIED, EXTRACT_NO_CENTER, EXTRACT_TOO_MANY, EXTRACT_FEW_POINTS = 0, 1, 2, 3, 4
+
+
+class ExtractAccumulateArgs(ctypes.Structure):
+    """Mirror of `pnr_extract_accumulate_args` (include/pnr.h)."""
+    _fields_ = [("H", _u32), ("W", _u32), ("weights_sum", _ptr), ("pixels", _ptr), ("image_format", _int), ("channels", _u32),
+                ("row_stride_bytes", _u64), ("linear", _int), ("thresh", _f32), ("counts_coarse", _ptr), ("counts_fine", _ptr), ("total", _ptr)]
+
+
+class ExtractKmeansArgs(ctypes.Structure):
+    """Mirror of `pnr_extract_kmeans_args` (include/pnr.h)."""
+    _fields_ = [("counts_coarse", _ptr), ("counts_fine", _ptr), ("total", _ptr), ("tau", ctypes.c_double), ("tol", ctypes.c_double), ("max_iter", _u32),
+                ("workspace", _ptr), ("workspace_bytes", _u64), ("centers", _ptr), ("center_weights", _ptr), ("info", _ptr), ("labels", _ptr)]
 
 
 _lib = None

@@ -29,6 +29,7 @@ int shade_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups
 int field_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);    // field.hip
 int mlp_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);      // mlp.hip
 int occupancy_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);   // occupancy.hip
+int extract_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);     // extract.hip
 
 // One process may drive several GPUs: function attributes and events belong to a device, so one-time set-up is tracked per device id.
 constexpr int kMaxDevices = 64;

@@ -6,6 +6,7 @@
 // Built with -ffp-contract=off like every unit: a * b + c below is two roundings, which is what torch's separate kernels give.
 #include "pnr_common.hpp"
 #include "ray_core.hpp"
+#include "image_core.hpp"
 
 namespace pnr {
 namespace {
@@ -13,42 +14,6 @@ namespace {
 constexpr uint32_t kBatchBlock = 256;
 
 __device__ __forceinline__ long long clamp_index(long long i, long long n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-
-// one pixel of C channels as fp32: fp32 as stored, fp16 converted exactly, uint8 as the loader's astype(float32) / 255.
-// vec: the stack's base allows one request per RGBA pixel (16 / 8 / 4 bytes).
-template <int FMT, int C>
-__device__ __forceinline__ void load_pixel(const void* __restrict__ images, uint64_t pix, bool vec, float (&px)[4]) {
-    if (FMT == PNR_IMAGE_FP32) {
-        const float* s = reinterpret_cast<const float*>(images) + pix * C;
-        if (C == 4 && vec) {
-            const float4 q = *reinterpret_cast<const float4*>(s);
-            px[0] = q.x; px[1] = q.y; px[2] = q.z; px[3] = q.w;
-        } else {
-#pragma unroll
-            for (int c = 0; c < C; c++) px[c] = s[c];
-        }
-    } else if (FMT == PNR_IMAGE_FP16) {
-        const __half* s = reinterpret_cast<const __half*>(images) + pix * C;
-        if (C == 4 && vec) {
-            const uint2 q = *reinterpret_cast<const uint2*>(s);
-#pragma unroll
-            for (int c = 0; c < 4; c++) px[c] = __half2float(__ushort_as_half((unsigned short)(((c < 2 ? q.x : q.y) >> (16 * (c & 1))) & 0xffffu)));
-        } else {
-#pragma unroll
-            for (int c = 0; c < C; c++) px[c] = __half2float(s[c]);
-        }
-    } else {
-        const uint8_t* s = reinterpret_cast<const uint8_t*>(images) + pix * C;
-        if (C == 4 && vec) {
-            const uint32_t q = *reinterpret_cast<const uint32_t*>(s);
-#pragma unroll
-            for (int c = 0; c < 4; c++) px[c] = (float)((q >> (8 * c)) & 0xffu) / 255.0f;
-        } else {
-#pragma unroll
-            for (int c = 0; c < C; c++) px[c] = (float)s[c] / 255.0f;
-        }
-    }
-}
 
 template <int FMT, int C>
 __global__ void __launch_bounds__(kBatchBlock) k_train_batch(const pnr_train_batch_args a, const int vec) {
@@ -85,7 +50,7 @@ __global__ void __launch_bounds__(kBatchBlock) k_train_batch(const pnr_train_bat
 #pragma unroll 1
     for (int c = 0; c < 3; c++) {      // (rolled: one copy of powf)
         float x = px[c];
-        if (a.srgb_to_linear) x = x < 0.04045f ? x / 12.92f : powf((x + 0.055f) / 1.055f, 2.4f);     // nerf/utils.py:48-49
+        if (a.srgb_to_linear) x = srgb_to_linear(x);
         if (C == 4) {
             const float bg = a.bg_mode == 0 ? a.bg_const : (a.bg_mode == 1 ? a.bg_color[c] : a.bg_color[r * 3 + c]);
             x = x * px[3] + bg * (1.0f - px[3]);                                                    // palette/utils.py:471

@@ -1,0 +1,364 @@
+"""The front end of the palette extraction on the device: `PaletteTrainer.extract_palette` (palette/utils.py:1135-1200) into `palette_extraction`
+as far as `run_kmeans`' return (:167-226) -- step 2 of the reference's workflow, between the NeRF stage and the PaletteNeRF stage.
+
+The reference renders every training view, keeps four per-pixel arrays for the pixels with weights_sum > 0.5, concatenates them over all views,
+copies them to the host, histograms them twice on one core and runs scikit-learn's weighted KMeans on the non-empty fine bins.  All the later
+stages need from that are two histograms (512 + 32 768 counts) and K <= 124 colour centres with their weights.  Here a view is ONE launch that
+folds it into both histograms (`pnr_extract_accumulate`: integer counts, so exact and independent of order), the whole weighted k-means is ONE
+launch (`pnr_extract_kmeans`: float64, fixed summation order), and a few kilobytes are read back once.
+
+    res = extract.extract_centers(model, poses, intrinsics, H, W, trainset)            # or an image stack, host or device
+    palette = Hull_Simplification_posternerf(res["centers"], prefix, pixel_counts=res["center_weights"], ...)      # the reference's rgbsg package
+
+The hull simplification and the weight LUT stay with the reference's CPU package.  The `extract-radiance-raw.png` debugging
+image of palette/utils.py:196-203 needs every sample on the host and is not produced.  `extract_centers_per_op` is the reference's own sequence,
+kept to measure and test against.  There is no fallback: on a CPU tensor or without the HIP library the device functions raise."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._torch_glue import stream_ptr
+
+_FORMAT_OF = {torch.float32: _lib.IMAGE_FP32, torch.float16: _lib.IMAGE_FP16, torch.uint8: _lib.IMAGE_UINT8}
+_BINS = {3: _lib.EXTRACT_COARSE_BINS, 5: _lib.EXTRACT_FINE_BINS}
+_STATUS_TEXT = {_lib.EXTRACT_NO_CENTER: "no coarse bin is heavier than tau (K = 0): nothing to cluster",
+                _lib.EXTRACT_TOO_MANY: f"more than {_lib.EXTRACT_MAX_K} coarse bins are heavier than tau (K above the compiled cap)",
+                _lib.EXTRACT_FEW_POINTS: "fewer non-empty fine bins than centres (P < K)"}
+
+
+def bin_centers_of(bits):
+    """The reference's bin centres (palette/src/bindings.cpp:77-87) as float32 [2^(3 bits), 3]: (code + 0.5) / 2^bits per channel, r most significant."""
+    code = np.arange(1 << (3 * bits), dtype=np.int64)
+    mask = (1 << bits) - 1
+    c = np.stack([(code >> (2 * bits)) & mask, (code >> bits) & mask, code & mask], axis=1).astype(np.float32)
+    return (c + np.float32(0.5)) / np.float32(1 << bits)
+
+
+class RadianceHistogram:
+    """The two count tables of the extraction (3 and 5 bits per channel) and the number of valid samples, on the device as int64.
+    `update` is one launch and reads nothing back; `counts`, `bin_weights`, `bin_centers` are device tensors; `total` is a read-back."""
+
+    def __init__(self, device="cuda"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("RadianceHistogram needs the HIP path (a CUDA/HIP device); there is no CPU fallback")
+        self._buf = torch.zeros(_BINS[3] + _BINS[5] + 1, dtype=torch.int64, device=self.device)      # coarse | fine | total
+
+    def clear(self):
+        self._buf.zero_()
+
+    def counts(self, bits):
+        """The int64 table of `bits` (3 or 5) bits per channel, a view of the live buffer."""
+        if bits not in _BINS:
+            raise ValueError("RadianceHistogram: the tables have 3 and 5 bits per channel")
+        return self._buf[:_BINS[3]] if bits == 3 else self._buf[_BINS[3]:_BINS[3] + _BINS[5]]
+
+    @property
+    def total_tensor(self):
+        return self._buf[_BINS[3] + _BINS[5]:]
+
+    @property
+    def total(self):
+        """The number of valid samples so far (synchronises: one int64 read back)."""
+        return int(self.total_tensor.item())
+
+    def bin_weights(self, bits):
+        """compute_RGB_histogram's first result for unit weights: float64 [2^(3 bits)] on the device (the counts, not normalised)."""
+        return self.counts(bits).to(torch.float64)
+
+    def bin_centers(self, bits):
+        """compute_RGB_histogram's second result: float32 [2^(3 bits), 3] on the device."""
+        if bits not in _BINS:
+            raise ValueError("RadianceHistogram: the tables have 3 and 5 bits per channel")
+        return torch.from_numpy(bin_centers_of(bits)).to(self.device)
+
+    def load_counts(self, coarse, fine, total=None):
+        """Replace the tables (a saved run, a test): coarse [512], fine [32768] integer counts; total defaults to coarse.sum()."""
+        coarse = torch.as_tensor(np.asarray(coarse), dtype=torch.int64).reshape(-1)
+        fine = torch.as_tensor(np.asarray(fine), dtype=torch.int64).reshape(-1)
+        if coarse.numel() != _BINS[3] or fine.numel() != _BINS[5] or bool((coarse < 0).any()) or bool((fine < 0).any()):
+            raise ValueError("RadianceHistogram.load_counts: coarse [512] and fine [32768] non-negative counts")
+        total = int(coarse.sum()) if total is None else int(total)
+        self._buf.copy_(torch.cat([coarse, fine, torch.tensor([total], dtype=torch.int64)]).to(self.device))
+        return self
+
+    def update(self, weights_sum, pixels, linear=False, thresh=0.5):
+        """Fold one view in: weights_sum [H W] fp32 on the device (the frame's output, read where it lies), pixels [H,W,3 or 4] (or [N,3 or 4]) as
+        fp32, fp16 or uint8 -- the ground truth as TrainSet stores it; rows may be padded, alpha is not read; a host array is uploaded.
+        valid = weights_sum > thresh; linear: srgb_to_linear on the pixel first.  ONE launch, no synchronisation."""
+        if not torch.is_tensor(pixels):
+            pixels = torch.from_numpy(np.asarray(pixels))
+        if pixels.dtype == torch.float64:
+            pixels = pixels.to(torch.float32)
+        if pixels.dtype not in _FORMAT_OF:
+            raise ValueError(f"RadianceHistogram.update: pixels must be float32, float16 or uint8, got {pixels.dtype}")
+        if pixels.ndim == 2:
+            pixels = pixels[None]
+        if pixels.ndim != 3 or pixels.shape[2] not in (3, 4):
+            raise ValueError(f"RadianceHistogram.update: pixels must be [H,W,3 or 4] or [N,3 or 4], got {tuple(pixels.shape)}")
+        if pixels.device != self.device:
+            pixels = pixels.to(self.device, non_blocking=True)
+        H, W, C = pixels.shape
+        if pixels.numel() and (pixels.stride(2) != 1 or pixels.stride(1) != C or (H > 1 and pixels.stride(0) < W * C)):
+            pixels = pixels.contiguous()
+        if not torch.is_tensor(weights_sum) or weights_sum.dtype != torch.float32 or weights_sum.device != self.device:
+            raise RuntimeError("RadianceHistogram.update: weights_sum must be a float32 tensor on the histogram's device")
+        if weights_sum.numel() != H * W:
+            raise ValueError(f"RadianceHistogram.update: weights_sum has {weights_sum.numel()} values, the view {H} x {W} pixels")
+        weights_sum = weights_sum.detach()
+        if not weights_sum.is_contiguous():
+            weights_sum = weights_sum.contiguous()
+        a = _lib.ExtractAccumulateArgs()
+        a.H, a.W, a.channels, a.image_format = H, W, C, _FORMAT_OF[pixels.dtype]
+        a.weights_sum, a.pixels = weights_sum.data_ptr(), pixels.data_ptr()
+        a.row_stride_bytes = (pixels.stride(0) if H > 1 else W * C) * pixels.element_size()
+        a.linear, a.thresh = int(bool(linear)), float(thresh)
+        a.counts_coarse, a.counts_fine, a.total = self.counts(3).data_ptr(), self.counts(5).data_ptr(), self.total_tensor.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pnr_extract_accumulate(ctypes.byref(a), stream_ptr()), "pnr_extract_accumulate")
+        return self
+
+
+def _view_source(images, device):
+    """view i of the ground truth -> a [H,W,C] tensor: a TrainSet's device-resident stack and a device stack are indexed (a view, no copy);
+    a host stack is uploaded view by view."""
+    stack = getattr(images, "images", None) if not torch.is_tensor(images) and not isinstance(images, np.ndarray) else None
+    if stack is not None:                                   # a TrainSet
+        return lambda i: stack[i]
+    if torch.is_tensor(images) and images.is_cuda:
+        return lambda i: images[i]
+    return lambda i: torch.as_tensor(np.asarray(images[i]) if not torch.is_tensor(images) else images[i]).to(device, non_blocking=True)
+
+
+def _render_kwargs(model, render_kwargs):
+    kw = dict(render_kwargs, bg_color=None, perturb=False)              # test_step's defaults (palette/utils.py:938-946)
+    if hasattr(model, "num_basis"):
+        kw.setdefault("gui_mode", True)                                # only weights_sum is read: the frame without the per-basis maps (pass gui_mode=False for test_step's own)
+    return kw
+
+
+def radiance_histograms(model, poses, intrinsics, H, W, images, linear=False, thresh=0.5, hist=None, frames_in_flight=1, **render_kwargs):
+    """The loop of extract_palette (palette/utils.py:1157-1194) for a NeRF or a PaletteNeRF model: for every view, rays on the device, a frame
+    with bg_color = None and perturb = False through pipeline.render_queue (frame i + 1 is prepared under frame i; frames_in_flight > 1:
+    pipeline.FramesInFlight instead), then ONE launch that folds the view into both histograms.  images: [n,H,W,3 or 4] host or device stack
+    (fp32, fp16 or uint8), or a TrainSet, whose device-resident stack is read in place.  linear: the scene's colour space is linear
+    (TrainSet.color_space == "linear").  Nothing is read back.  Returns the RadianceHistogram (`hist`, or a new one)."""
+    from . import pipeline
+    from . import rays as prays
+    device = next(model.parameters()).device
+    poses = torch.as_tensor(poses, dtype=torch.float32).reshape(-1, 4, 4).to(device)
+    n = poses.shape[0]
+    if hist is None:
+        hist = RadianceHistogram(device)
+    view = _view_source(images, device)
+    kw = _render_kwargs(model, render_kwargs)
+
+    def rays_of(i):
+        return prays.rays_from_indices(poses[i:i + 1], intrinsics, H, W, None)
+
+    def use(i, r):
+        hist.update(r["weights_sum"].reshape(-1), view(i), linear=linear, thresh=thresh)
+
+    if int(frames_in_flight) > 1 and n > 1:
+        fif = pipeline.FramesInFlight(model, min(int(frames_in_flight), n), device)
+        try:
+            fif.render(rays_of, n, consume=use, **kw)
+        finally:
+            fif.close()
+    else:
+        pipeline.render_queue(model, rays_of, n, consume=use, **kw)
+    return hist
+
+
+# ---------------------------------------------------------------- k-means on the host: the per-op leg and the emptied-cluster hand-over
+def _labels_of(X, centers):
+    d = X[:, None, :] - centers[None, :, :]
+    d *= d
+    return np.argmin((d[..., 0] + d[..., 1]) + d[..., 2], axis=1)
+
+
+def lloyd_host(X, w, init, max_iter=300, tol=1e-4):
+    """scikit-learn's _kmeans_single_lloyd (1.7: sklearn/cluster/_kmeans.py, _k_means_lloyd.pyx, _k_means_common.pyx) in numpy float64, WITH the
+    relocation of emptied clusters (_relocate_empty_clusters_dense) -- what pnr_extract_kmeans hands over when a cluster loses its points, and what
+    the per-op leg runs where scikit-learn is not installed.  X [P,3], w [P], init [K,3].  Returns (centers [K,3], labels [P], iterations, stop),
+    stop in ("labels", "shift", "max_iter").  scikit-learn's centring of X and its float32 rounding are not imitated."""
+    X, w = np.asarray(X, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    centers = np.array(init, dtype=np.float64)
+    K = centers.shape[0]
+    tol_abs = np.mean(np.var(X, axis=0)) * tol
+    labels_old = np.full(X.shape[0], -1, dtype=np.int64)
+    stop, it = "max_iter", 0
+    for it in range(int(max_iter)):
+        labels = _labels_of(X, centers)
+        sums, wk = np.zeros((K, 3)), np.zeros(K)
+        np.add.at(sums, labels, w[:, None] * X)
+        np.add.at(wk, labels, w)
+        empty = np.where(wk == 0)[0]
+        if empty.size:                                           # _relocate_empty_clusters_dense
+            dist = ((X - centers[labels]) ** 2).sum(axis=1)
+            far = np.argpartition(dist, -empty.size)[:-empty.size - 1:-1]
+            if dist.max() != 0:
+                for new, f in zip(empty, far):
+                    old = labels[f]
+                    sums[old] -= X[f] * w[f]
+                    sums[new] = X[f] * w[f]
+                    wk[new] = w[f]
+                    wk[old] -= w[f]
+        new = sums
+        heaviest = int(np.argmax(wk))
+        for k in range(K):                                       # _average_centers, in its order
+            new[k] = new[k] * (1.0 / wk[k]) if wk[k] > 0 else new[heaviest]
+        shift = np.sqrt(((new - centers) ** 2).sum(axis=1))      # _center_shift, squared again by the caller
+        centers = new
+        if np.array_equal(labels, labels_old):
+            stop = "labels"
+            break
+        if (shift ** 2).sum() <= tol_abs:
+            stop = "shift"
+            break
+        labels_old = labels
+    if stop != "labels":
+        labels = _labels_of(X, centers)
+    return centers, labels, it + 1, stop
+
+
+def sort_centers(centers, labels, w):
+    """run_kmeans' tail (palette/utils.py:159-165): the weight of every cluster, both sorted by descending weight, ties to the lower cluster index."""
+    K = centers.shape[0]
+    cw = np.array([np.sum(w[labels == k]) for k in range(K)], dtype=np.float64)
+    order = np.argsort(-cw, kind="stable")
+    return centers[order], cw[order]
+
+
+def points_of(counts_coarse, counts_fine, total, tau):
+    """palette/utils.py:209-222 from the count tables: (points [P,3], weights [P], init [K,3]) in float64."""
+    coarse, fine = np.asarray(counts_coarse, dtype=np.float64), np.asarray(counts_fine, dtype=np.float64)
+    total = float(total)
+    heavy = coarse / total > tau if total > 0 else np.zeros(coarse.shape, dtype=bool)
+    some = fine > 0
+    return bin_centers_of(5)[some].astype(np.float64), fine[some] / total, bin_centers_of(3)[heavy].astype(np.float64)
+
+
+def kmeans_centers(hist, tau=8e-3, max_iter=300, tol=1e-4, return_labels=False):
+    """The rest of palette_extraction up to run_kmeans' return, from a RadianceHistogram: ONE launch and ONE read-back of 4 KB.
+    Returns (centers [K,3] float64, center_weights [K] float64, info): the arguments of Hull_Simplification_posternerf(centers, ...,
+    pixel_counts=center_weights).  info: K, P, iterations, stop ("labels", "shift" or "max_iter"), emptied (False, or the iteration at which a
+    cluster lost its points: from there the loop was finished on the host with scikit-learn's relocation rule, lloyd_host), and with
+    return_labels the final label of every point (before the sort), a second read-back.  K = 0, K > 128 and P < K raise RuntimeError."""
+    lib = _lib.load()
+    dev = hist.device
+    kmax = _lib.EXTRACT_MAX_K
+    out = torch.empty(4 * kmax + 4, dtype=torch.float64, device=dev)                 # centres | weights | info (8 int32)
+    labels = torch.empty(_BINS[5], dtype=torch.int32, device=dev) if return_labels else None
+    ws_bytes = int(lib.pnr_extract_kmeans_workspace_bytes())
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    a = _lib.ExtractKmeansArgs()
+    a.counts_coarse, a.counts_fine, a.total = hist.counts(3).data_ptr(), hist.counts(5).data_ptr(), hist.total_tensor.data_ptr()
+    a.tau, a.tol, a.max_iter = float(tau), float(tol), int(max_iter)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+    a.centers, a.center_weights, a.info = out.data_ptr(), out.data_ptr() + 8 * 3 * kmax, out.data_ptr() + 8 * 4 * kmax
+    a.labels = None if labels is None else labels.data_ptr()
+    with torch.cuda.device(dev):
+        _lib.check(lib.pnr_extract_kmeans(ctypes.byref(a), stream_ptr()), "pnr_extract_kmeans")
+    host = out.cpu().numpy()
+    K, P, iters, stop, status = (int(v) for v in host[4 * kmax:].view(np.int32)[:5])
+    if status in _STATUS_TEXT:
+        raise RuntimeError(f"pnr_extract_kmeans: {_STATUS_TEXT[status]} (K = {K}, P = {P}, tau = {tau})")
+    info = {"K": K, "P": P, "iterations": iters, "stop": _lib.EXTRACT_STOP[stop], "emptied": False}
+    centers, cw = host[:3 * K].reshape(K, 3).copy(), host[3 * kmax:3 * kmax + K].copy()
+    lab = None if labels is None else labels[:P].cpu().numpy().astype(np.int64)
+    if status == _lib.EXTRACT_EMPTIED:
+        buf = hist._buf.cpu().numpy()
+        X, w, _ = points_of(buf[:_BINS[3]], buf[_BINS[3]:_BINS[3] + _BINS[5]], buf[-1], tau)
+        c, lab, n, stop = lloyd_host(X, w, centers, max_iter=int(max_iter) - iters, tol=tol)
+        centers, cw = sort_centers(c, lab, w)
+        info.update(iterations=iters + n, stop=stop, emptied=iters)
+    if return_labels:
+        info["labels"] = lab
+    return centers, cw, info
+
+
+def _result(centers, cw, info, coarse, fine, total):
+    total = float(total)
+    return {"centers": centers, "center_weights": cw, "hist_coarse": np.asarray(coarse, dtype=np.float64) / total,
+            "hist_fine": np.asarray(fine, dtype=np.float64) / total, "hist_rgb": bin_centers_of(5), "total": int(total), "info": info}
+
+
+def extract_centers(model, poses, intrinsics, H, W, images, linear=False, thresh=0.5, tau=8e-3, max_iter=300, tol=1e-4, frames_in_flight=1,
+                    **render_kwargs):
+    """radiance_histograms + kmeans_centers.  Returns a dict: centers [K,3] and center_weights [K] (float64, by descending weight), hist_coarse
+    [512] and hist_fine [32768] (float64, the two histograms over the number of valid samples), hist_rgb [32768,3] (float32: the 5-bit bin
+    centres the reference's weight-LUT step reads, palette/utils.py:235), total, info (kmeans_centers)."""
+    hist = radiance_histograms(model, poses, intrinsics, H, W, images, linear=linear, thresh=thresh, frames_in_flight=frames_in_flight, **render_kwargs)
+    centers, cw, info = kmeans_centers(hist, tau=tau, max_iter=max_iter, tol=tol)
+    buf = hist._buf.cpu().numpy()
+    return _result(centers, cw, info, buf[:_BINS[3]], buf[_BINS[3]:_BINS[3] + _BINS[5]], buf[-1])
+
+
+_SAVED = ("centers", "center_weights", "hist_coarse", "hist_fine", "hist_rgb")
+
+
+def save_centers(path, result):
+    """The arrays of an extract_centers result (and its total) as one .npz."""
+    np.savez(path, total=np.int64(result["total"]), **{k: np.asarray(result[k]) for k in _SAVED})
+
+
+def load_centers(path):
+    with np.load(path) as z:
+        out = {k: z[k] for k in _SAVED}
+        out["total"] = int(z["total"])
+    return out
+
+
+def _pixels_float(t):
+    """a stored view as the loader's fp32 pixels: uint8 / 255, fp16 converted exactly"""
+    return t.to(torch.float32) / 255 if t.dtype == torch.uint8 else t.to(torch.float32)
+
+
+def extract_centers_per_op(model, poses, intrinsics, H, W, images, linear=False, thresh=0.5, tau=8e-3, max_iter=300, tol=1e-4, kmeans="auto",
+                           **render_kwargs):
+    """The reference's own sequence (palette/utils.py:1157-1200, :189-226), op by op -- what extract_centers is measured and tested against: per
+    view the torch expressions and a boolean-mask gather, torch.cat over the views and .cpu(), compute_RGB_histogram twice on the samples, and
+    sklearn.cluster.KMeans where it can be imported (otherwise, or with kmeans="host", lloyd_host in float64).  Returns extract_centers' dict."""
+    from . import palette_utils
+    from . import rays as prays
+    device = next(model.parameters()).device
+    poses = torch.as_tensor(poses, dtype=torch.float32).reshape(-1, 4, 4).to(device)
+    view = _view_source(images, device)
+    kw = _render_kwargs(model, render_kwargs)
+    kept = []
+    with torch.no_grad():
+        for i in range(poses.shape[0]):
+            ro, rd = prays.rays_from_indices(poses[i:i + 1], intrinsics, H, W, None)
+            r = model.render(ro, rd, **kw)
+            preds = _pixels_float(view(i))[..., :3].reshape(-1, 3)
+            if linear:
+                preds = torch.where(preds < 0.04045, preds / 12.92, ((preds + 0.055) / 1.055) ** 2.4)
+            norm = preds + 0.05
+            norm = norm / norm.norm(dim=-1, p=2, keepdim=True)
+            kept.append(norm[r["weights_sum"].reshape(-1) > thresh])
+        colors = torch.cat(kept, dim=0).detach().cpu().numpy()
+    weights = np.ones_like(colors[..., 0])
+    coarse, centers_coarse = palette_utils.compute_RGB_histogram(colors, weights, 3)
+    total = np.sum(coarse)
+    fine, centers_fine = palette_utils.compute_RGB_histogram(colors, weights, 5)
+    heavy, some = coarse / total > tau, fine > 0
+    X, w, init = centers_fine[some], fine[some] / total, centers_coarse[heavy]
+    if init.shape[0] == 0 or X.shape[0] < init.shape[0]:
+        raise RuntimeError(f"extract_centers_per_op: K = {init.shape[0]} centres for P = {X.shape[0]} points")
+    KMeans = None
+    if kmeans != "host":
+        try:
+            from sklearn.cluster import KMeans
+        except ImportError:
+            pass
+    if KMeans is not None:
+        km = KMeans(n_clusters=init.shape[0], init=init, max_iter=max_iter, tol=tol).fit(X=X, sample_weight=w)
+        c, labels, n, stop = km.cluster_centers_.astype(np.float64), km.labels_, km.n_iter_, None
+    else:
+        c, labels, n, stop = lloyd_host(X, w, init, max_iter=max_iter, tol=tol)
+    centers, cw = sort_centers(c, labels, w)
+    info = {"K": init.shape[0], "P": X.shape[0], "iterations": int(n), "stop": stop, "emptied": False}
+    return _result(centers, cw, info, coarse, fine, total)
