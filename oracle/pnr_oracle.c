@@ -20,9 +20,11 @@
  *     (oracle/ref_build.py: build_hip -> oracle/_ref/ref_*.so), and tests/test_gpu_reference_kernels.py runs them on the MI355X next to
  *     this repository's kernels: bit-identical for march / composite / Morton / packbits / near-far, <= 2e-6 for the rest.  This library
  *     agrees with the kernels of this repository bit for bit on the same functions, hence with the reference's.
- *   - hash-grid encoder kernels: gridencoder.cu does not compile for gfx950 (atomicAdd(__half2*, __half2) is missing in ROCm 7.2 HIP),
- *     so its arithmetic is pinned through the reference's GridEncoder wrapper over this restatement and by independent int64 / float64
- *     formulations in tests/ -- "parity unpinned by execution" for that one extension.
+ *   - hash-grid encoder kernels: gridencoder.cu is built by the same recipe, with this repository's stand-in for the one overload ROCm 7.2's
+ *     HIP headers lack (atomicAdd(__half2*, __half2), oracle/ref_half2_atomic.h; only the fp16 table gradient with an even feature count
+ *     reaches it), and tests/test_gpu_reference_grid.py runs kernel_grid / kernel_grid_backward / kernel_input_backward on the MI355X next
+ *     to this restatement and this repository's kernels: inside the float64 bounds of tests/grid_reference.py in every cell, dy_dx
+ *     bit-identical, the forward bit-identical to this library's from C = 2 on (profiles/reference_grid/README.md).
  *
  * Canonical scalar spec (shared *by description*, not by header, with the HIP kernels):
  *   - IEEE fp32, no implicit contraction (-ffp-contract=off); the places where the reference's

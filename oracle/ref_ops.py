@@ -1,6 +1,6 @@
 """The reference's Python operator layer restated over the REFERENCE-BUILT extension modules (oracle/_ref/ref_*.so: raymarching.cu, shencoder.cu,
-palette.cu of /root/reference compiled for gfx950, oracle/ref_build.py).  TEST INFRASTRUCTURE: tests/test_gpu_reference_kernels.py and bench.py's
-`extra.reference_kernels` leg only.  The reference's raymarching/raymarching.py cannot travel to the GPU box, so the few lines each wrapper adds
+palette.cu and gridencoder.cu of /root/reference compiled for gfx950, oracle/ref_build.py).  TEST INFRASTRUCTURE: tests/test_gpu_reference_kernels.py,
+tests/test_gpu_reference_grid.py and bench.py's `extra.reference_kernels` leg only.  The reference's raymarching/raymarching.py cannot travel to the GPU box, so the few lines each wrapper adds
 around its `_backend` call -- which buffers it allocates, which are zero-filled, the always-pad alignment, the slice to the counter -- are restated
 here, citing the lines; the kernels underneath are the reference's own."""
 import types
@@ -111,11 +111,77 @@ class SHEncoder(torch.nn.Module):
         return out.reshape(lead + [self.output_dim])
 
 
+def grid_available():
+    """oracle/_ref/ref_gridencoder.so is there (apart from available(): bench.py's reference leg is keyed on the three older extensions alone)."""
+    return ref_build.hip_available("gridencoder")
+
+
+_grid_backend = None
+
+
+def _grid():
+    global _grid_backend
+    if _grid_backend is None:
+        _grid_backend = ref_build.load_hip("gridencoder")
+    return _grid_backend
+
+
+class _grid_encode(torch.autograd.Function):
+    """gridencoder/grid.py:19-84 over the reference's own kernel_grid / kernel_grid_backward / kernel_input_backward."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")                                                      # grid.py:21 (no cast_inputs: only the autocast state is kept)
+    def forward(ctx, inputs, embeddings, offsets, per_level_scale, base_resolution, calc_grad_inputs=False, gridtype=0, align_corners=False):
+        import numpy as np
+        inputs = inputs.contiguous()                                                              # :28
+        B, D = inputs.shape                                                                       # :30
+        L, C = offsets.shape[0] - 1, embeddings.shape[1]                                          # :31-32
+        S, H = np.log2(per_level_scale), base_resolution                                          # :33-34
+        if torch.is_autocast_enabled() and C % 2 == 0:                                            # :38-39: a half table only for an even feature count
+            embeddings = embeddings.to(torch.half)
+        outputs = torch.empty(L, B, C, device=inputs.device, dtype=embeddings.dtype)              # :42
+        dy_dx = torch.empty(B, L * D * C, device=inputs.device, dtype=embeddings.dtype) if calc_grad_inputs else None      # :44-47
+        _grid().grid_encode_forward(inputs, embeddings, offsets, outputs, B, D, C, L, S, H, dy_dx, gridtype, align_corners)   # :49
+        outputs = outputs.permute(1, 0, 2).reshape(B, L * C)                                      # :52
+        ctx.save_for_backward(inputs, embeddings, offsets, dy_dx)                                 # :54
+        ctx.dims, ctx.align_corners = [B, D, C, L, S, H, gridtype], align_corners                 # :55-56
+        return outputs
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")                                                      # :62
+    def backward(ctx, grad):
+        inputs, embeddings, offsets, dy_dx = ctx.saved_tensors                                    # :65
+        B, D, C, L, S, H, gridtype = ctx.dims
+        grad = grad.view(B, L, C).permute(1, 0, 2).contiguous()                                   # :70
+        grad_embeddings = torch.zeros_like(embeddings)                                            # :72
+        grad_inputs = torch.zeros_like(inputs, dtype=embeddings.dtype) if dy_dx is not None else None                      # :74-77
+        _grid().grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
+                                     ctx.align_corners)                                           # :79
+        if dy_dx is not None:
+            grad_inputs = grad_inputs.to(inputs.dtype)                                            # :81-82
+        return grad_inputs, grad_embeddings, None, None, None, None, None, None
+
+
+def grid_encode(inputs, embeddings, offsets, per_level_scale, base_resolution, calc_grad_inputs=False, gridtype=0, align_corners=False):
+    """The reference's `grid_encode` (gridencoder/grid.py:88) over oracle/_ref/ref_gridencoder.so.  `grid_encode.calls` counts the calls (a test
+    that swaps it in shows with it that the lookups really went here)."""
+    grid_encode.calls += 1
+    return _grid_encode.apply(inputs, embeddings, offsets, per_level_scale, base_resolution, calc_grad_inputs, gridtype, align_corners)
+
+
+grid_encode.calls = 0
+
+
 class swapped_in:
-    """Context manager: this repository's renderer / network mirror running on the REFERENCE's march, composite and SH kernels (the hash grid
-    stays this repository's: gridencoder.cu does not compile for HIP).  `sh_encode_cat` -- this repository's fused [SH | geo] launch -- is
-    replaced by the reference's plain `torch.cat([encoder_dir(d), geo_feat])` (nerf/network.py:109-115) so that the SH values really come
-    from kernel_sh."""
+    """Context manager: this repository's renderer / network mirror running on the REFERENCE's march, composite and SH kernels, and with
+    `grid=True` on the reference's hash-grid kernels as well (default False: the hash grid stays this repository's, which is what bench.py's
+    reference leg measures).  `sh_encode_cat` -- this repository's fused [SH | geo] launch -- is replaced by the reference's plain
+    `torch.cat([encoder_dir(d), geo_feat])` (nerf/network.py:109-115) so that the SH values really come from kernel_sh.  grid=True replaces
+    `palettenerf_amd.gridencoder.grid_encode` (what GridEncoder.forward calls) and sends the network mirror's `encode_mlp` down its plain
+    composition `run_mlp(net, cat([encoder(x, bound), tail]))`, so that no fused launch looks the table up with this repository's kernel."""
+
+    def __init__(self, grid=False):
+        self._grid = grid
 
     def __enter__(self):
         from palettenerf_amd import network, renderer
@@ -124,9 +190,25 @@ class swapped_in:
         self._saved = (renderer.raymarching, psh.SHEncoder, network.sh_encode_cat)
         renderer.raymarching, psh.SHEncoder = raymarching_module(), SHEncoder
         network.sh_encode_cat = lambda enc, d, tail: torch.cat([enc(d), tail], dim=-1)
+        if self._grid:
+            import palettenerf_amd.gridencoder as pge
+            from palettenerf_amd import mlp
+            self._saved_grid = (pge.grid_encode, network.encode_mlp)
+            pge.grid_encode = grid_encode
+
+            def encode_mlp(encoder, x, bound, tail, net, act=torch.nn.functional.relu, enc=None):
+                h = encoder(x, bound=bound)
+                if tail is not None:
+                    h = torch.cat([h, tail], dim=-1)
+                return mlp.run_mlp(net, h, act)
+
+            network.encode_mlp = encode_mlp
         return self
 
     def __exit__(self, *exc):
         renderer, psh, network = self._mods
         renderer.raymarching, psh.SHEncoder, network.sh_encode_cat = self._saved
+        if self._grid:
+            import palettenerf_amd.gridencoder as pge
+            pge.grid_encode, network.encode_mlp = self._saved_grid
         return False

@@ -1,5 +1,5 @@
 """Float64 statement of the multiresolution grid encoder for any D, C, gridtype and align_corners, with the error bounds the tests hold the oracle and
-the HIP kernels to.  TEST HELPER (imported by tests/test_oracle.py, tests/test_gpu_grid_variants.py and tests/test_gpu_grid_binned.py); numpy only, no GPU.
+the HIP kernels to.  TEST HELPER (imported by tests/test_oracle.py, tests/test_gpu_grid_variants.py, tests/test_gpu_grid_binned.py and tests/test_gpu_reference_grid.py); numpy only, no GPU.
 
 What is shared with the code under test are the kernels' INPUTS only: the per-level (scale, resolution) of oracle.grid_level_params and the fp32 cell
 position (one rounding of x * scale [+ 0.5], its floor, the fp32 fractional part).  Everything after that -- corner weights, sums, differences, scatter --
@@ -117,6 +117,35 @@ class GridReference:
             for ch in range(C):
                 gt[:, ch] += np.bincount(rows, weights=t[:, ch], minlength=self.rows_total)
                 mag[:, ch] += np.bincount(rows, weights=np.abs(t[:, ch]), minlength=self.rows_total)
+        return gt, mag, n
+
+    def table_grad_sparse(self, grad):
+        """table_grad() restricted to the rows a sample reaches -> (touched rows [T] ascending, d / d table [T, C], sum |w g| [T, C], addends [T]).  For
+        tables of millions of rows of which a batch touches few: the same addends summed in the same order (np.bincount adds in input order), so the
+        values are those of table_grad() bit for bit (tests/test_oracle.py shows it on a variant case)."""
+        g = np.asarray(grad, np.float64).reshape(self.B, self.L, -1)
+        C = g.shape[2]
+        sel = self.inr
+        touched, compact = np.unique(self.rows[:, :, sel], return_inverse=True)
+        compact = compact.reshape(self.L, 1 << self.D, -1)
+        T = len(touched)
+        gt, mag, n = np.zeros((T, C)), np.zeros((T, C)), np.zeros(T, np.int64)
+        corners = np.arange(1 << self.D)
+        for l in range(self.L):
+            rows = compact[l].reshape(-1)
+            t = (self._weights(l, corners)[:, sel, None] * g[sel, l][None]).reshape(-1, C)
+            n += np.bincount(rows, minlength=T)
+            for ch in range(C):
+                gt[:, ch] += np.bincount(rows, weights=t[:, ch], minlength=T)
+                mag[:, ch] += np.bincount(rows, weights=np.abs(t[:, ch]), minlength=T)
+        return touched, gt, mag, n
+
+    def table_grad_from_sparse(self, grad):
+        """table_grad()'s dense triple, assembled from table_grad_sparse()"""
+        touched, s_gt, s_mag, s_n = self.table_grad_sparse(grad)
+        gt, n = np.zeros((self.rows_total, s_gt.shape[1])), np.zeros(self.rows_total, np.int64)
+        mag = np.zeros_like(gt)
+        gt[touched], mag[touched], n[touched] = s_gt, s_mag, s_n
         return gt, mag, n
 
     def input_grad(self, grad, dy, dy_mag):

@@ -34,7 +34,7 @@ class _Checks:
     """Collects every miss of one test (so that one run shows them all) and the worst error / bound ratio per (dtype, quantity)."""
 
     def __init__(self):
-        self.fails, self.worst = [], {}
+        self.fails, self.worst, self.cells = [], {}, 0
 
     def bound(self, tag, dtype, what, got, want, bound):
         r = gr.error_ratio(got, want, bound)
@@ -58,47 +58,88 @@ def _encode(x, table, offsets, gridtype, ac, calc_grad_inputs=False):
     return gridencoder.grid_encode(x, table, offsets, PLS, H, calc_grad_inputs, gridtype, ac)
 
 
-def _one_table(ck, cuda, tag, dtype, ref, x, table, offsets, gridtype, ac, g, D, C):
-    """forward (without and with dy_dx), backward (with and without input gradients) of one table dtype against float64."""
-    B = x.shape[0]
-    u = gr.U32 if dtype == "fp32" else gr.U16
+# what one table is walked through; tests/test_gpu_reference_grid.py walks the reference's own kernel through the same
+QUANTITIES = ("forward", "forward with dy_dx", "dy_dx", "table gradient with input gradients", "table gradient without input gradients", "input gradient")
+FORWARD_QUANTITIES = QUANTITIES[:3]
+
+
+def run_table(encode, cuda, x, table, offsets, gridtype, ac, g, backward=True):
+    """{quantity: numpy array} of `encode` (the signature of _encode) for one table: forward (without and with dy_dx), dy_dx as the autograd function
+    saved it, and with `backward` the table gradient (with and without input gradients) and the input gradient.  "_out": the first forward's tensor."""
     tx, to = dev(x, cuda), dev(offsets, cuda)
-    out = _encode(tx, dev(table, cuda), to, gridtype, ac)
-    want, mag = ref.forward(table)
-    ck.true(tag, f"{dtype} output shape / dtype", out.shape == (B, L * C) and host(out).dtype == table.dtype)
-    ck.same_bits(tag, f"{dtype} forward against the oracle", host(out), oracle.grid_encode_forward(x, table, offsets, PLS, H, gridtype=gridtype, align_corners=ac))
-    ck.bound(tag, dtype, "forward", host(out).reshape(B, L, C), want, gr.forward_bound(D, mag, u))
-    ck.true(tag, f"{dtype} out-of-range rows give zeros", not host(out)[~ref.inr].any())
+    out = encode(tx, dev(table, cuda), to, gridtype, ac)
+    te, txg = dev(table, cuda).requires_grad_(True), dev(x, cuda).requires_grad_(True)
+    out2 = encode(txg, te, to, gridtype, ac, True)
+    q = {"_out": out, "forward": host(out), "forward with dy_dx": host(out2), "dy_dx": host(out2.grad_fn.saved_tensors[3])}
+    if backward:
+        (out2 * dev(g, cuda)).sum().backward()
+        te2 = dev(table, cuda).requires_grad_(True)
+        (encode(tx, te2, to, gridtype, ac) * dev(g, cuda)).sum().backward()
+        q["table gradient with input gradients"], q["table gradient without input gradients"] = host(te.grad), host(te2.grad)
+        q["input gradient"] = host(txg.grad)
+    return q
+
+
+def want_table(ref, table, g, sparse=False):
+    """The float64 values and magnitudes of one table, computed once for every subject that is held to them (sparse: the table gradient by way of
+    GridReference.table_grad_sparse, for a table of millions of rows; the same values)."""
+    w = {"forward": ref.forward(table), "dy_dx": ref.dy_dx(table), "table gradient": ref.table_grad_from_sparse(g) if sparse else ref.table_grad(g)}
+    w["input gradient"] = ref.input_grad(g, *w["dy_dx"])
+    return w
+
+
+def check_table(ck, tag, dtype, ref, x, table, offsets, gridtype, ac, g, D, C, q, want=None, oracle_per_level_scale=PLS, oracle_base=H):
+    """Holds the quantities of run_table to float64 (bounds of tests/grid_reference.py) and, for the forward, bit for bit to the oracle when
+    `oracle_per_level_scale` is given.  ck.cells counts the quantities checked."""
+    B, L_ = x.shape[0], ref.L
+    u = gr.U32 if dtype == "fp32" else gr.U16
+    w = want if want is not None else want_table(ref, table, g)
+    out = q["forward"]
+    fwd, mag = w["forward"]
+    ck.true(tag, f"{dtype} output shape / dtype", out.shape == (B, L_ * C) and out.dtype == table.dtype)
+    if oracle_per_level_scale is not None:
+        ck.same_bits(tag, f"{dtype} forward against the oracle", out,
+                     oracle.grid_encode_forward(x, table, offsets, oracle_per_level_scale, oracle_base, gridtype=gridtype, align_corners=ac))
+    ck.bound(tag, dtype, "forward", out.reshape(B, L_, C), fwd, gr.forward_bound(D, mag, u))
+    ck.true(tag, f"{dtype} out-of-range rows give zeros", not out[~ref.inr].any())
+    ck.cells += 1
 
     # with dy_dx, then backward through the autograd wrapper
-    te, txg = dev(table, cuda).requires_grad_(True), dev(x, cuda).requires_grad_(True)
-    out2 = _encode(txg, te, to, gridtype, ac, True)
-    ck.same_bits(tag, f"{dtype} forward with dy_dx requested", host(out2), host(out))
-    dy_gpu = host(out2.grad_fn.saved_tensors[3]).reshape(B, L, D, C)
-    dy, dmag = ref.dy_dx(table)
+    ck.same_bits(tag, f"{dtype} forward with dy_dx requested", q["forward with dy_dx"], out)
+    ck.cells += 1
+    dy_gpu = q["dy_dx"].reshape(B, L_, D, C)
+    dy, dmag = w["dy_dx"]
     ck.true(tag, f"{dtype} dy_dx dtype", dy_gpu.dtype == table.dtype)
-    ck.bound(tag, dtype, "dy_dx", dy_gpu, dy, gr.dy_dx_bound(D, dmag) if dtype == "fp32" else gr.input_grad_bound(D, L, C, dmag, u))
+    ck.bound(tag, dtype, "dy_dx", dy_gpu, dy, gr.dy_dx_bound(D, dmag) if dtype == "fp32" else gr.input_grad_bound(D, L_, C, dmag, u))
     ck.true(tag, f"{dtype} out-of-range rows give zero dy_dx", not dy_gpu[~ref.inr].any())
-    (out2 * dev(g, cuda)).sum().backward()
-    gt, gmag, n = ref.table_grad(g)
+    ck.cells += 1
+    if "input gradient" not in q:
+        return
+    gt, gmag, n = w["table gradient"]
     gbound = gr.table_grad_bound(D, gmag, n, u)
-    wi, imag = ref.input_grad(g, dy, dmag)
-    for label, grad in (("with input gradients", te.grad), ("without input gradients", None)):
-        if grad is None:
-            te2 = dev(table, cuda).requires_grad_(True)
-            (_encode(tx, te2, to, gridtype, ac) * dev(g, cuda)).sum().backward()
-            grad = te2.grad
-        got = host(grad)
+    wi, imag = w["input gradient"]
+    touched = n > 0      # the bound is 0 on every other row (no addend: sum |w g| = 0), which asks for the exact zeros of the line after it
+    gt_t, gbound_t = gt[touched], gbound[touched]
+    for label in ("with input gradients", "without input gradients"):
+        got = q[f"table gradient {label}"]
         ck.true(tag, f"{dtype} table gradient dtype {label}", got.dtype == table.dtype and got.shape == table.shape)
-        ck.bound(tag, dtype, "table gradient", got, gt, gbound)
-        ck.true(tag, f"{dtype} untouched rows are exactly 0 {label}", not got[n == 0].any())
+        ck.bound(tag, dtype, "table gradient", got[touched], gt_t, gbound_t)
+        ck.true(tag, f"{dtype} untouched rows are exactly 0 {label}", not got[~touched].any())
         r = abs(got.astype(np.float64).sum() - gt.sum()) / gbound.sum()
         ck.true(tag, f"{dtype} checksum of the table gradient {label}: error / summed bound = {r}", r <= 1.0)
-    gi = host(txg.grad)
+        ck.cells += 1
+    gi = q["input gradient"]
     ck.true(tag, f"{dtype} input gradient dtype", gi.dtype == np.float32 and gi.shape == x.shape)
-    ck.bound(tag, dtype, "input gradient", gi, wi, gr.input_grad_bound(D, L, C, imag, u))
+    ck.bound(tag, dtype, "input gradient", gi, wi, gr.input_grad_bound(D, L_, C, imag, u))
     ck.true(tag, f"{dtype} out-of-range rows get exactly 0 input gradient", not gi[~ref.inr].any())
-    return out
+    ck.cells += 1
+
+
+def _one_table(ck, cuda, tag, dtype, ref, x, table, offsets, gridtype, ac, g, D, C):
+    """forward (without and with dy_dx), backward (with and without input gradients) of one table dtype against float64."""
+    q = run_table(_encode, cuda, x, table, offsets, gridtype, ac, g)
+    check_table(ck, tag, dtype, ref, x, table, offsets, gridtype, ac, g, D, C, q)
+    return q["_out"]
 
 
 @pytest.mark.parametrize("C", [1, 2, 4, 8])

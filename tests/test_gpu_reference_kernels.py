@@ -2,8 +2,9 @@
 
 oracle/_ref/ref_{raymarching,shencoder,palette}.so are raymarching.cu, shencoder.cu and palette.cu of the reference, compiled unmodified for gfx950
 by the image's toolchain for CUDA extensions on ROCm (torch.utils.cpp_extension: hipify + hipcc; oracle/ref_build.py: build_hip), called through
-their own pybind modules with the argument lists of raymarching.h / shencoder.h / palette_func.h.  (gridencoder.cu does not compile for HIP --
-one atomicAdd(__half2*) overload is missing from ROCm 7.2 -- and stays pinned through the reference's Python wrapper over the oracle.)
+their own pybind modules with the argument lists of raymarching.h / shencoder.h / palette_func.h.  (The fourth extension, gridencoder.cu, is built
+by the same recipe -- with this repository's stand-in for the one atomicAdd(__half2*, __half2) overload the HIP headers lack, which only the fp16
+table gradient with an even feature count reaches -- and has a file of its own: tests/test_gpu_reference_grid.py.)
 
 What holds (measured, profiles/r04_reference_kernels.json), and is asserted here:
   bit for bit   morton3D / invert, packbits, near_far_from_aabb, march_rays_train (counter, per-ray counts, every position / direction / delta of
@@ -48,6 +49,9 @@ def window(cuda):
     aabb = torch.tensor([-2, -2, -2, 2, 2, 2], dtype=torch.float32, device=cuda)
     nears, fars = raymarching.near_far_from_aabb(ro, rd, aabb, 0.2)
     return ro, rd, nears, fars, bitfield, grid, aabb
+
+
+FRAME_ATOL = 1e-6      # images of one frame under the reference's kernels and under this repository's (also tests/test_gpu_reference_grid.py)
 
 
 def same_bits(a, b, what=""):
@@ -215,8 +219,8 @@ def test_sh_and_hsv_against_the_reference_kernels(cuda, ref):
 
 def test_frame_under_the_reference_kernels_equals_the_frame_under_ours(cuda, ref):
     """The per-op loop (this repository's mirror of run_cuda in compat mode) once over this repository's kernels and once with the reference's own
-    march / composite / SH kernels swapped in (the hash grid stays this repository's: gridencoder.cu is unbuildable for HIP): same samples, and
-    images that agree to 1e-6 -- the two kernel sets are interchangeable under the reference's control flow."""
+    march / composite / SH kernels swapped in (the hash grid stays this repository's here; tests/test_gpu_reference_grid.py swaps it as well):
+    same samples, and images that agree to 1e-6 -- the two kernel sets are interchangeable under the reference's control flow."""
     from oracle import ref_ops
     from palettenerf_amd import network
     H = W = 96
@@ -237,5 +241,5 @@ def test_frame_under_the_reference_kernels_equals_the_frame_under_ours(cuda, ref
     with ref_ops.swapped_in():
         theirs = frame()
     assert int(ours["rendered"].sum()) == int(theirs["rendered"].sum()) > 50_000
-    assert float((ours["image"] - theirs["image"]).abs().max()) <= 1e-6
+    assert float((ours["image"] - theirs["image"]).abs().max()) <= FRAME_ATOL
     assert torch.equal(ours["weights_sum"] > 0, theirs["weights_sum"] > 0)

@@ -398,6 +398,20 @@ def test_grid_reference_runs_of_equal_rows_cover_the_segmented_sum_cases():
     assert uni.B == 257 and (np.diff(uni.rows[4, 0]) != 0).mean() > 0.95
 
 
+@pytest.mark.parametrize("D,C,case,xname", [(3, 2, 0, "rays"), (2, 4, 5, "uniform"), (5, 1, 4, "rays")])
+def test_grid_reference_sparse_table_gradient_is_the_dense_one(D, C, case, xname):
+    """table_grad_sparse (what the GPU test of the shipped 6-million-row geometry uses) against the dense table_grad on variant cases -- a dense level,
+    a tiny hashed table, odd level sizes: the same rows, and the same float64 bits on them."""
+    ref = gr.variant_geometry(D, case, xname)
+    g = gr.variant_tables(D, C, case)[1][: ref.B]
+    gt, mag, n = ref.table_grad(g)
+    touched, s_gt, s_mag, s_n = ref.table_grad_sparse(g)
+    assert np.array_equal(touched, np.flatnonzero(n)) and len(touched) > 0
+    assert np.array_equal(s_n, n[touched]) and np.array_equal(s_gt, gt[touched]) and np.array_equal(s_mag, mag[touched])
+    for dense, assembled in zip((gt, mag, n), ref.table_grad_from_sparse(g)):
+        assert dense.dtype == assembled.dtype and np.array_equal(dense, assembled)
+
+
 # ------------------------------------------------------------------------------------------ march
 @pytest.fixture(scope="module")
 def s0():
