@@ -1288,7 +1288,8 @@ int pnr_mesh_vertex_records(const pnr_vertex_records_args* args, pnr_stream_t st
 
 /* ---- palette extraction, front end: histograms and k-means on the device (additive, ABI 10; csrc/extract.hip) ----
  * PaletteTrainer.extract_palette (palette/utils.py:1135-1200) into palette_extraction as far as run_kmeans' return (:167-226).  The hull
- * simplification and the weight LUT stay with the reference's CPU package; `centers` / `center_weights` below are exactly their input.
+ * simplification stays with the reference's CPU package; `centers` / `center_weights` below are exactly its input.  The weight LUT of the
+ * palette it returns is pnr_lut_weights, further down.
  *
  * pnr_extract_accumulate: ONE launch folds one rendered view of H x W pixels into both colour histograms.  Per pixel i (row-major):
  *   valid = weights_sum[i] > thresh            strict; a NaN is not valid (:1185)
@@ -1366,6 +1367,65 @@ typedef struct pnr_extract_kmeans_args {
 } pnr_extract_kmeans_args;
 uint64_t pnr_extract_kmeans_workspace_bytes(void);
 int pnr_extract_kmeans(const pnr_extract_kmeans_args* args, pnr_stream_t stream);
+
+/* ---- palette extraction, weight LUT: hull projection and barycentrics on the device (additive, ABI 10; csrc/lut.hip) ----
+ * What palette_extraction does after the hull simplification (palette/utils.py:235-245): the Tan-2016/2018 "ASAP" weights of the 32 768
+ * five-bit colour bins against the palette -- Get_ASAP_weights_using_Tan_2016_triangulation_and_then_barycentric_coordinates
+ * (rgbsg/fastLayerDecomposition/Additive_mixing_layers_extraction.py:397-547) -- the `hist_weights` table that initialize_palette, every
+ * training batch's weights_guide and the guide sheet read.  The hull simplification itself (the palette) stays with the reference's CPU package.
+ *
+ * pnr_lut_weights: the weights of N colours against a palette of M colours, PNR_LUT_MIN_M <= M <= PNR_LUT_MAX_M, ONE launch, float64:
+ *   order     the palette rows by L1 distance to black (|r| + |g|) + |b|, a tie to the lower row (:404-406): V[0] is the darkest row
+ *   hull      the faces are the triples i < j < k of V whose plane has every other row on one side by more than 1e-9, in ascending
+ *             (i, j, k), each with its unit normal pointing outwards; a row inside the hull belongs to no face and gets weight 0
+ *   project   a point is outside iff its signed distance to some face plane exceeds 1e-8 (the reference's find_simplex(tol=1e-8)); it is
+ *             replaced by the closest point of the hull surface: the nearest over the faces of the closest point on the triangle
+ *             (:426-437), a tie to the lower face (the closest point of a convex body is unique, so a tie does not change it)
+ *   star      for every face without V[0] the tetrahedron (V[0], Vi, Vj, Vk) (:463-486); the point takes its four barycentric
+ *             coordinates from the tetrahedron in which its smallest coordinate is largest, a tie to the lower face: on a shared face
+ *             both neighbours give the same weights, so this is the reference's "first tetrahedron that contains it" without the
+ *             dependence on qhull's face order.  All other columns are 0.
+ *   out       the columns in the caller's palette order (:541-543)
+ * points: PNR_LUT_POINTS_FP32 / _FP64: [N,3] on the device with point_stride elements between rows (>= 3: a frame's columns are read in
+ * place); PNR_LUT_POINTS_BINS: points NULL, N = 32 768, point n = ((code + 0.5) / 32 per channel, r most significant) of code n -- the
+ * fp32 bin centres of compute_RGB_histogram, exact -- nothing is uploaded.  normalize_input: every point becomes (c + 0.05) / |c + 0.05|
+ * in float64 first, the norm as sqrt((c0 c0 + c1 c1) + c2 c2) (palette/utils.py:237-240: --use_normalized_palette).
+ * weights64 [N,M] float64 and lut32 fp32 are both optional, one is required.  lut32 holds the float64 results rounded once, as [N,M] for
+ * an array of points and as element (k, ir, ig, ib) of [1,M,32,32,32] for PNR_LUT_POINTS_BINS: bit for bit what initialize_palette forms
+ * from the [32,32,32,M] float64 table.
+ * info [4]: the status, the hull's faces, its star tetrahedra, 0.  The palette is known on the device only, so its refusals are answered
+ * in info[0], not in the return value, and then NO weight is written:
+ *   PNR_LUT_FLAT      no triple has a row off its plane by more than 1e-9 (fewer than four non-coplanar rows): there is no hull
+ *   PNR_LUT_COPLANAR  a supporting plane carries a fourth row within 1e-9: the triangulation of that facet is a choice, and so are the
+ *                     weights (the reference's answer depends on qhull there) -- refused rather than picked
+ * Launch shape: min(1024, ceil(N / 128)) workgroups of 128 lanes, one point per lane, a workgroup walking contiguous runs of 128 points
+ * (pnr_launch_geometry("pnr_lut_weights", N)); every workgroup rebuilds the hull in LDS itself.  No atomics, every sum and minimum in a
+ * fixed order: two runs give the same bits, and a row's result does not depend on the batch it came in.
+ * Order of the checks, all before any launch: a NULL struct, palette or info, neither output, M outside 4..16 -> PNR_ERR_INVALID; an
+ * unknown points_format -> PNR_ERR_UNSUPPORTED; PNR_LUT_POINTS_BINS with points or N != 32 768, an array without points, with a stride
+ * below 3 or a base not aligned to its element, a misaligned palette or output -> PNR_ERR_INVALID. */
+#define PNR_LUT_MIN_M 4
+#define PNR_LUT_MAX_M 16
+#define PNR_LUT_MAX_FACES 28
+#define PNR_LUT_POINTS_BINS 0
+#define PNR_LUT_POINTS_FP32 1
+#define PNR_LUT_POINTS_FP64 2
+#define PNR_LUT_OK 0
+#define PNR_LUT_FLAT 1
+#define PNR_LUT_COPLANAR 2
+typedef struct pnr_lut_weights_args {
+    const double* palette;              /* [M,3] on the device, the caller's order */
+    uint32_t M;
+    const void* points;                 /* [N,3] with a row stride, or NULL (PNR_LUT_POINTS_BINS) */
+    int points_format;                  /* PNR_LUT_POINTS_* */
+    uint64_t point_stride;              /* elements between rows */
+    uint32_t N;
+    int normalize_input;
+    double* weights64;                  /* [N,M] out, optional */
+    float* lut32;                       /* [N,M], or [M,32,32,32] for the bins; out, optional */
+    int32_t* info;                      /* [4] out */
+} pnr_lut_weights_args;
+int pnr_lut_weights(const pnr_lut_weights_args* args, pnr_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,7 @@ SIGNATURES = {
     "pnr_extract_accumulate": [_ptr, _ptr],
     "pnr_extract_kmeans_workspace_bytes": [],
     "pnr_extract_kmeans": [_ptr, _ptr],
+    "pnr_lut_weights": [_ptr, _ptr],
 }
 _RESTYPES = {"pnr_frame_metrics_workspace_bytes": _u64, "pnr_mesh_workspace_bytes": _u64, "pnr_lattice_density_workspace_bytes": _u64, "pnr_occupancy_workspace_bytes": _u64, "pnr_occupancy_samples": _u32, "pnr_adam_max_tensors": _u32, "pnr_error_string": ctypes.c_char_p, "pnr_scan_scratch_bytes": _u64, "pnr_nerf_field_packed_bytes": _u64, "pnr_occupancy_mip_bytes": _u64, "pnr_nerf_frame_workspace_bytes": _u64, "pnr_palette_field_packed_bytes": _u64, "pnr_palette_frame_workspace_bytes": _u64,
              "pnr_palette_aux_channels": _u32, "pnr_linear_wgrad_workspace_bytes": _u64, "pnr_grid_backward_binned_workspace_bytes": _u64,
@@ -355,6 +356,17 @@ class ExtractKmeansArgs(ctypes.Structure):
     """Mirror of `pnr_extract_kmeans_args` (include/pnr.h)."""
     _fields_ = [("counts_coarse", _ptr), ("counts_fine", _ptr), ("total", _ptr), ("tau", ctypes.c_double), ("tol", ctypes.c_double), ("max_iter", _u32),
                 ("workspace", _ptr), ("workspace_bytes", _u64), ("centers", _ptr), ("center_weights", _ptr), ("info", _ptr), ("labels", _ptr)]
+
+
+LUT_MIN_M, LUT_MAX_M, LUT_MAX_FACES = 4, 16, 28                             # PNR_LUT_*
+LUT_POINTS_BINS, LUT_POINTS_FP32, LUT_POINTS_FP64 = 0, 1, 2
+LUT_OK, LUT_FLAT, LUT_COPLANAR = 0, 1, 2
+
+
+class LutWeightsArgs(ctypes.Structure):
+    """Mirror of `pnr_lut_weights_args` (include/pnr.h)."""
+    _fields_ = [("palette", _ptr), ("M", _u32), ("points", _ptr), ("points_format", _int), ("point_stride", _u64), ("N", _u32),
+                ("normalize_input", _int), ("weights64", _ptr), ("lut32", _ptr), ("info", _ptr)]
 
 
 _lib = None

@@ -10,7 +10,7 @@ extern "C" {
 int pnr_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip) {
     if (!entry || !workgroups || !rows_per_trip) return PNR_ERR_INVALID;
     for (auto unit : {heads_launch_geometry, smooth_launch_geometry, shade_launch_geometry, field_launch_geometry, mlp_launch_geometry, occupancy_launch_geometry,
-                      extract_launch_geometry})
+                      extract_launch_geometry, lut_launch_geometry})
         if (unit(entry, rows, workgroups, rows_per_trip) == PNR_OK) return PNR_OK;
     return PNR_ERR_INVALID;
 }

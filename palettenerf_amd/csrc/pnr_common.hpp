@@ -30,6 +30,7 @@ int field_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups
 int mlp_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);      // mlp.hip
 int occupancy_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);   // occupancy.hip
 int extract_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);     // extract.hip
+int lut_launch_geometry(const char* entry, uint64_t rows, uint32_t* workgroups, uint32_t* rows_per_trip);         // lut.hip
 
 // One process may drive several GPUs: function attributes and events belong to a device, so one-time set-up is tracked per device id.
 constexpr int kMaxDevices = 64;

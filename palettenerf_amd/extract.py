@@ -9,11 +9,17 @@ launch (`pnr_extract_kmeans`: float64, fixed summation order), and a few kilobyt
 
     res = extract.extract_centers(model, poses, intrinsics, H, W, trainset)            # or an image stack, host or device
     palette = Hull_Simplification_posternerf(res["centers"], prefix, pixel_counts=res["center_weights"], ...)      # the reference's rgbsg package
+    extract.initialize_from_extraction(palette_model, palette, normalize_input=True)   # the weight LUT: ONE launch, stays on the device
 
-The hull simplification and the weight LUT stay with the reference's CPU package.  The `extract-radiance-raw.png` debugging
-image of palette/utils.py:196-203 needs every sample on the host and is not produced.  `extract_centers_per_op` is the reference's own sequence,
-kept to measure and test against.  There is no fallback: on a CPU tensor or without the HIP library the device functions raise."""
+The hull simplification stays with the reference's CPU package; `load_palette` reads the palette it wrote.  The back end
+from the palette on is here: the weight LUT -- the Tan-2016/2018 "ASAP" weights of the 32 768 five-bit bins, palette/utils.py:235-245 -- is
+`weight_lut` (`pnr_lut_weights`: hull, projection and barycentrics in float64, one launch, nothing uploaded but the palette), and
+`palette_weights` is the same for any device array of colours.  `weight_lut_per_op` is the same statement in numpy on the host, kept to
+measure and test against.  The `extract-radiance-raw.png` debugging image of palette/utils.py:196-203 needs every sample on the host and is
+not produced.  `extract_centers_per_op` is the reference's own sequence, kept to measure and test against.  There is no fallback: on a CPU
+tensor or without the HIP library the device functions raise."""
 import ctypes
+import itertools
 
 import numpy as np
 import torch
@@ -362,3 +368,243 @@ def extract_centers_per_op(model, poses, intrinsics, H, W, images, linear=False,
     centers, cw = sort_centers(c, labels, w)
     info = {"K": init.shape[0], "P": X.shape[0], "iterations": int(n), "stop": stop, "emptied": False}
     return _result(centers, cw, info, coarse, fine, total)
+
+
+# ---------------------------------------------------------------- the weight LUT: hull projection and barycentrics (pnr_lut_weights)
+_LUT_STATUS_TEXT = {_lib.LUT_FLAT: "the palette has fewer than four non-coplanar colours: there is no hull",
+                    _lib.LUT_COPLANAR: "a face plane of the palette's hull carries a fourth colour within 1e-9: the triangulation of that "
+                                       "facet, and with it the weights, would be a choice"}
+_PLANE_EPS, _OUTSIDE_EPS = 1e-9, 1e-8
+
+
+def _palette_rows(palette):
+    p = np.asarray(palette.detach().cpu() if torch.is_tensor(palette) else palette, dtype=np.float64).reshape(-1, 3)
+    if not _lib.LUT_MIN_M <= p.shape[0] <= _lib.LUT_MAX_M:
+        raise ValueError(f"a palette of {_lib.LUT_MIN_M}..{_lib.LUT_MAX_M} colours is needed, got {p.shape[0]}")
+    return np.ascontiguousarray(p)
+
+
+def _launch_lut(palette, device, points, normalize_input, want64, want32):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("the palette weights need the HIP path (a CUDA/HIP device); there is no CPU fallback")
+    rows = _palette_rows(palette)
+    M = rows.shape[0]
+    pal = torch.from_numpy(rows).to(device)
+    a = _lib.LutWeightsArgs()
+    a.palette, a.M, a.normalize_input = pal.data_ptr(), M, int(bool(normalize_input))
+    if points is None:
+        N = _lib.EXTRACT_FINE_BINS
+        a.points, a.points_format, a.point_stride = None, _lib.LUT_POINTS_BINS, 3
+        shape32 = (1, M, 32, 32, 32)
+    else:
+        N = points.shape[0]
+        a.points, a.point_stride = points.data_ptr(), points.stride(0) if N > 1 else 3
+        a.points_format = _lib.LUT_POINTS_FP32 if points.dtype == torch.float32 else _lib.LUT_POINTS_FP64
+        shape32 = (N, M)
+    a.N = N
+    info = torch.zeros(4, dtype=torch.int32, device=device)
+    w64 = torch.empty(N, M, dtype=torch.float64, device=device) if want64 else None
+    w32 = torch.empty(shape32, dtype=torch.float32, device=device) if want32 else None
+    a.weights64 = None if w64 is None else w64.data_ptr()
+    a.lut32 = None if w32 is None else w32.data_ptr()
+    a.info = info.data_ptr()
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().pnr_lut_weights(ctypes.byref(a), stream_ptr()), "pnr_lut_weights")
+    status = int(info[0].item())
+    if status in _LUT_STATUS_TEXT:
+        raise RuntimeError(f"pnr_lut_weights: {_LUT_STATUS_TEXT[status]}")
+    return w64, w32
+
+
+def palette_weights(points, palette, out_dtype=torch.float64, normalize_input=False):
+    """The Tan-2016/2018 "ASAP" weights of `points` [...,3] (a float32 or float64 tensor on the device; a 2-D view with a row stride is read
+    in place) against `palette` [M,3], 4 <= M <= 16: [...,M] in out_dtype, float64 or float32 (the float64 result rounded once).  ONE launch.
+    normalize_input: every point becomes (c + 0.05) / |c + 0.05| first.  A flat palette or a hull with a coplanar fourth colour raises."""
+    if not torch.is_tensor(points) or not points.is_cuda or points.dtype not in (torch.float32, torch.float64) or points.shape[-1] != 3:
+        raise RuntimeError("palette_weights: points must be a float32 or float64 [...,3] tensor on the device; there is no CPU fallback")
+    if out_dtype not in (torch.float64, torch.float32):
+        raise ValueError("palette_weights: out_dtype is torch.float64 or torch.float32")
+    lead = points.shape[:-1]
+    p = points.detach()
+    if p.ndim != 2:
+        p = p.reshape(-1, 3)
+    if p.shape[0] > 1 and (p.stride(1) != 1 or p.stride(0) < 3):
+        p = p.contiguous()
+    elif p.shape[0] == 1 and p.stride(1) != 1:
+        p = p.contiguous()
+    if p.shape[0] >= 1 << 32:
+        raise ValueError("palette_weights: more than 2^32 - 1 points")
+    if p.shape[0] == 0:
+        return torch.empty(*lead, _palette_rows(palette).shape[0], dtype=out_dtype, device=p.device)
+    w64, w32 = _launch_lut(palette, p.device, p, normalize_input, out_dtype == torch.float64, out_dtype == torch.float32)
+    out = w64 if out_dtype == torch.float64 else w32
+    return out.reshape(*lead, out.shape[-1])
+
+
+def weight_lut(palette, normalize_input=False, device="cuda", return_weights64=False):
+    """The `hist_weights` table of palette/utils.py:235-245 as the model keeps it: float32 [1,M,32,32,32] on the device, the palette weights of the
+    32 768 five-bit bin centres (with normalize_input, of (c + 0.05) / |c + 0.05|: --use_normalized_palette).  ONE launch that generates the bin
+    centres itself; only the palette is uploaded and only the status word is read back.  return_weights64: also the float64 [32768,M] results
+    the table was rounded from."""
+    w64, w32 = _launch_lut(palette, device, None, normalize_input, bool(return_weights64), True)
+    return (w32, w64) if return_weights64 else w32
+
+
+def initialize_from_extraction(model, palette, normalize_input=False):
+    """main_palette.py:138-141 + :217 without the reference's hist_weights.npz: the LUT of `palette` on the model's device, handed to
+    model.initialize_palette in the layout the model keeps (no host round trip, no [32,32,32,M] numpy).  Returns the LUT."""
+    rows = _palette_rows(palette)
+    device = next(model.parameters()).device
+    lut = weight_lut(rows, normalize_input=normalize_input, device=device)
+    model.initialize_palette(rows, hist_lut=lut)
+    return lut
+
+
+def load_palette(path):
+    """The palette the reference's hull simplification wrote: `palette.npz` / `*-palette.npz` (key 'palette') or `*-palette.txt` (one colour a
+    line, three numbers: write_palette_txt, rgbsg/hull_simplification_posternerf.py:86-95).  Returns float64 [M,3]."""
+    if str(path).endswith(".npz"):
+        with np.load(path) as z:
+            p = np.asarray(z["palette"], dtype=np.float64)
+    else:
+        with open(path) as f:
+            p = np.array([[float(v) for v in line.split()] for line in f if line.strip()], dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] == 0:
+        raise ValueError(f"load_palette: {path} does not hold an [M,3] palette")
+    return p
+
+
+def lut_to_hist_weights(lut):
+    """[1,M,R,G,B] (the model's layout, tensor or array) -> the reference's host table [R,G,B,M] float64."""
+    a = lut.detach().cpu().numpy() if torch.is_tensor(lut) else np.asarray(lut)
+    if a.ndim != 5 or a.shape[0] != 1:
+        raise ValueError("lut_to_hist_weights: a [1,M,R,G,B] table is needed")
+    return np.ascontiguousarray(np.transpose(a[0], (1, 2, 3, 0))).astype(np.float64)
+
+
+def save_lut(path, lut):
+    """A LUT as the reference's `hist_weights.npz` (key 'hist_weights', [32,32,32,M] float64): main_palette.py:140 reads it as it reads its
+    own.  lut: weight_lut's [1,M,32,32,32] tensor, or a [32,32,32,M] host table."""
+    a = lut.detach().cpu().numpy() if torch.is_tensor(lut) else np.asarray(lut)
+    np.savez(path, hist_weights=lut_to_hist_weights(a) if a.ndim == 5 else a.astype(np.float64))
+
+
+def load_lut(path, device=None):
+    """`hist_weights.npz`, the reference's or save_lut's: the [32,32,32,M] float64 host table (initialize_palette's `hist_weights`), or with
+    `device` the float32 [1,M,32,32,32] tensor there (initialize_palette's `hist_lut`)."""
+    with np.load(path) as z:
+        hw = np.asarray(z["hist_weights"], dtype=np.float64)
+    if hw.ndim != 4:
+        raise ValueError(f"load_lut: {path} does not hold an [R,G,B,M] table")
+    if device is None:
+        return hw
+    return torch.as_tensor(hw).float().permute(3, 0, 1, 2).unsqueeze(0).contiguous().to(device)
+
+
+def _dot3(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _cross3(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def palette_hull(palette):
+    """The hull of pnr_lut_weights in numpy float64: (order [M], V [M,3] = palette[order], faces [F,3] ascending triples of V, normals [F,3]
+    unit and outward).  RuntimeError for a flat palette and for a coplanar fourth colour, with the device call's texts."""
+    P = _palette_rows(palette)
+    M = P.shape[0]
+    order = np.argsort((np.abs(P[:, 0]) + np.abs(P[:, 1])) + np.abs(P[:, 2]), kind="stable")
+    V = P[order]
+    faces, normals, nonflat, coplanar = [], [], False, False
+    for i, j, k in itertools.combinations(range(M), 3):
+        n = _cross3(V[j] - V[i], V[k] - V[i])
+        len2 = _dot3(n, n)
+        if not len2 > 0.0:
+            continue
+        n = n / np.sqrt(len2)
+        others = [l for l in range(M) if l not in (i, j, k)]
+        dist = _dot3(n[None], V[others] - V[i])
+        pos, neg = int((dist > _PLANE_EPS).sum()), int((dist < -_PLANE_EPS).sum())
+        near = len(others) - pos - neg
+        if pos + neg == 0:
+            continue
+        nonflat = True
+        if pos and neg:
+            continue
+        if near:
+            coplanar = True
+        else:
+            faces.append((i, j, k))
+            normals.append(-n if pos else n)
+    if not nonflat:
+        raise RuntimeError(f"palette_hull: {_LUT_STATUS_TEXT[_lib.LUT_FLAT]}")
+    if coplanar or len(faces) > _lib.LUT_MAX_FACES:
+        raise RuntimeError(f"palette_hull: {_LUT_STATUS_TEXT[_lib.LUT_COPLANAR]}")
+    if len(faces) < 4:
+        raise RuntimeError(f"palette_hull: {_LUT_STATUS_TEXT[_lib.LUT_FLAT]}")
+    return order, V, np.array(faces), np.array(normals)
+
+
+def _closest_on_triangles(p, a, ab, ac):
+    """closest point of the triangles (a, a + ab, a + ac) [F,3] to the points p [N,3] -> [N,F,3]: the Voronoi regions in the kernel's order"""
+    p = p[:, None, :]
+    ap, bp, cp = p - a, p - (a + ab), p - (a + ac)
+    d1, d2, d3, d4, d5, d6 = _dot3(ab, ap), _dot3(ac, ap), _dot3(ab, bp), _dot3(ac, bp), _dot3(ab, cp), _dot3(ac, cp)
+    vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+    with np.errstate(divide="ignore", invalid="ignore"):
+        total = (va + vb) + vc
+        v, w = vb / total, vc / total                                                        # the inside, unless a region below claims the point
+        wbc = (d4 - d3) / ((d4 - d3) + (d5 - d6))
+        regions = [((va <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0), 1.0 - wbc, wbc),            # (the last rule first: an earlier one overwrites it)
+                   ((vb <= 0) & (d2 >= 0) & (d6 <= 0), 0.0, d2 / (d2 - d6)),
+                   ((d6 >= 0) & (d5 <= d6), 0.0, 1.0),
+                   ((vc <= 0) & (d1 >= 0) & (d3 <= 0), d1 / (d1 - d3), 0.0),
+                   ((d3 >= 0) & (d4 <= d3), 1.0, 0.0),
+                   ((d1 <= 0) & (d2 <= 0), 0.0, 0.0)]
+        for mask, rv, rw in regions:
+            v, w = np.where(mask, rv, v), np.where(mask, rw, w)
+    return a + (v[..., None] * ab + w[..., None] * ac)
+
+
+def palette_weights_per_op(points, palette, normalize_input=False, return_info=False):
+    """pnr_lut_weights' statement in numpy float64 on the host, operation for operation (the hull by brute force, the closest point on every
+    triangle, the star tetrahedra's inverse edge matrices): what the device call is measured and tested against.  points [N,3] -> [N,M];
+    with return_info also {"outside": [N] bool, "projected": [N,3], "faces", "order"}."""
+    order, V, faces, normals = palette_hull(palette)
+    x = np.array(points, dtype=np.float64).reshape(-1, 3)
+    if normalize_input:
+        x = x + 0.05
+        x = x / np.sqrt(_dot3(x, x))[:, None]
+    a, ab, ac = V[faces[:, 0]], V[faces[:, 1]] - V[faces[:, 0]], V[faces[:, 2]] - V[faces[:, 0]]
+    outside = (_dot3(normals, x[:, None, :] - a) > _OUTSIDE_EPS).any(axis=1)
+    if outside.any():
+        xo = x[outside]
+        c = _closest_on_triangles(xo, a, ab, ac)
+        e = xo[:, None, :] - c
+        x[outside] = c[np.arange(xo.shape[0]), np.argmin(_dot3(e, e), axis=1)]           # argmin: the first of equal minima, the lower face
+    star = faces[faces[:, 0] != 0]
+    cols = [V[star[:, m]] - V[0] for m in range(3)]                                      # [T,3] each: the columns of the edge matrices
+    rows = [_cross3(cols[(m + 1) % 3], cols[(m + 2) % 3]) for m in range(3)]
+    det = _dot3(cols[0], rows[0])
+    y = (x - V[0])[:, None, :]
+    b = [_dot3(rows[m] / det[:, None], y) for m in range(3)]                             # [N,T] each
+    b0 = 1.0 - ((b[0] + b[1]) + b[2])
+    best = np.argmax(np.minimum(np.minimum(b0, b[0]), np.minimum(b[1], b[2])), axis=1)   # argmax: the first of equal maxima
+    n = np.arange(x.shape[0])
+    W = np.zeros((x.shape[0], V.shape[0]), dtype=np.float64)
+    W[n, order[0]] = b0[n, best]
+    for m in range(3):
+        W[n, order[star[best, m]]] = b[m][n, best]
+    if return_info:
+        return W, {"outside": outside, "projected": x, "faces": faces, "order": order}
+    return W
+
+
+def weight_lut_per_op(palette, normalize_input=False):
+    """The reference's hist_weights table [32,32,32,M] float64 (palette/utils.py:235-245) by palette_weights_per_op: the host leg the device's
+    weight_lut is measured and tested against.  The reference's own loop needs scipy, cvxopt and a Cython module; this needs numpy."""
+    W = palette_weights_per_op(bin_centers_of(5).astype(np.float64), palette, normalize_input=normalize_input)
+    return W.reshape(32, 32, 32, W.shape[1])

@@ -803,9 +803,10 @@ class PaletteRenderer(_RendererBase):
         else:
             self.basis_color = None
 
-    def initialize_palette(self, color_list=None, hist_weights=None):
+    def initialize_palette(self, color_list=None, hist_weights=None, hist_lut=None):
         """palette/renderer.py:247-268; with --color_space linear the extracted (sRGB) palette is moved to linear colour first (:256-259,
-        srgb_to_linear of nerf/utils.py:39-40)."""
+        srgb_to_linear of nerf/utils.py:39-40).  hist_weights: the reference's [R,G,B,nb] host table.  hist_lut: the same table as the model
+        keeps it, a float32 [1,nb,R,G,B] tensor (extract.weight_lut), taken as it is: no host round trip, no permuted view."""
         if color_list is None:
             if self.basis_color is None:
                 self.basis_color = nn.Parameter(torch.zeros([self.num_basis, 3]) + 0.5, requires_grad=True)
@@ -821,6 +822,12 @@ class PaletteRenderer(_RendererBase):
         if hist_weights is not None:
             hw = torch.as_tensor(hist_weights).float().permute(3, 0, 1, 2).unsqueeze(0)
             self.hist_weights = nn.Parameter(hw, requires_grad=False)
+        if hist_lut is not None:
+            if hist_weights is not None:
+                raise ValueError("initialize_palette: give hist_weights or hist_lut, not both")
+            if not torch.is_tensor(hist_lut) or hist_lut.dtype != torch.float32 or hist_lut.ndim != 5 or hist_lut.shape[:2] != (1, self.num_basis):
+                raise ValueError(f"initialize_palette: hist_lut must be a float32 [1,{self.num_basis},R,G,B] tensor")
+            self.hist_weights = nn.Parameter(hist_lut.detach().to(self.aabb_train.device), requires_grad=False)
 
     def forward(self, x, d):
         raise NotImplementedError()
