@@ -32,7 +32,8 @@ extern "C" {
 #define PNR_ERR_INVALID (-1)      /* null pointer / bad size                                  */
 #define PNR_ERR_UNSUPPORTED (-2)  /* C not in {1,2,4,8}, D not in 1..5, n_channel > 128, ...  */
 #define PNR_ERR_LAUNCH (-3)       /* hipGetLastError() != hipSuccess after a launch           */
-#define PNR_ERR_ALIGNMENT (-4)    /* pnr_mlp_*: an activation array that does not start on a 16-byte boundary or holds fewer than four floats */
+#define PNR_ERR_ALIGNMENT (-4)    /* pnr_mlp_*: an activation array that does not start on a 16-byte boundary or holds fewer than four floats;
+                                     elsewhere: an array off the boundary its entry's comment names */
 
 #define PNR_DTYPE_F32 0
 #define PNR_DTYPE_F16 1
@@ -272,7 +273,10 @@ int pnr_compact_alive(uint32_t n_alive, const int32_t* rays_alive_in, int32_t* r
 
 /* replaces grid_encode_forward, gridencoder/src/gridencoder.h:12, gridencoder.cu:424-447.
  * dtype selects the table/outputs/dy_dx element type (PNR_DTYPE_F32 / PNR_DTYPE_F16).
- * outputs is [L,B,C] as in the reference; dy_dx may be NULL. offsets: device int32[L+1]. */
+ * outputs is [L,B,C] as in the reference; dy_dx may be NULL. offsets: device int32[L+1].
+ * fp16 arrays (dtype PNR_DTYPE_F16: the table, outputs, dy_dx; in pnr_grid_encode_backward grad, grad_embeddings, dy_dx, grad_inputs) start on a 4-byte
+ * boundary -- they move as pairs of halves, the table gradient as one 4-byte atomic per pair -- else PNR_ERR_ALIGNMENT, before anything is launched.
+ * fp32 arrays need their element's alignment only. */
 int pnr_grid_encode_forward(const float* inputs, const void* embeddings, const int32_t* offsets, void* outputs,
                             uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, void* dy_dx,
                             uint32_t gridtype, int align_corners, int dtype, pnr_stream_t stream);
@@ -586,6 +590,8 @@ int pnr_linear_wgrad(const void* x, int x_dtype, const void* dy, int dy_dtype, u
  *   pnr_mlp_backward  x, dy [B, dims[n_layers]] -> dx [B, dims[0]] (NULL: not wanted), dw_l [dims[l+1]][dims[l]] (NULL: not wanted);
  *                     hidden activations are recomputed from x; dw is reduced deterministically through `workspace`.
  *                     y: the forward's output, read only with PNR_MLP_OUT_SIGMOID (dZ = dY (1 - y) y; NULL otherwise).
+ *   A row-major activation array is at least two columns wide: dims[0] == 1 (plain forms), dims[n_layers] == 1 and a one-column x_tail (dims[0] == 33 in the
+ *   level-major forms) are PNR_ERR_UNSUPPORTED -- the tile moves divide element indices by the width with a 32-bit reciprocal, which width 1 does not have.
  *   Every activation array (x, x_tail, y, dy, dx; the level-major forms' enc / denc) must start on a 16-byte boundary and hold at least four floats -- tiles move
  *   as 16-byte requests (round 5); PNR_ERR_ALIGNMENT otherwise (a contiguous view such as x[1:] of a 3-wide tensor starts inside an allocation: copy it). */
 typedef struct {
@@ -873,7 +879,9 @@ int pnr_rgb_histogram(const float* colors_rgb, const float* weights, uint32_t n,
  * Supported: num_levels = 4, level_dim = 2, sh_degree = 4, num_layers = 2, hidden_dim = 64 (the reference's only background architecture);
  * anything else is PNR_ERR_UNSUPPORTED, before anything is launched.  A null struct or a missing pointer is PNR_ERR_INVALID; N = 0 is PNR_OK.
  *   pnr_background_pack: bg_net.0.weight [64, 24] and bg_net.1.weight [3, 64] (row-major [out][in], device fp32) -> `packed`
- *                        (pnr_background_packed_bytes() bytes, 16-byte aligned); call again when either weight changes. */
+ *                        (pnr_background_packed_bytes() bytes, 16-byte aligned); call again when either weight changes.
+ * Alignment: coords_in / coords_out start on an 8-byte boundary (float2 accesses), the table on 8 bytes (fp32) or 4 (fp16), `packed` on 16; PNR_ERR_ALIGNMENT
+ * otherwise, before anything is launched. */
 typedef struct pnr_background_args {
     uint32_t N;
     const float* rays_o;           /* [N,3]; not read with coords_in */

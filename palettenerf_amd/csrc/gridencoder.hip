@@ -8,6 +8,7 @@
 // HBM layout: table [sum_l T_l, C] row-major (fp32 or fp16), offsets int32[L+1], inputs [B,D] fp32
 // in [0,1], outputs [L,B,C] (level-major: a block column works on ONE level so that level's
 // <= 4 MiB table stays resident in the XCD L2s while the samples stream through).
+#include <initializer_list>
 #include "pnr_common.hpp"
 #include "grid_core.hpp"
 #include <type_traits>
@@ -513,6 +514,13 @@ int pnr_grid_encode_forward_pair(const float* inputs, const float* pair_embeddin
     return check_launch();
 }
 
+// fp16 arrays move as pairs of halves -- the table gradient adds a __half2 with one 4-byte atomic, the lookups load and store pairs -- so every fp16 array of
+// these entries starts on a 4-byte boundary (torch allocations do; a view that starts on an odd half does not): refused before anything is launched.
+static bool halves_on_pairs(std::initializer_list<const void*> ptrs) {
+    for (const void* q : ptrs) if (q && (reinterpret_cast<uintptr_t>(q) & 3u) != 0) return false;
+    return true;
+}
+
 int pnr_grid_encode_forward(const float* inputs, const void* embeddings, const int32_t* offsets, void* outputs, uint32_t B, uint32_t D,
                             uint32_t C, uint32_t L, float S, uint32_t H, void* dy_dx, uint32_t gridtype, int align_corners, int dtype,
                             pnr_stream_t stream) {
@@ -527,6 +535,7 @@ int pnr_grid_encode_forward_layout(const float* inputs, const void* embeddings, 
     if (dtype != PNR_DTYPE_F32 && dtype != PNR_DTYPE_F16) return PNR_ERR_UNSUPPORTED;
     if (B == 0) return PNR_OK;
     if (!inputs || !embeddings || !offsets || !outputs) return PNR_ERR_INVALID;
+    if (dtype == PNR_DTYPE_F16 && !halves_on_pairs({embeddings, outputs, dy_dx})) return PNR_ERR_ALIGNMENT;
     const LevelParams lp = make_level_params(L, S, H);
     if (dtype == PNR_DTYPE_F32)
         return launch_fwd<float>(inputs, static_cast<const float*>(embeddings), offsets, static_cast<float*>(outputs), B, D, C, L, lp,
@@ -546,6 +555,7 @@ int pnr_grid_encode_backward(const void* grad, const float* inputs, const void* 
     if (B == 0) return PNR_OK;
     if (!grad || !inputs || !offsets || !grad_embeddings) return PNR_ERR_INVALID;
     if ((dy_dx == nullptr) != (grad_inputs == nullptr)) return PNR_ERR_INVALID;
+    if (dtype == PNR_DTYPE_F16 && !halves_on_pairs({grad, grad_embeddings, dy_dx, grad_inputs})) return PNR_ERR_ALIGNMENT;
     const LevelParams lp = make_level_params(L, S, H);
     const auto impl = dtype == PNR_DTYPE_F32 ? encode_backward<float> : encode_backward<__half>;
     return impl(grad, inputs, offsets, grad_embeddings, B, D, C, L, lp, dy_dx, grad_inputs, gridtype, align_corners != 0, as_stream(stream));

@@ -1107,8 +1107,12 @@ static bool arrays_ok(std::initializer_list<const void*> ptrs, uint32_t B, const
 }
 
 static int plan_sources(MlpPlan& p, uint32_t lm_levels, const float* x_tail) {
+    // A row-major activation array of width 1 has no magic: floor(2^32 / 1) + 1 does not fit 32 bits (it wraps to 1, every element would be staged into row 0).
+    // No stack of either field has a one-column end; such a stack is refused, not computed wrongly.
+    if (p.dims[p.n_layers] == 1 || (lm_levels == 0 && p.dims[0] == 1)) return PNR_ERR_UNSUPPORTED;
     if (lm_levels == 0) return PNR_OK;
     if (lm_levels != 16 || p.dims[0] < 32) return PNR_ERR_UNSUPPORTED;
+    if (p.dims[0] == 33) return PNR_ERR_UNSUPPORTED;      // a one-column x_tail: likewise
     p.lm = 1;
     p.tail = p.dims[0] - 32;
     if (p.tail && !x_tail) return PNR_ERR_INVALID;
@@ -1152,14 +1156,14 @@ static int mlp_backward_impl(const pnr_mlp_desc* desc, const float* packed, cons
                              uint32_t B, float* dx, float* dw0, float* dw1, float* dw2, void* workspace, uint64_t workspace_bytes, pnr_stream_t stream) {
     MlpPlan p;
     if (!make_plan(desc, p)) return PNR_ERR_UNSUPPORTED;
-    if (int rc = plan_sources(p, lm_levels, x_tail)) return rc;
     hipStream_t s = as_stream(stream);
     MlpGrads gr{{dw0, dw1, dw2}};
-    if (B == 0) {
+    if (B == 0) {      // an empty batch is answered before the sources are looked at, as in the forward
         for (uint32_t l = 0; l < p.n_layers; l++)
             if (gr.dw[l] && hipMemsetAsync(gr.dw[l], 0, (size_t)p.dims[l] * p.dims[l + 1] * 4, s) != hipSuccess) return PNR_ERR_LAUNCH;
         return PNR_OK;
     }
+    if (int rc = plan_sources(p, lm_levels, x_tail)) return rc;
     if (!packed || !x || !dy || !workspace || (p.out_act && !y)) return PNR_ERR_INVALID;
     if (!p.out_act) y = nullptr;
     if ((uint64_t)B * 64 >= (1ull << 32)) return PNR_ERR_UNSUPPORTED;   // element indices are 32-bit

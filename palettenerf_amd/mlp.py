@@ -83,8 +83,8 @@ def fusable(net, h, act):
     if act not in _ACT or len(net) not in (2, 3) or not MIN_ROWS <= h.numel() // h.shape[-1] < 2 ** 26:
         return False
     dims = [net[0].in_features] + [l.out_features for l in net]
-    if max(dims) > 64 or any(l.bias is not None or l.weight.dtype != torch.float32 for l in net):
-        return False
+    if max(dims) > 64 or min(dims[0], dims[-1]) < 2 or any(l.bias is not None or l.weight.dtype != torch.float32 for l in net):
+        return False      # (a one-column end is refused by the launches: pnr_mlp_* in include/pnr.h)
     tiles = [(d + 31) // 32 if i in (0, len(dims) - 1) else 2 for i, d in enumerate(dims)]
     packed = 2 * sum(tiles[i] * tiles[i + 1] for i in range(len(dims) - 1)) * 1024
     if (packed + 8 * 32 * 65) * 4 > 160 * 1024:      # weights (both orientations) + the backward's staging tiles must fit one CU's LDS
@@ -184,7 +184,7 @@ def encode_mlp_fused_ok(encoder, x, tail, net, act=F.relu):
           and hasattr(encoder, "embeddings") and encoder.embeddings.dtype == torch.float32 and x.numel() // 3 >= max(MIN_ROWS, BINNED_MIN_ROWS)
           and x.numel() // 3 * 16 * 8 < 2 ** 32)
     if ok:
-        ok = net[0].in_features == 32 + (0 if tail is None else tail.shape[-1]) and fusable(net, _Rows(x.numel() // 3, net[0].in_features, x), act)
+        ok = net[0].in_features == 32 + (0 if tail is None else tail.shape[-1]) and net[0].in_features != 33 and fusable(net, _Rows(x.numel() // 3, net[0].in_features, x), act)
     return bool(ok)
 
 
