@@ -1,9 +1,11 @@
 """MI355X-first fused evaluation of the fields (no reference counterpart as one call): level-major
 hash-grid lookup feeding the MFMA tiny-MLP kernel directly, no permute/copy, no per-layer launches."""
+import contextlib
 import ctypes
 import math
 import os
 import threading
+import warnings
 
 import numpy as np
 import torch
@@ -71,7 +73,6 @@ class _PairCopy:
             if self.sum_ref[i] is None:
                 self.sum_ref[i] = now[i]
             elif self.sum_ref[i] != now[i]:
-                import warnings
                 warnings.warn("pair lookup: a hash table was rewritten behind torch's version counters (a `.data` write) -- the interleaved copy "
                               "was stale for one call; call invalidate_fused_caches(model) after such writes")
                 self.keys[i] = None
@@ -115,9 +116,11 @@ def grid_encode_raw_pair(enc_a, enc_b, x01):
         enc_a.__dict__["_pnr_pair"] = hit      # (__dict__: a plain attribute, not a registered buffer -- it must stay out of state_dict)
     hit.lagged_check()
     hit.refresh((ea, eb))
-    pair = hit.table
-    B = x01.shape[0]
-    L = enc_a.num_levels
+    return _encode_pair(enc_a, hit.table, x01)
+
+
+def _encode_pair(enc_a, pair, x01):     # pnr_grid_encode_forward_pair over an interleaved [rows][2][2] fp32 table of two encoders of enc_a's geometry -> two raw [L,B,2] outputs
+    B, L = x01.shape[0], enc_a.num_levels
     out0 = torch.empty(L, B, 2, device=x01.device, dtype=torch.float32)
     out1 = torch.empty(L, B, 2, device=x01.device, dtype=torch.float32)
     call("pnr_grid_encode_forward_pair", ptr(require(x01, torch.float32, "inputs")), ptr(pair), ptr(enc_a.offsets), ptr(out0), ptr(out1), _u32(B), _u32(L),
@@ -196,15 +199,79 @@ def invalidate_fused_caches(model):
             invalidate_fused_caches(twin)
 
 
-def _half_copy(owner, attr, t):
-    """fp16 copy of a table, cached on `owner` until the table changes (identity / data pointer / version)."""
-    key = _pkey(t)
-    cached = getattr(owner, attr, None)
-    if cached is None or cached[0] != key or PARANOID:
-        cached = (key, t.to(torch.float16).contiguous())
-        setattr(owner, attr, cached)
-    return cached[1]
+class _Derived:
+    """Everything a fused object derives from parameters and settings (packed weight blobs, half / interleaved tables, the guard's bounds, the edit struct, the
+    frame call's kept argument struct, the checksum call's argument arrays): slot -> (key, value).  THE RULES, stated here once:
+      * a value is valid while its key is unchanged: the _pkey of every source (identity, storage, version), the settings it was built for and, where the
+        sources' keys do not already say so, the device;
+      * a rebuild is a NEW object.  The cache never writes into a value it has handed out: a prepared or submitted frame holds the old one (its token keeps it);
+      * PNR_PARANOID_CACHE=1 rebuilds on every use (get() is the only place that reads PARANOID for one of these slots);
+      * invalidate_caches() of the owner clears every slot; a frame that finds sources moved drops the slots derived from THEM (_SourceWatch._watch_begin).
+        Both bump `_gen`, by which a frame prepared earlier is recognised (StaleFrame);
+      * a copy or a pickle of the owner carries no values along and rebuilds its own (as _PairCopy)."""
+    def __init__(self):
+        self._slots = {}
 
+    def get(self, slot, key, build, *args):
+        """The stored value of `slot` while its key is `key`, else build(*args), a NEW object (a function and its arguments, not a closure: most calls are hits)."""
+        hit = self._slots.get(slot)
+        if hit is None or hit[0] != key or PARANOID:
+            hit = self._slots[slot] = (key, build(*args))
+        return hit[1]
+
+    def key(self, slot):
+        return self._slots.get(slot, (None, None))[0]
+
+    def peek(self, slot):
+        return self._slots.get(slot, (None, None))[1]
+
+    def slots(self):
+        return list(self._slots)
+
+    def clear(self):
+        self._slots = {}
+
+    def drop(self, pkeys):     # forget every slot whose key holds one of these source keys, at any depth
+        holds = lambda k: k in pkeys or (type(k) is tuple and any(holds(x) for x in k))
+        self._slots = {s: kv for s, kv in self._slots.items() if not holds(kv[0])}
+
+    def __deepcopy__(self, memo):
+        return _Derived()
+
+    def __reduce__(self):
+        return (_Derived, ())
+
+
+class _FusedState:
+    """The fused objects' state, declared in one place (the mixins below have no constructor): every constructor calls _init_state().  `_cache`: see _Derived."""
+
+    def _init_state(self):
+        self._cache = _Derived()
+        self._gen = 0                 # invalidations and precision changes so far: frames prepared before the last one are refused (StaleFrame)
+        self._slot = 1                # the argument struct / read-back row of the frame prepared last (two alternate)
+        self._handed = None           # the slot of the blob handed out last (`packed` / `versions`)
+        self._overflowed_key = None   # the guard key of the weights that left fp16's range under the watch
+        self._watch_keys = self._watch_ref = None     # _SourceWatch: the sources' keys at the last frame; (keys, checksums) of the reference
+        self._watch_dev = self._watch_host = self._watch_rows = None     # its read-back buffers and their two rows
+        self._guard_hold = False      # _PrecisionGuard._held: inside a held call, and the answers held for it
+        self._guard_held = self._weights_held = None
+        self._ws = None               # the frame call's workspace
+        self.ray_order = None         # setting: a permutation of the rays (tile_ray_order)
+        self.time_grid_kernel = False  # bench.py: HIP-event timing of the grid-encode launches inside the native frame loop
+
+    packed = property(lambda self: self._cache.peek(self._handed), doc="the weight blob handed out last (None after an invalidation)")
+    versions = property(lambda self: self._cache.key(self._handed), doc="its key: (device, the _pkey of every source, precision)")
+
+    def invalidate_caches(self):
+        self._cache.clear()
+        self._watch_ref = None       # the next frame rebuilds every blob: its source checksums become the reference
+        self._guard_held = self._weights_held = None   # (a held call that retries asks again)
+        self._gen += 1               # frames prepared before this point hold pointers into the old blobs (frame_launch refuses them)
+
+    _to_half = staticmethod(lambda t: t.to(torch.float16).contiguous())
+
+    def _half_table(self, t):     # the reference's `embeddings.to(torch.half)` per forward (gridencoder/grid.py:38), converted once per update here
+        return self._cache.get("half_table", _pkey(t), self._to_half, t)
 
 
 F16X3_SAFE_ACTIVATION = 3.0e4   # fp16 overflows at 65 504: above this bound on any split operand the field runs on the exact fp32 path
@@ -239,60 +306,61 @@ class _PrecisionGuard:
     def _guard_weights(self):
         return self._w()
 
+    def _blob_sources(self):     # the tensors the packed blob is derived from: the weights that run, and what a field packs next to them
+        return self._guard_weights()
+
     def _guard_bound(self, tmax, scales):
         raise NotImplementedError
 
+    @contextlib.contextmanager
     def _held(self):
         """Context manager for one call of the stand-alone ops: the guard is evaluated once and its answer held until the call returns (effective_precision,
         enc_scales and _pack each ask; every answer walks the model's parameters -- 36 % of the host time of a drop-in frame with dropin.fuse_field)."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def hold():
-            self._guard_hold = True
-            outer = getattr(_held_keys, "memo", None)
+        self._guard_hold = True
+        outer = getattr(_held_keys, "memo", None)     # (a thread-local: absent in a thread's first call)
+        if outer is None:
+            _held_keys.memo = {}
+        try:
+            yield
+        finally:
+            self._guard_hold = False
+            self._guard_held = self._weights_held = None
             if outer is None:
-                _held_keys.memo = {}
-            try:
-                yield
-            finally:
-                self._guard_hold = False
-                self._guard_held = None
-                self._weights_held = None
-                if outer is None:
-                    _held_keys.memo = None
-        return hold()
+                _held_keys.memo = None
 
     def _w(self):
         """self._weights(), looked up once per held call (a dozen nn.Module attribute walks, asked for by the guard, the packer and the source watch)."""
-        held = self.__dict__.get("_weights_held")
-        if held is not None:
-            return held
+        if self._weights_held is not None:
+            return self._weights_held
         ws = self._weights()
-        if self.__dict__.get("_guard_hold"):
+        if self._guard_hold:
             self._weights_held = ws
         return ws
 
-    def _guard(self):
-        held = self.__dict__.get("_guard_held")
-        if held is not None:
-            return held
-        state = self._guard_now()
-        if self.__dict__.get("_guard_hold"):
+    def _guard(self):     # -> (enc scales, static bound, largest |weight|): the "guard" slot, keyed on the weights and tables it is computed from
+        if self._guard_held is not None:
+            return self._guard_held
+        tables = self._guard_tables()
+        key = tuple(_pkey(w) for w in self._guard_weights()) + tuple(_pkey(t) for t in tables)
+        state = self._cache.get("guard", key, self._guard_build, tables)
+        if self._guard_hold:
             self._guard_held = state
         return state
 
-    def _guard_now(self):
-        tables = self._guard_tables()
-        key = tuple(_pkey(w) for w in self._guard_weights()) + tuple(_pkey(t) for t in tables)
-        if getattr(self, "_guard_key", None) != key or PARANOID:
-            tmax = [float(v) for v in torch.stack([t.detach().abs().max().float() for t in tables]).cpu().tolist()]
-            scales = [_prescale_of(v) for v in tmax]
-            bound = float(self._guard_bound(tmax, scales))
-            wmax = float(torch.stack([w.detach().abs().max().float() for w in self._guard_weights()]).max())   # the weights are split into fp16 halves too
-            self._guard_state = (scales + [1.0] * (3 - len(scales)), bound, wmax)
-            self._guard_key = key
-        return self._guard_state
+    def _guard_build(self, tables):
+        tmax = [float(v) for v in torch.stack([t.detach().abs().max().float() for t in tables]).cpu().tolist()]
+        scales = [_prescale_of(v) for v in tmax]
+        bound = float(self._guard_bound(tmax, scales))
+        wmax = float(torch.stack([w.detach().abs().max().float() for w in self._guard_weights()]).max())   # the weights are split into fp16 halves too
+        return (scales + [1.0] * (3 - len(scales)), bound, wmax)
+
+    def _pack(self, prec=None):
+        """The MFMA-ordered weight blob for `prec`, slot ("blob", prec): one blob per precision (the stand-alone ops may run fp32 where the frame loops run
+        split-fp16 with the watch, and a frame prepared or in flight at one precision must never see the other's layout); _pack_build(prec) packs a new one."""
+        prec = self.effective_precision() if prec is None else prec
+        srcs = self._blob_sources()
+        self._handed = slot = ("blob", prec)
+        return self._cache.get(slot, (srcs[0].device,) + tuple(_pkey(t) for t in srcs) + (prec,), self._pack_build, prec)
 
     def enc_scales(self, prec=None):
         """[s_encoder, s_encoder_palette, s_encoder_clip] for the split-fp16 path (all 1.0 on the fp32 path)."""
@@ -318,16 +386,13 @@ class _PrecisionGuard:
             return 0, False
         if self._guard()[1] < F16X3_SAFE_ACTIVATION:
             return self._fp16_level(), False
-        if getattr(self, "_overflowed_key", None) == self._guard_key:
+        if self._overflowed_key is not None and self._overflowed_key == self._cache.key("guard"):
             return 0, False
         return self._fp16_level(), True
 
     def _note_overflow(self):
-        import warnings
-        self._overflowed_key = self._guard_key
-        # frames prepared before this point carry the split-fp16 precision and watch in their argument structs: frame_launch refuses them (StaleFrame) and
-        # render_launch prepares them again, on the exact fp32 path
-        self._gen = self.__dict__.get("_gen", 0) + 1
+        self._overflowed_key = self._cache.key("guard")
+        self._gen += 1     # frames prepared before this point carry split-fp16 and the watch in their structs: frame_launch refuses them (StaleFrame), render_launch prepares them again
         warnings.warn("fused field: an activation left fp16's range (> 65504) in the split-fp16 matrix path: the frame is rendered again on the exact "
                       "fp32 path, which these weights keep from now on")
 
@@ -335,13 +400,19 @@ class _PrecisionGuard:
 TABLE_CHECK_STRIDE = 1 if PARANOID else 1021   # hash tables are checksummed on every 1021st word per frame (12 k scattered words of a 50 MB table: ~3 us; every 61st cost 18 us); weights in full
 
 
+def _checksum_args(srcs):     # pnr_checksum's three argument arrays for [(tensor, stride in 4-byte words)]
+    return ((ctypes.c_void_p * len(srcs))(*[t.data_ptr() for t, _ in srcs]), (ctypes.c_uint64 * len(srcs))(*[t.numel() * t.element_size() for t, _ in srcs]),
+            (_u32 * len(srcs))(*[int(st) for _, st in srcs]))
+
+
 class _SourceWatch:
     """Blobs derived from parameters go stale SILENTLY when the parameters are rewritten through `.data` (torch_ema's copy_to / restore around
     an evaluation, nerf/utils.py:829-839, 959-961): neither identity nor version moves, so the keys above cannot tell.  The frame loops
     therefore checksum the sources on the device once per frame (pnr_checksum: one small launch, 8 bytes per source back with the frame's own
     read-back) and compare with the checksums taken when the blobs were built; on a mismatch the blobs are rebuilt and the frame is rendered
-    again.  When torch CAN tell (a key changed) every blob of the object is rebuilt in that frame and its checksums become the reference, so a
-    `.data` write can never hide behind an unrelated version bump.  Tables are sampled (TABLE_CHECK_STRIDE): a swap or a re-initialisation
+    again.  When torch CAN tell (a key changed), what derives from the sources that moved is rebuilt in that frame -- also what was built since the
+    move -- and only THEIR checksums become the new reference: the other sources are still compared, so a `.data` write cannot hide behind another
+    source's version bump (it gives the warning and the second render).  Tables are sampled (TABLE_CHECK_STRIDE): a swap or a re-initialisation
     touches every row and is caught.  LIMITATION: a `.data` write that touches only PART of a table (loading or pruning some levels, a partial
     re-initialisation) will usually miss the sampled words and is NOT detected -- call invalidate_fused_caches(model) after such a write, or
     run with PNR_PARANOID_CACHE=1, which checks every word."""
@@ -354,37 +425,41 @@ class _SourceWatch:
         """slot: 0 / 1 -- a frame prepared while the previous one is still running (frame_prepare / frame_launch / frame_finish) takes the other read-back row."""
         srcs = self._watched()
         keys = tuple(_pkey(t) for t, _ in srcs)
-        had = getattr(self, "_watch_keys", None)
-        record = had != keys or getattr(self, "_watch_ref", None) is None
-        if had is not None and had != keys:
-            self.invalidate_caches()
+        had = self._watch_keys
+        if had == keys:
+            keys = had         # (the same OBJECT while nothing moves: _watch_end and the plan key then compare by identity)
+        elif had is not None:      # (an object's sources are the same tensors' places for life: the two tuples pair up)
+            self._cache.drop({k for pair in zip(had, keys) if pair[0] != pair[1] for k in pair})
+            self._gen += 1           # frames prepared before this point hold pointers into the old blobs (frame_launch refuses them)
         self._watch_keys = keys
         n, dev = len(srcs), srcs[0][0].device
-        if getattr(self, "_watch_dev", None) is None or self._watch_dev.device != dev or self._watch_dev.shape[1] < n:
+        if self._watch_dev is None or self._watch_dev.device != dev or self._watch_dev.shape[1] < n:
             self._watch_dev = torch.zeros(2, max(n, 24), dtype=torch.int64, device=dev)
             self._watch_host = torch.zeros(2, max(n, 24), dtype=torch.int64).pin_memory()
             self._watch_rows = [(self._watch_dev[k], self._watch_host[k]) for k in (0, 1)]     # (row views made once: a view per frame is host time)
-        if getattr(self, "_watch_args_key", None) != keys:     # (the keys hold the data pointers: same keys, same argument arrays)
-            self._watch_args = ((ctypes.c_void_p * n)(*[t.data_ptr() for t, _ in srcs]), (ctypes.c_uint64 * n)(*[t.numel() * t.element_size() for t, _ in srcs]),
-                                (_u32 * n)(*[int(st) for _, st in srcs]))
-            self._watch_args_key = keys
-        ptrs, sizes, strides = self._watch_args
+        ptrs, sizes, strides = self._cache.get("watch_args", keys, _checksum_args, srcs)     # (the keys hold the data pointers: same keys, same argument arrays)
         drow, hrow = self._watch_rows[slot]
         call("pnr_checksum", ptrs, sizes, strides, _u32(n), ptr(drow))
         hrow.copy_(drow, non_blocking=True)     # complete once the frame's own read-back is (same stream)
-        return record, n, slot
+        return self._watch_ref is None, keys, slot
 
     def _watch_end(self, state):
         """True: the frame just rendered used blobs that match their sources."""
-        record, n, slot = state
-        now = tuple(self._watch_rows[slot][1][:n].tolist())
-        if record:
-            self._watch_ref = now
-            return True
-        return now == self._watch_ref
+        record, keys, slot = state
+        sums = tuple(self._watch_rows[slot][1][:len(keys)].tolist())
+        ref = self._watch_ref            # (keys, checksums) as recorded
+        if not record:
+            if ref is None or keys is not self._watch_keys:      # invalidated, or a source moved, under the frame
+                return False
+            if keys is ref[0]:
+                return sums == ref[1]
+            have = dict(zip(*ref))      # a source whose key the reference holds must have its checksum; one that moved since gets its reference here
+            if any(have.get(k, c) != c for k, c in zip(keys, sums)):
+                return False
+        self._watch_ref = (keys, sums)
+        return True
 
     def _watch_failed(self):
-        import warnings
         warnings.warn("fused field: parameters were rewritten behind torch's version counters (a `.data` write); the packed blobs were rebuilt and "
                       "the frame rendered again -- invalidate_fused_caches(model) after such writes avoids the double render")
         self.invalidate_caches()
@@ -504,7 +579,7 @@ class _FrameLoop:
             return self._frame_prepare(rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises)
 
     def frame_launch(self, tok):
-        if tok.gen != self.__dict__.get("_gen", 0):
+        if tok.gen != self._gen:
             raise StaleFrame("the frame was prepared before the packed blobs were rebuilt")
         tok.stream = stream_ptr()
         name = self._frame_entry + "_submit"
@@ -535,51 +610,46 @@ class _FrameLoop:
         _lib.check(rc, self._frame_entry)
         return self._frame_post(tok)
 
+    def _frame_plan(self, N, dev, order, m, enc):
+        """Everything of the argument struct that only changes when a parameter, a table or a setting does, filled once and kept (slot ("plan", 0 / 1): re-deriving
+        these fifty values per frame was a third of the call's host time in front of the first launch) -> (args, its pnr_nerf_frame_args part, precision, watch, tensors it points at)."""
+        nbytes = int(self._frame_workspace_bytes(_lib.load(), N))
+        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        prec, watch = self.frame_precision()
+        args, a = self._frame_struct()
+        a.table_dtype = 1 if self.table_half else 0
+        a.N = N
+        a.bound, a.C, a.H = float(m.bound), int(m.cascade), int(m.grid_size)
+        a.offsets = enc.offsets.data_ptr()
+        a.num_levels, a.S, a.base_resolution, a.gridtype = enc.num_levels, float(np.log2(enc.per_level_scale)), enc.base_resolution, enc.gridtype_id
+        a.field_precision, a.watch_overflow = int(prec), int(watch)
+        for k, v in enumerate(self.enc_scales(prec)):
+            a.enc_scale[k] = v
+        a.density_scale = float(m.density_scale)
+        a.workspace, a.workspace_bytes = self._ws.data_ptr(), nbytes
+        a.ray_order = order.data_ptr() if order is not None else None
+        return args, a, prec, watch, (self._ws, order) + self._frame_fill(args, a, m, enc)
+
     def _frame_prepare(self, rays_o, rays_d, nears, fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises=None):
         from . import raymarching
         m = self.model
         N = rays_o.shape[0]
         dev = rays_o.device
-        slot = self._slot = 1 - self.__dict__.get("_slot", 1)
+        slot = self._slot = 1 - self._slot
         watch_state = self._watch_begin(slot)
         ws = torch.empty(N, dtype=torch.float32, device=dev)
         depth = torch.empty(N, dtype=torch.float32, device=dev)
         image = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        order = getattr(self, "ray_order", None)
+        order = self.ray_order
         if order is not None and order.numel() != N:
             order = None
         enc = m.encoder
-        # Everything of the argument struct that only changes when a parameter, a table or a setting does is filled once and kept (the "plan"): the key holds
-        # the identity and version of every source (the watch's keys, formed above), the frame size and the settings read here and in _frame_fill.  A frame whose
-        # key matches sets the per-frame fields only -- a third of the call's host time in front of the first launch went into re-deriving the same fifty values.
-        plan_key = (self._watch_keys, N, dev, int(self.precision), bool(self.table_half), self.__dict__.get("_overflowed_key"), None if order is None else (id(order), order.data_ptr()),
+        plan_key = (self._watch_keys, N, dev, int(self.precision), bool(self.table_half), self._overflowed_key, None if order is None else (id(order), order.data_ptr()),
                     float(m.bound), int(m.cascade), int(m.grid_size), float(m.density_scale), enc.num_levels, enc.per_level_scale, enc.base_resolution, enc.gridtype_id,
                     self._frame_key(m, enc))
-        plans = self.__dict__.get("_frame_plan")
-        if plans is None:
-            plans = self._frame_plan = {}
-        plan = plans.get(slot)
-        if plan is None or plan[0] != plan_key or PARANOID:
-            nbytes = int(self._frame_workspace_bytes(_lib.load(), N))
-            if getattr(self, "_ws", None) is None or self._ws.numel() < nbytes or self._ws.device != dev:
-                self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            prec, watch = self.frame_precision()
-            args, a = self._frame_struct()
-            a.table_dtype = 1 if self.table_half else 0
-            a.N = N
-            a.bound, a.C, a.H = float(m.bound), int(m.cascade), int(m.grid_size)
-            a.offsets = enc.offsets.data_ptr()
-            a.num_levels, a.S, a.base_resolution, a.gridtype = enc.num_levels, float(np.log2(enc.per_level_scale)), enc.base_resolution, enc.gridtype_id
-            a.field_precision, a.watch_overflow = int(prec), int(watch)
-            for k, v in enumerate(self.enc_scales(prec)):
-                a.enc_scale[k] = v
-            a.density_scale = float(m.density_scale)
-            a.workspace, a.workspace_bytes = self._ws.data_ptr(), nbytes
-            a.ray_order = order.data_ptr() if order is not None else None
-            plan = plans[slot] = (plan_key, args, a, prec, watch, (self._ws, order) + self._frame_fill(args, a, m, enc))     # (the tensors whose addresses the struct holds)
-        args, a, prec, watch = plan[1], plan[2], plan[3], plan[4]
-        # The packed blob is NOT part of the plan: it is looked up per frame (a key compare when nothing changed) and the token keeps it alive; a repack -- new
-        # weights, or the stand-alone ops (`self(x, d)` from network.forward) asking for THEIR precision -- goes into another tensor (_pack).
+        args, a, prec, watch, kept = self._cache.get(("plan", slot), plan_key, self._frame_plan, N, dev, order, m, enc)
+        # The packed blob is NOT part of the plan: it is looked up per frame (a key compare when nothing changed, see _pack) and the token keeps it alive
         blob = self._pack(prec)
         a.packed_weights = blob.data_ptr()
         mip = raymarching.occupancy_mip(m.density_bitfield, m.cascade, m.grid_size, m.bound)
@@ -592,15 +662,15 @@ class _FrameLoop:
         a.dt_gamma, a.max_steps, a.T_thresh = float(dt_gamma), int(max_steps), float(T_thresh)
         a.weights_sum, a.depth, a.image = ws.data_ptr(), depth.data_ptr(), image.data_ptr()
         a.stats = ctypes.cast(stats, ctypes.c_void_p)
-        a.kernel_ms = ctypes.cast(kms, ctypes.c_void_p) if getattr(self, "time_grid_kernel", False) else None     # (bench.py sets it; a palette object has none until then)
+        a.kernel_ms = ctypes.cast(kms, ctypes.c_void_p) if self.time_grid_kernel else None     # (bench.py sets it)
         finished = _set_finish(a, bg_color, N, self._frame_finish_mask)
         a.noises = _noises_ptr(noises, N, dev)
         for t, name in ((rays_o, "rays_o"), (rays_d, "rays_d"), (nears, "nears"), (fars, "fars")):
             require(t, torch.float32, name)
-        tok = _FrameToken(gen=self.__dict__.get("_gen", 0), args=args, base=a, out=(ws, depth, image), stats=stats, kms=kms, watch_state=watch_state, watch=watch, finished=finished,
+        tok = _FrameToken(gen=self._gen, args=args, base=a, out=(ws, depth, image), stats=stats, kms=kms, watch_state=watch_state, watch=watch, finished=finished,
                           nears=nears, fars=fars,
                           again=(rays_o, rays_d, None if aabb is not None else nears, None if aabb is not None else fars, dt_gamma, max_steps, T_thresh, bg_color, aabb, min_near, noises),
-                          keep=(mip, bg_color, blob), noises=noises)
+                          keep=(mip, bg_color, blob, kept), noises=noises)
         self._frame_extras(tok, N, dev)
         return tok
 
@@ -614,21 +684,17 @@ class _FrameLoop:
                                          "grid_ms": float(kms[0]), "grid_launches": int(kms[1]), "finished": tok.finished, "nears": tok.nears, "fars": tok.fars})
 
 
-class BackgroundFused:
+class BackgroundFused(_FusedState):
     """The background model of a bg_radius > 0 network as ONE launch per frame (pnr_background_forward: sphere coordinates, the 2-D lookup of
-    `encoder_bg`, SH, bg_net, sigmoid), for inference batches.  Conventions of the field classes: the weight blob and, for the reference's -O mode,
-    the half copy of the table are cached and rebuilt when torch's version counters move (_pkey) or invalidate_fused_caches(model) says so; a
-    repack goes into a NEW tensor, so a launch already enqueued keeps reading what it was given; `state()` changes whenever a cached blob was
-    or has to be rebuilt, which is how a frame prepared before a weight change is recognised (renderer.render_launch).
+    `encoder_bg`, SH, bg_net, sigmoid), for inference batches.  The weight blob and, for the reference's -O mode, the half copy of the table are slots of
+    the object's cache ("blob", "half_table": see _Derived); `state()` changes whenever one was or has to be rebuilt (renderer.render_launch looks at it).
     Training batches (train_from_rays / train_from_coords) use none of these caches: the launches read the parameters themselves."""
 
     def __init__(self, model):
         if not self.supported(model):
             raise RuntimeError("the fused background launch is specialised for the reference's background model (hashgrid 4 x 2 over 2-D, SH degree 4, bg_net 24 -> 64 -> 3)")
         self.model = model
-        self._blob = None
-        self._emb_half = None
-        self._gen = 0
+        self._init_state()
 
     @staticmethod
     def supported(m):
@@ -645,34 +711,33 @@ class BackgroundFused:
     def _weights(self):
         return [_weight_of(self.model, "bg_net", 0), _weight_of(self.model, "bg_net", 1)]
 
-    def invalidate_caches(self):
-        self._blob = None
-        self._emb_half = None
-        self._gen += 1
-
     def state(self):
         """Identity of everything a launch reads, as far as torch can tell, and the number of invalidations so far."""
         return (self._gen,) + tuple(_pkey(w) for w in self._weights()) + (_pkey(self.model.encoder_bg.embeddings),)
 
     def _pack(self):
         ws = self._weights()
-        key = tuple(_pkey(w) for w in ws)
-        hit = self._blob
-        if hit is None or hit[0] != key or hit[1].device != ws[0].device or PARANOID:
-            blob = torch.empty(int(_lib.load().pnr_background_packed_bytes()) // 4, dtype=torch.float32, device=ws[0].device)
-            call("pnr_background_pack", *[ptr(require(w.detach().contiguous(), torch.float32, "bg_net weight")) for w in ws], ptr(blob))
-            hit = self._blob = (key, blob)
-        return hit[1]
+        return self._cache.get("blob", (ws[0].device,) + tuple(_pkey(w) for w in ws), self._pack_build, ws)
+
+    def _pack_build(self, ws):
+        blob = torch.empty(int(_lib.load().pnr_background_packed_bytes()) // 4, dtype=torch.float32, device=ws[0].device)
+        call("pnr_background_pack", *[ptr(require(w.detach().contiguous(), torch.float32, "bg_net weight")) for w in ws], ptr(blob))
+        return blob
 
     def _table(self, half):
         emb = self.model.encoder_bg.embeddings
-        if half:      # the reference's --fp16 table (`embeddings.to(torch.half)` per forward, gridencoder/grid.py:38): converted once per update here
-            return _half_copy(self, "_emb_half", emb), 1
-        return require(emb.detach(), torch.float32, "encoder_bg.embeddings"), 0
+        return (self._half_table(emb), 1) if half else (require(emb.detach(), torch.float32, "encoder_bg.embeddings"), 0)
+
+    def _set_geometry(self, a, table, dtype):     # the fields of a Background(Train)Args that say where the table is and how the lookup, the SH and bg_net are shaped
+        m, enc = self.model, self.model.encoder_bg
+        a.embeddings, a.table_dtype, a.offsets, a.table_rows = table.data_ptr(), dtype, require(enc.offsets, torch.int32, "offsets").data_ptr(), int(table.shape[0])
+        a.num_levels, a.level_dim, a.S, a.H = enc.num_levels, enc.level_dim, float(np.log2(enc.per_level_scale)), enc.base_resolution
+        a.gridtype, a.align_corners = enc.gridtype_id, int(enc.align_corners)
+        a.sh_degree, a.num_layers, a.hidden_dim = int(m.encoder_dir.degree), int(m.num_layers_bg), int(m.hidden_dim_bg)
 
     @torch.no_grad()
     def _launch(self, rays_o, rays_d, coords, want_coords, half):
-        m, enc = self.model, self.model.encoder_bg
+        m = self.model
         rays_d = require(rays_d.reshape(-1, 3).contiguous(), torch.float32, "rays_d")
         N, dev = rays_d.shape[0], rays_d.device
         half = torch.is_autocast_enabled() if half is None else bool(half)
@@ -693,10 +758,7 @@ class BackgroundFused:
             if rays_o.shape[0] != N:
                 raise RuntimeError("background: one origin per direction")
             a.rays_o, a.radius = rays_o.data_ptr(), float(m.bg_radius)
-        a.embeddings, a.table_dtype, a.offsets, a.table_rows = table.data_ptr(), dtype, require(enc.offsets, torch.int32, "offsets").data_ptr(), int(table.shape[0])
-        a.num_levels, a.level_dim, a.S, a.H = enc.num_levels, enc.level_dim, float(np.log2(enc.per_level_scale)), enc.base_resolution
-        a.gridtype, a.align_corners = enc.gridtype_id, int(enc.align_corners)
-        a.sh_degree, a.num_layers, a.hidden_dim = int(m.encoder_dir.degree), int(m.num_layers_bg), int(m.hidden_dim_bg)
+        self._set_geometry(a, table, dtype)
         a.packed, a.out = blob.data_ptr(), out.data_ptr()
         a.coords_out = coords_out.data_ptr() if coords_out is not None else None
         # (the launch is enqueued on torch's current stream before this returns: the caching allocator keeps `table`, `blob` and the inputs alive for it)
@@ -713,13 +775,9 @@ class BackgroundFused:
         return self._launch(None, d, x, False, half).view(*d.shape[:-1], 3)
 
     def _train_args(self, N, rays_d, coords, table):
-        m, enc = self.model, self.model.encoder_bg
         a = _lib.BackgroundTrainArgs()
         a.N, a.rays_d, a.coords_in = N, rays_d.data_ptr(), ptr(coords)
-        a.embeddings, a.table_dtype, a.offsets, a.table_rows = table.data_ptr(), 0, require(enc.offsets, torch.int32, "offsets").data_ptr(), int(table.shape[0])
-        a.num_levels, a.level_dim, a.S, a.H = enc.num_levels, enc.level_dim, float(np.log2(enc.per_level_scale)), enc.base_resolution
-        a.gridtype, a.align_corners = enc.gridtype_id, int(enc.align_corners)
-        a.sh_degree, a.num_layers, a.hidden_dim = int(m.encoder_dir.degree), int(m.num_layers_bg), int(m.hidden_dim_bg)
+        self._set_geometry(a, table, 0)
         return a
 
     def _train(self, rays_o, rays_d, coords):
@@ -820,16 +878,14 @@ def background_fused(model):
     return f
 
 
-class NeRFFieldFused(_PrecisionGuard, _SourceWatch, _FrameLoop):
+class NeRFFieldFused(_FusedState, _PrecisionGuard, _SourceWatch, _FrameLoop):
     """Caches the MFMA-ordered weight blob of a NeRFNetwork and evaluates (sigma, rgb) for sample batches."""
 
     def __init__(self, model):
         self.model = model
-        self.packed = None
-        self.versions = None
+        self._init_state()
         self.precision = 1  # PNR_FIELD_F16X3 (split-fp16 matrix path, ~2^-22 relative); 0 = PNR_FIELD_FP32 (exact fmaf chains); 2 = PNR_FIELD_F16X2 (opt-in: ~1e-5 on a colour)
         self.supports_f16x2 = True
-        self.time_grid_kernel = False  # bench.py: HIP-event timing of the grid-encode launches inside the native frame loop
         self.table_half = False        # native loop: look the hash table up as fp16 with the reference's half interpolation (its --fp16 mode)
         m = model
         ok = (m.encoder.num_levels == 16 and m.encoder.level_dim == 2 and m.encoder.input_dim == 3 and m.hidden_dim == 64 and m.geo_feat_dim == 15
@@ -840,16 +896,6 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch, _FrameLoop):
     def _weights(self):
         m = self.model
         return [_weight_of(m, "sigma_net", 0), _weight_of(m, "sigma_net", 1), _weight_of(m, "color_net", 0), _weight_of(m, "color_net", 1), _weight_of(m, "color_net", 2)]
-
-    def invalidate_caches(self):
-        self.versions = None
-        self._blobs = {}
-        self._emb_half = None
-        self._guard_key = None
-        self._watch_ref = None       # the next frame rebuilds every blob: its source checksums become the reference
-        self._guard_held = self._weights_held = None   # (a held call that retries asks again)
-        self._frame_plan = None      # the frame call's kept argument struct points into the blobs
-        self._gen = self.__dict__.get("_gen", 0) + 1     # frames prepared before this point hold pointers into the old blobs (frame_launch refuses them)
 
     def _guard_tables(self):
         return [self.model.encoder.embeddings]
@@ -867,29 +913,11 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch, _FrameLoop):
         c1 = l1[3] * c0
         return max(enc, h1, geo, c0, c1)
 
-    def _blob_key(self, prec):
-        """What the blob of precision `prec` is derived from: every weight of the field and the precision (the blob's layout depends on it)."""
-        return tuple(_pkey(w) for w in self._w()) + (prec,)
-
-    def _pack(self, prec=None):
-        """The MFMA-ordered weight blob for `prec`: one blob per precision (the stand-alone ops may run fp32 where the frame loops run split-fp16 with the
-        watch, and a frame prepared or in flight at one precision must never see the other's layout), each packed into a NEW tensor when its sources change --
-        never rewritten in place, so the tensor a kept or submitted argument struct points at (frame tokens hold it) stays as it was."""
-        prec = self.effective_precision() if prec is None else prec
-        versions = self._blob_key(prec)
-        blobs = self.__dict__.get("_blobs")
-        if blobs is None:
-            blobs = self._blobs = {}
-        hit = blobs.get(prec)
-        ws = self._w()
-        dev = ws[0].device
-        if hit is None or hit[0] != versions or hit[1].device != dev or PARANOID:
-            blob = torch.empty(int(_lib.load().pnr_nerf_field_packed_bytes()) // 4, dtype=torch.float32, device=dev)
-            ws = [require(w.detach().contiguous(), torch.float32, "weight") for w in ws]
-            call("pnr_nerf_field_pack", *[ptr(w) for w in ws], ptr(blob), _int(prec))
-            hit = blobs[prec] = (versions, blob)
-        self.versions, self.packed = hit      # (the blob handed out last and its key)
-        return hit[1]
+    def _pack_build(self, prec):
+        ws = [require(w.detach().contiguous(), torch.float32, "weight") for w in self._w()]
+        blob = torch.empty(int(_lib.load().pnr_nerf_field_packed_bytes()) // 4, dtype=torch.float32, device=ws[0].device)
+        call("pnr_nerf_field_pack", *[ptr(w) for w in ws], ptr(blob), _int(prec))
+        return blob
 
     _frame_entry = "pnr_nerf_render_frame"
 
@@ -905,8 +933,8 @@ class NeRFFieldFused(_PrecisionGuard, _SourceWatch, _FrameLoop):
 
     def _frame_fill(self, args, a, m, enc):
         emb = require(enc.embeddings.detach(), torch.float32, "embeddings")
-        if self.table_half:   # the reference's --fp16 tables (`embeddings.to(torch.half)` per forward, gridencoder/grid.py:38): converted once per update here
-            emb = _half_copy(self, "_emb_half", enc.embeddings)
+        if self.table_half:   # the reference's --fp16 tables
+            emb = self._half_table(enc.embeddings)
         a.embeddings = emb.data_ptr()
         return (emb,)
 
@@ -929,17 +957,13 @@ class DensityFused(NeRFFieldFused):
     gradient.  Works for NeRFNetwork and PaletteNetwork (same encoder / sigma_net / color_net shapes; only the sigma_net part of the blob
     is read).  Users: the occupancy sweep (update_extra_state), density() under no_grad, PaletteNeRF training (geometry detached)."""
 
-    def _guard_weights(self):   # only sigma_net runs here: colour-head updates (every training step) must not touch the guard or the blob
-        m = self.model
-        return [m.sigma_net[0].weight, m.sigma_net[1].weight]
+    def _guard_weights(self):   # only sigma_net runs here: colour-head updates (every training step) must not touch the guard or the blob (_blob_sources)
+        return [_weight_of(self.model, "sigma_net", 0), _weight_of(self.model, "sigma_net", 1)]
 
     def _guard_bound(self, tmax, scales):
         l1 = [float(v) for v in torch.stack([_l1(w).float() for w in self._guard_weights()]).cpu().tolist()]
         enc = tmax[0] * scales[0]
         return max(enc, l1[0] * enc)
-
-    def _blob_key(self, prec):     # only the sigma_net part of the blob is read here: colour-head updates keep the blob
-        return tuple(_pkey(w) for w in self._guard_weights()) + (prec,)
 
     @torch.no_grad()
     def __call__(self, x, scale=1.0, want_geo=True, enc=None):
@@ -964,14 +988,13 @@ def density_fused(model):
     return d
 
 
-class PaletteFieldFused(_PrecisionGuard, _SourceWatch, _FrameLoop):
+class PaletteFieldFused(_FusedState, _PrecisionGuard, _SourceWatch, _FrameLoop):
     """Fused PaletteNeRF field + colour-basis composite (pnr_palette_field_forward).  Produces, per sample,
     sigma * density_scale, rgb and one packed aux row [direct 3 | view_dep 3 | omega nb | basis_rgb 3nb | unscaled 3nb | clip | pad]."""
 
     def __init__(self, model):
         self.model = model
-        self.packed = None
-        self.versions = None
+        self._init_state()
         m = model
         ok = (m.encoder.num_levels == 16 and m.encoder.level_dim == 2 and m.hidden_dim == 64 and m.geo_feat_dim == 15 and m.num_layers == 2
               and m.num_layers_color == 3 and m.encoder_dir.degree == 4 and 1 <= m.num_basis <= _lib.MAX_BASIS and m.opt.clip_dim <= _lib.MAX_CLIP)
@@ -1004,14 +1027,6 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch, _FrameLoop):
         m = self.model
         return [m.basis_color, m.offsets_radiance_net.bias]
 
-    def invalidate_caches(self):
-        self.versions = None
-        self._pair_key = self._triple_key = self._triple_half_key = self._guard_key = None
-        self._watch_ref = None       # the next frame rebuilds every blob: its source checksums become the reference
-        self._guard_held = self._weights_held = None   # (a held call that retries asks again)
-        self._frame_plan = None      # the frame call's kept argument struct points into the blobs
-        self._gen = self.__dict__.get("_gen", 0) + 1     # frames prepared before this point hold pointers into the old blobs (frame_launch refuses them)
-
     def _watched(self):
         return [(w, 1) for w in self._w() + self._tables()] + [(t, TABLE_CHECK_STRIDE) for t in self._guard_tables()]
 
@@ -1038,44 +1053,39 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch, _FrameLoop):
             sites += [ce, l1[12] * ce]
         return max(sites)
 
-    def _pack(self, prec=None):
+    def _blob_sources(self):
+        return self._w() + self._tables()
+
+    def _pack_build(self, prec):
+        # (the contiguous fp32 forms of the sources are not kept: the pack is enqueued on torch's current stream before they are freed, as for the other blobs)
         ws = self._w()
-        prec = self.effective_precision() if prec is None else prec
-        versions = tuple(_pkey(w) for w in ws + self._tables()) + (prec,)
-        if self.packed is None or versions != self.versions or PARANOID:
-            dev = ws[0].device
-            lib = _lib.load()
-            self.packed = torch.empty(int(lib.pnr_palette_field_packed_bytes(self.nb, self.clip_dim, int(self.pred_clip))), dtype=torch.uint8, device=dev)
-            self._keep = [require(w.detach().contiguous(), torch.float32, "weight") for w in ws]
-            pw = _lib.PaletteWeights()
-            names = ["sigma0", "sigma1", "diff0", "diff1", "diff2", "color0", "color1", "color2", "basis0", "basis1", "offsets_radiance", "omega"]
-            if self.pred_clip:
-                names += ["clip0", "clip1"]
-            for name, w in zip(names, self._keep):
-                setattr(pw, name, w.data_ptr())
-            self._keep_tables = [require(t.detach().float().contiguous(), torch.float32, "palette / bias") for t in self._tables()]
-            pw.basis_color, pw.or_bias = self._keep_tables[0].data_ptr(), self._keep_tables[1].data_ptr()
-            pw.num_basis, pw.clip_dim, pw.pred_clip, pw.precision = self.nb, self.clip_dim, int(self.pred_clip), int(prec)
-            rc = lib.pnr_palette_field_pack(ctypes.byref(pw), ctypes.c_void_p(self.packed.data_ptr()),
-                                            ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-            _lib.check(rc, "pnr_palette_field_pack")
-            self.versions = versions
-        return self.packed
+        lib = _lib.load()
+        blob = torch.empty(int(lib.pnr_palette_field_packed_bytes(self.nb, self.clip_dim, int(self.pred_clip))), dtype=torch.uint8, device=ws[0].device)
+        pw = _lib.PaletteWeights()
+        srcs = [require(w.detach().contiguous(), torch.float32, "weight") for w in ws]      # (12 weights, 14 with the clip head: _weights' order)
+        for name, w in zip(("sigma0", "sigma1", "diff0", "diff1", "diff2", "color0", "color1", "color2", "basis0", "basis1", "offsets_radiance", "omega", "clip0", "clip1"), srcs):
+            setattr(pw, name, w.data_ptr())
+        tabs = [require(t.detach().float().contiguous(), torch.float32, "palette / bias") for t in self._tables()]
+        pw.basis_color, pw.or_bias = tabs[0].data_ptr(), tabs[1].data_ptr()
+        pw.num_basis, pw.clip_dim, pw.pred_clip, pw.precision = self.nb, self.clip_dim, int(self.pred_clip), int(prec)
+        rc = lib.pnr_palette_field_pack(ctypes.byref(pw), ctypes.c_void_p(blob.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        _lib.check(rc, "pnr_palette_field_pack")
+        return blob
 
     def _edit_struct(self):
         """The model's RegionEdit / Stylizer state as a pnr_palette_edit (None when neither is set).  Rebuilt when the controllers' tensors
         change (object identity / version): a few small D2H copies per change, none per frame."""
-        m = self.model
-        edit, sty = getattr(m, "edit", None), getattr(m, "stylizer", None)
+        edit, sty = getattr(self.model, "edit", None), getattr(self.model, "stylizer", None)
         if edit is None and sty is None:
             return None
         if sty is not None:
             key = ("s", id(sty), _pkey(sty.dI), _pkey(sty.dP), _pkey(sty.ddelta))
         else:
-            tkey = lambda t: None if t is None or not torch.is_tensor(t) else (id(t), t.data_ptr(), t._version)
-            key = ("e", id(edit), tkey(edit.delta_hsv), tkey(edit.mean_xyz), tkey(edit.mean_clip), float(edit.std_xyz), float(edit.std_clip), bool(edit.weight_mode))
-        if getattr(self, "_edit_key", None) == key and not PARANOID:
-            return self._edit
+            key = ("e", id(edit), float(edit.std_xyz), float(edit.std_clip), bool(edit.weight_mode)) + tuple(
+                _pkey(t) if torch.is_tensor(t) else None for t in (edit.delta_hsv, edit.mean_xyz, edit.mean_clip))
+        return self._cache.get("edit", key, self._edit_build, edit, sty)
+
+    def _edit_build(self, edit, sty):
         e = _lib.PaletteEdit()
         nb = self.nb
         if sty is not None:    # palette/renderer.py:150-183
@@ -1099,51 +1109,45 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch, _FrameLoop):
                     e.mean_xyz[k] = v
             if edit.mean_clip is not None:
                 mc = edit.mean_clip.detach().float().cpu().reshape(-1).tolist()
-                if len(mc) != int(m.opt.clip_dim):
+                if len(mc) != int(self.model.opt.clip_dim):
                     raise RuntimeError("RegionEdit.mean_clip must have clip_dim entries")
                 e.has_mean_clip = len(mc)
                 for k, v in enumerate(mc):
                     e.mean_clip[k] = v
             e.std_xyz, e.std_clip, e.weight_mode = float(edit.std_xyz), float(edit.std_clip), int(bool(edit.weight_mode))
-        self._edit, self._edit_key = e, key
         return e
 
     @torch.no_grad()
-    def _pair_table(self):
-        """`encoder` and `encoder_palette` interleaved row by row ([rows, 4] fp32; one 16-byte gather then serves both lookups).
-        A copy of both tables (2 x 50 MB for the shipped config), rebuilt when either changes."""
-        m = self.model
-        key = (_pkey(m.encoder.embeddings), _pkey(m.encoder_palette.embeddings), bool(self.table_half))
-        a, b = m.encoder.embeddings.detach(), m.encoder_palette.embeddings.detach()
-        if a.dtype != torch.float32 or b.dtype != torch.float32 or a.shape != b.shape or a.shape[1] != 2:
-            return None
-        if getattr(self, "_pair_key", None) != key or PARANOID:
-            if self.table_half:   # rows of 4 halves: (a.x, a.y, b.x, b.y)
-                out = torch.cat([a.to(torch.float16), b.to(torch.float16)], dim=1).contiguous()
-            else:
-                out = torch.empty(a.shape[0], 4, dtype=torch.float32, device=a.device)
-                call("pnr_interleave_tables", ptr(a.contiguous()), ptr(b.contiguous()), ctypes.c_uint64(a.shape[0]), ptr(out))
-            self._pair, self._pair_key = out, key
-        return self._pair
-
-    @torch.no_grad()
-    def _triple_table(self):
-        """--pred_clip: the three tables interleaved row by row ([rows, 8] fp32 = encoder, encoder_palette, encoder_clip, 2 pad): one 32-byte
-        row per corner serves all three lookups.  table_half: [rows, 8] fp16 instead (pnr_interleave_tables3_half, one 16-byte row).  Rebuilt
-        when any table changes; the fp32 and half copies are cached apart (a new tensor per rebuild: a frame in flight keeps the one it was given)."""
-        m = self.model
-        half = bool(self.table_half)
-        key = tuple(_pkey(e.embeddings) for e in (m.encoder, m.encoder_palette, m.encoder_clip)) + (half,)
-        ts = [e.embeddings.detach() for e in (m.encoder, m.encoder_palette, m.encoder_clip)]
+    def _interleaved(self, slot, encs, build):
+        ts = [e.embeddings for e in encs]
         if any(t.dtype != torch.float32 or t.shape != ts[0].shape or t.shape[1] != 2 for t in ts):
             return None
-        name = "_triple_half" if half else "_triple"
-        if getattr(self, name + "_key", None) != key or PARANOID:
-            out = torch.empty(ts[0].shape[0], 8, dtype=torch.float16 if half else torch.float32, device=ts[0].device)
-            call("pnr_interleave_tables3_half" if half else "pnr_interleave_tables3", *[ptr(t.contiguous()) for t in ts], ctypes.c_uint64(ts[0].shape[0]), ptr(out))
-            setattr(self, name, out)
-            setattr(self, name + "_key", key)
-        return getattr(self, name)
+        half = bool(self.table_half)
+        return self._cache.get(slot, tuple(_pkey(t) for t in ts) + (half,), build, [t.detach() for t in ts], half)
+
+    def _pair_table(self):
+        """`encoder` and `encoder_palette` interleaved row by row ([rows, 4] fp32; one 16-byte gather then serves both lookups; table_half: rows of 4
+        halves).  A copy of both tables (2 x 50 MB for the shipped config): ONE slot with table_half in its key, so that it is never held twice."""
+        return self._interleaved("pair", (self.model.encoder, self.model.encoder_palette), self._pair_build)
+
+    def _pair_build(self, ts, half):
+        a, b = ts
+        if half:   # rows of 4 halves: (a.x, a.y, b.x, b.y)
+            return torch.cat([a.to(torch.float16), b.to(torch.float16)], dim=1).contiguous()
+        out = torch.empty(a.shape[0], 4, dtype=torch.float32, device=a.device)
+        call("pnr_interleave_tables", ptr(a.contiguous()), ptr(b.contiguous()), ctypes.c_uint64(a.shape[0]), ptr(out))
+        return out
+
+    def _triple_table(self):
+        """--pred_clip: the three tables interleaved row by row ([rows, 8] fp32 = encoder, encoder_palette, encoder_clip, 2 pad): one 32-byte
+        row per corner serves all three lookups.  table_half: [rows, 8] fp16 instead (one 16-byte row).  A slot each: ("triple", half)."""
+        m = self.model
+        return self._interleaved(("triple", bool(self.table_half)), (m.encoder, m.encoder_palette, m.encoder_clip), self._triple_build)
+
+    def _triple_build(self, ts, half):
+        out = torch.empty(ts[0].shape[0], 8, dtype=torch.float16 if half else torch.float32, device=ts[0].device)
+        call("pnr_interleave_tables3_half" if half else "pnr_interleave_tables3", *[ptr(t.contiguous()) for t in ts], ctypes.c_uint64(ts[0].shape[0]), ptr(out))
+        return out
 
     _frame_entry = "pnr_palette_render_frame"
     _frame_finish_mask = 7
@@ -1216,12 +1220,7 @@ class PaletteFieldFused(_PrecisionGuard, _SourceWatch, _FrameLoop):
         if self.stand_alone_pair and self.interleave_tables and not self.pred_clip and not self.table_half and pairable(m.encoder, m.encoder_palette):
             pair = self._pair_table()       # opt-in (stand_alone_pair): the native loop's interleaved copy, rebuilt when torch can tell either table changed
         if pair is not None:
-            L = m.encoder.num_levels
-            enc = torch.empty(L, B, 2, device=dev, dtype=torch.float32)
-            enc_pal = torch.empty(L, B, 2, device=dev, dtype=torch.float32)
-            e0 = m.encoder
-            call("pnr_grid_encode_forward_pair", ptr(require(x01, torch.float32, "inputs")), ptr(pair), ptr(e0.offsets), ptr(enc), ptr(enc_pal), _u32(B), _u32(L),
-                 _f32(np.log2(e0.per_level_scale)), _u32(e0.base_resolution), _u32(e0.gridtype_id), _int(int(e0.align_corners)), units=B)
+            enc, enc_pal = _encode_pair(m.encoder, pair, x01)
         else:
             enc = grid_encode_raw(m.encoder, x01)
             enc_pal = grid_encode_raw(m.encoder_palette, x01)

@@ -247,7 +247,7 @@ def test_fp16_autocast_frame_matches_the_reference_half_frame(cuda, golden_dir):
     for k in FULL_KEYS:
         close(r[k], g[f"half_{k}"], FP16_TOL, f"-O {k}")
     assert err_of(r["image"], g["fp32_image"]) > 10 * FP16_TOL                  # the half tables were really used
-    assert background_fused(m)._emb_half is not None
+    assert background_fused(m)._cache.peek("half_table") is not None
 
 
 # ---------------------------------------------------------------- 4. cache life cycle
@@ -270,12 +270,12 @@ def test_cache_life_cycle(cuda):
             m.march_mode, m.fused_field = "native", True
 
     first = frame()
-    blob0 = bgf._blob[1]
+    blob0 = bgf._cache.peek("blob")
     # a write through .data moves no version counter: invalidate_fused_caches() is the rule
     m.bg_net[1].weight.data.mul_(-1.5)
     m.invalidate_fused_caches()
     second = frame()
-    assert bgf._blob[1] is not blob0                                            # a repack goes into a new tensor
+    assert bgf._cache.peek("blob") is not blob0                                            # a repack goes into a new tensor
     assert float((second - first).abs().max()) > 10 * COLOUR_TOL and float((second - expected()).abs().max()) <= COLOUR_TOL
     # an optimiser step moves the version counters
     opt = torch.optim.SGD(list(m.bg_net.parameters()) + [m.encoder_bg.embeddings], lr=0.5)
@@ -287,10 +287,10 @@ def test_cache_life_cycle(cuda):
     # the -O copy of the table follows the table
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
         h1 = bgf.from_rays(ro.view(-1, 3), rd.view(-1, 3))
-        half0 = bgf._emb_half[1]
+        half0 = bgf._cache.peek("half_table")
         m.encoder_bg.embeddings.mul_(0.5)
         h2 = bgf.from_rays(ro.view(-1, 3), rd.view(-1, 3))
-    assert bgf._emb_half[1] is not half0 and float((h1 - h2).abs().max()) > 1e-3
+    assert bgf._cache.peek("half_table") is not half0 and float((h1 - h2).abs().max()) > 1e-3
     # a frame prepared before the weights changed is refused and prepared again
     pend = m.render_prepare(ro, rd, **kw)
     with torch.no_grad():
@@ -508,7 +508,7 @@ def test_frames_in_flight_with_background(cuda, kind):
                 same(a, b, f"pass {step} frame {i}")
             owners = [h.__dict__.get("_bg_fused") for h in fif.models]
             assert all(isinstance(o, BackgroundFused) for o in owners) and len({id(o) for o in owners}) == 3
-            assert len({o._blob[1].data_ptr() for o in owners}) == 3
+            assert len({o._cache.peek("blob").data_ptr() for o in owners}) == 3
             before = want[0]["image"].clone()
             with torch.no_grad():
                 if step == 0:

@@ -456,7 +456,7 @@ def test_palette_native_loop_pair_table_is_bit_identical(cuda, pred_clip):
                 assert torch.equal(torch.nan_to_num(b[k], nan=-7.0), torch.nan_to_num(v, nan=-7.0)), k
         return a
     first = both()
-    assert (getattr(m._fused, "_triple", None) is not None) == pred_clip
+    assert (m._fused._cache.peek(("triple", False)) is not None) == pred_clip
     with torch.no_grad():
         m.encoder_palette.embeddings.mul_(0.5)      # in-place update: the interleaved copy must be rebuilt
         if pred_clip:
@@ -801,7 +801,7 @@ def test_checkpoint_file_to_native_render(cuda, golden_dir, tmp_path, kind, case
     if kind == "palette":
         for k in ("clip_feat", "direct_rgb", "view_dep_rgb", "basis_rgb", "unscaled_basis_rgb", "basis_acc"):
             close(r[k], g[k], what=k)
-        table = fused._triple if fused.pred_clip else fused._pair                      # the interleaved copy holds the LOADED tables
+        table = fused._cache.peek(("triple", False)) if fused.pred_clip else fused._cache.peek("pair")                      # the interleaved copy holds the LOADED tables
         assert torch.equal(table[:, 0:2], m.encoder.embeddings.detach()) and torch.equal(table[:, 2:4], m.encoder_palette.embeddings.detach())
     # a 'best' checkpoint (no density_grid, utils.py:1135) loads non-strictly and leaves the occupancy alone
     best = checkpoint.save_model(m, str(tmp_path / "ngp.pth"), best=True)
@@ -1050,7 +1050,7 @@ def test_kept_frame_arguments_follow_every_setting(cuda, kind):
 def test_kept_frame_arguments_survive_a_stand_alone_field_call_at_another_precision(cuda, kind):
     """weights that fail the STATIC fp16 bound run the stand-alone ops (`model.forward` -> `self._fused(x, d)`) on the exact fp32 path
     (effective_precision() == 0) while the frame loops keep split-fp16 with the overflow watch (frame_precision()).  The stand-alone call repacks the blob for
-    ITS precision -- into a new tensor, its own blob of that precision (NeRF) or the one blob's replacement (PaletteNeRF) -- so the frame call must not keep
+    ITS precision -- into a new tensor, its own blob of that precision (both fields keep a blob per precision) -- so the frame call must not keep
     the blob's address or layout in its kept argument struct: frame, stand-alone call, frame again = the same frame bit for bit, and equal to a fresh object's frame."""
     from palettenerf_amd.fused import NeRFFieldFused, PaletteFieldFused
     if kind == "nerf":
@@ -1079,7 +1079,7 @@ def test_kept_frame_arguments_survive_a_stand_alone_field_call_at_another_precis
     x = (torch.rand(4096, 3, device=cuda) * 2 - 1) * 1.5
     d = torch.nn.functional.normalize(torch.randn(4096, 3, device=cuda), dim=-1)
     for rounds in range(2):
-        alone = kept(x, d)                                   # fp32 layout now sits in (or replaced) the blob the first frame used
+        alone = kept(x, d)                                   # the fp32 blob is the one handed out last now
         assert kept.versions[-1] == 0
         torch.empty(1 << 22, device=cuda).fill_(float("nan"))   # whatever the allocator hands out next must not be what the frame reads
         again = frame(kept)
@@ -1094,6 +1094,112 @@ def test_kept_frame_arguments_survive_a_stand_alone_field_call_at_another_precis
     exact = kept(x, d)
     for a, b in zip(alone, exact):
         assert torch.equal(a, b)
+
+
+def _derived_cache_case(cuda, kind):
+    """The 48 x 64 brick scene of the neighbouring tests with a fused object of its own -> (model, fused object, frame(), tensor_slots())."""
+    from palettenerf_amd.fused import NeRFFieldFused, PaletteFieldFused
+    if kind == "nerf":
+        m = network.NeRFNetwork(bound=2, cuda_ray=True, density_scale=100.0)
+    else:
+        m = network.PaletteNetwork(renderer.default_opt(pred_clip=(kind == "palette_clip")), bound=2, cuda_ray=True, density_scale=100.0)
+    scene.seed_field_(m, 3)
+    m = m.to(cuda).eval()
+    m.density_grid.copy_(torch.from_numpy(scene.brick_density_grid()).to(cuda))
+    raymarching.packbits(m.density_grid, 0.5, m.density_bitfield)
+    H, W = 48, 64
+    ro, rd = scene.get_rays(torch.from_numpy(scene.lookat_pose(azimuth_deg=25.0))[None], scene.intrinsics_from_fov(H, W), H, W)
+    ro, rd = ro[0].to(cuda).contiguous(), rd[0].to(cuda).contiguous()
+    f = (NeRFFieldFused if kind == "nerf" else PaletteFieldFused)(m)
+    frame = lambda: f.render_frame(ro, rd, None, None, 0.0, 1024, 1e-4, bg_color=1, aabb=m.aabb_infer, min_near=m.min_near)
+    tensor_slots = lambda: {s: f._cache.peek(s) for s in f._cache.slots() if torch.is_tensor(f._cache.peek(s))}
+    f.table_half = False
+    assert frame()[-1]["rendered"] > 1000
+    f.table_half = True                                      # (the setting the later frames keep: the pair table is ONE slot with table_half in its key)
+    assert frame()[-1]["rendered"] > 1000
+    return m, f, frame, tensor_slots
+
+
+DERIVED_KINDS = ["nerf", "palette", "palette_clip"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", DERIVED_KINDS)
+def test_every_derived_blob_is_rebuilt_into_a_new_tensor_and_only_when_its_sources_move(cuda, kind):
+    """One native frame with table_half off and one with it on fill every tensor-valued slot of the object's cache (fused._Derived); then, as the issue
+    that introduced the cache sets it: (1) a colour-head weight bumped in place and a frame: the ("blob", prec) value is a new tensor, the table slots hold
+    the same objects, the old blob equals its clone; (2) the palette table (NeRF: the table) bumped and a frame: the table slots derived from it are new, the
+    blob is the same object, the old tables equal their clones; (3) invalidate_caches() and a frame: every slot is new, `_gen` is one higher, the image equals
+    the image from just before the invalidation bit for bit.  A frame whose source keys moved drops what derives from the sources that moved, nothing else (_SourceWatch._watch_begin)."""
+    m, f, frame, tensor_slots = _derived_cache_case(cuda, kind)
+    blob_slot = ("blob", f.frame_precision()[0])
+    table_slots = {"nerf": ["half_table"], "palette": ["pair"], "palette_clip": [("triple", False), ("triple", True)]}[kind]
+    held = tensor_slots()
+    assert set(held) == {blob_slot, *table_slots}
+    clones = {s: t.clone() for s, t in held.items()}
+    seen = {}
+    with torch.no_grad():
+        m.color_net[2].weight.add_(0.01)
+    frame()
+    now = tensor_slots()
+    seen["1 blob new"] = now.get(blob_slot) is not None and now[blob_slot] is not held[blob_slot]
+    seen["1 tables same"] = all(now.get(s) is held[s] for s in table_slots)
+    seen["1 old blob intact"] = torch.equal(held[blob_slot], clones[blob_slot])
+    held1 = {**held, **now}
+    clones1 = {**clones, **{s: t.clone() for s, t in now.items() if t is not held.get(s)}}
+    with torch.no_grad():
+        (m.encoder if kind == "nerf" else m.encoder_palette).embeddings.mul_(1.25)
+    before = frame()
+    now = tensor_slots()
+    seen["2 tables new"] = all(now.get(s) is not held1[s] for s in table_slots)
+    seen["2 blob same"] = now.get(blob_slot) is held1[blob_slot]
+    seen["2 old tables intact"] = all(torch.equal(held1[s], clones1[s]) for s in table_slots)
+    held2 = {**held1, **now}
+    gen = f._gen
+    f.invalidate_caches()
+    after = frame()
+    now = tensor_slots()
+    seen["3 every slot new"] = all(now.get(s) is not held2[s] for s in held2)
+    seen["3 gen one higher"] = f._gen == gen + 1
+    seen["3 image equal"] = torch.equal(after[2], before[2])
+    for what, ok in seen.items():
+        assert ok, (kind, what, seen)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["nerf", "palette"])
+def test_a_data_write_cannot_hide_behind_a_version_bump(cuda, kind):
+    """A frame after some sources moved rebuilds what derives from THOSE sources only (the test above), so the others must still be compared with their
+    reference checksums: (a) a table rewritten through `.data` while a weight is bumped in place is noticed in that frame (warning, blobs rebuilt, frame
+    rendered again); (b) a blob that a stand-alone call packed after an in-place bump, from values a `.data` write then replaced, is not taken over by the
+    next frame.  Each frame equals, bit for bit, the frame after invalidate_caches()."""
+    import warnings
+    m, f, frame, tensor_slots = _derived_cache_case(cuda, kind)
+    table = (m.encoder if kind == "nerf" else m.encoder_palette).embeddings
+    weight = m.color_net[2].weight
+
+    def same_as_after_invalidation(got):
+        f.invalidate_caches()
+        want = frame()
+        assert got[-1]["rendered"] == want[-1]["rendered"] > 1000 and all(torch.equal(a, b) for a, b in zip(got[:-1], want[:-1]))
+        return want
+    with torch.no_grad():
+        weight.add_(0.01)
+    table.data.mul_(1.25)
+    with pytest.warns(UserWarning, match="rewritten behind torch's version counters"):
+        got = frame()
+    first = same_as_after_invalidation(got)
+    x = (torch.rand(4096, 3, device=cuda) * 2 - 1) * 1.5
+    d = torch.nn.functional.normalize(torch.randn(4096, 3, device=cuda), dim=-1)
+    with torch.no_grad():
+        weight.mul_(1.5)
+    f(x, d)                                                  # packs the blob of the bumped weight ...
+    weight.data.mul_(-1.0)                                   # ... which a `.data` write then replaces
+    with warnings.catch_warnings():
+        warnings.filterwarnings("error", message=".*rewritten behind.*")     # (torch can tell that the weight moved: no second render)
+        got = frame()
+    second = same_as_after_invalidation(got)
+    assert not torch.equal(first[2], second[2])
 
 
 @pytest.mark.gpu
