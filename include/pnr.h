@@ -1297,7 +1297,7 @@ int pnr_mesh_vertex_records(const pnr_vertex_records_args* args, pnr_stream_t st
 /* ---- palette extraction, front end: histograms and k-means on the device (additive, ABI 10; csrc/extract.hip) ----
  * PaletteTrainer.extract_palette (palette/utils.py:1135-1200) into palette_extraction as far as run_kmeans' return (:167-226).  The hull
  * simplification stays with the reference's CPU package; `centers` / `center_weights` below are exactly its input.  The weight LUT of the
- * palette it returns is pnr_lut_weights, further down.
+ * palette it returns is pnr_lut_weights, further down.  (The hull simplification on the device has a header of its own: include/pnr_hull.h.)
  *
  * pnr_extract_accumulate: ONE launch folds one rendered view of H x W pixels into both colour histograms.  Per pixel i (row-major):
  *   valid = weights_sum[i] > thresh            strict; a NaN is not valid (:1185)

@@ -369,6 +369,22 @@ class LutWeightsArgs(ctypes.Structure):
                 ("normalize_input", _int), ("weights64", _ptr), ("lut32", _ptr), ("info", _ptr)]
 
 
+# include/pnr_hull.h: the hull simplification.  A header and a table of its own beside include/pnr.h and SIGNATURES; load() binds both.
+HULL_SIGNATURES = {
+    "pnr_hull_simplify": [_ptr, _ptr],
+}
+HULL_MAX_M, HULL_MAX_RELATED = 16, 64                                       # PNR_HULL_*
+HULL_OK, HULL_COPLANAR, HULL_FLAT, HULL_DENSE = 0, 1, 2, 3
+HULL_STOP = ("none", "error", "target", "unchanged", "four")                # PNR_HULL_STOP_NONE, _ERROR, _TARGET, _UNCHANGED, _FOUR
+HULL_ERROR_NONE, HULL_ERROR_FAIL = -1.0, -2.0                               # PNR_HULL_ERROR_*
+
+
+class HullSimplifyArgs(ctypes.Structure):
+    """Mirror of `pnr_hull_simplify_args` (include/pnr_hull.h)."""
+    _fields_ = [("centers", _ptr), ("center_weights", _ptr), ("K", _u32), ("error_thres", ctypes.c_double), ("target_size", _u32),
+                ("palette", _ptr), ("info", _ptr), ("errors", _ptr), ("trace", _ptr), ("vertices", _ptr)]
+
+
 _lib = None
 
 
@@ -382,7 +398,7 @@ def load():
             f"palettenerf_amd: {LIB_PATH} is missing. Build it with `python -m palettenerf_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU or PyTorch fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in (*SIGNATURES.items(), *HULL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

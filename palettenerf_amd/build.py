@@ -47,7 +47,8 @@ def _deps_mtime():
 def _compile(src):
     obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
     hdr_m = max(os.path.getmtime(os.path.join(CSRC, f)) for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc", ".def")))
-    hdr_m = max(hdr_m, os.path.getmtime(os.path.join(HERE, "..", "include", "pnr.h")))
+    inc = os.path.join(HERE, "..", "include")
+    hdr_m = max(hdr_m, *(os.path.getmtime(os.path.join(inc, f)) for f in os.listdir(inc) if f.endswith(".h")))
     if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_m):
         return obj
     subprocess.check_call([hipcc(), *FLAGS, *UNIT_FLAGS.get(os.path.basename(src)[:-4], []), "-c", src, "-o", obj])

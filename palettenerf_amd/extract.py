@@ -1,23 +1,31 @@
-"""The front end of the palette extraction on the device: `PaletteTrainer.extract_palette` (palette/utils.py:1135-1200) into `palette_extraction`
-as far as `run_kmeans`' return (:167-226) -- step 2 of the reference's workflow, between the NeRF stage and the PaletteNeRF stage.
+"""Step 2 of the reference's workflow on the device, between the NeRF stage and the PaletteNeRF stage: `PaletteTrainer.extract_palette`
+(palette/utils.py:1135-1200) and `palette_extraction` (:167-254).
 
 The reference renders every training view, keeps four per-pixel arrays for the pixels with weights_sum > 0.5, concatenates them over all views,
 copies them to the host, histograms them twice on one core and runs scikit-learn's weighted KMeans on the non-empty fine bins.  All the later
 stages need from that are two histograms (512 + 32 768 counts) and K <= 124 colour centres with their weights.  Here a view is ONE launch that
 folds it into both histograms (`pnr_extract_accumulate`: integer counts, so exact and independent of order), the whole weighted k-means is ONE
-launch (`pnr_extract_kmeans`: float64, fixed summation order), and a few kilobytes are read back once.
+launch (`pnr_extract_kmeans`: float64, fixed summation order), the hull simplification that turns the centres into the 4..10 palette colours is
+ONE launch of one workgroup (`pnr_hull_simplify`, include/pnr_hull.h: every hull by brute force, every edge's linear program by vertex
+enumeration, float64, fixed order), and the weight LUT is ONE launch (`pnr_lut_weights`).  A few kilobytes are read back.
+
+    palette, lut, res = extract.extract_palette(model, poses, intrinsics, H, W, trainset, palette_model=palette_model, normalize_input=True)
+
+or step by step:
 
     res = extract.extract_centers(model, poses, intrinsics, H, W, trainset)            # or an image stack, host or device
-    palette = Hull_Simplification_posternerf(res["centers"], prefix, pixel_counts=res["center_weights"], ...)      # the reference's rgbsg package
-    extract.initialize_from_extraction(palette_model, palette, normalize_input=True)   # the weight LUT: ONE launch, stays on the device
+    palette = extract.simplify_hull(res["centers"], res["center_weights"])             # Hull_Simplification_posternerf
+    extract.initialize_from_extraction(palette_model, palette, normalize_input=True)   # the weight LUT: stays on the device
 
-The hull simplification stays with the reference's CPU package; `load_palette` reads the palette it wrote.  The back end
-from the palette on is here: the weight LUT -- the Tan-2016/2018 "ASAP" weights of the 32 768 five-bit bins, palette/utils.py:235-245 -- is
+`simplify_hull_per_op` is the hull simplification on the host in the reference's line order with scipy (ConvexHull, linprog(method="highs")),
+kept to measure and test against and to finish what the kernel hands over by status (a coplanar facet, a flat set, an edge with more related
+faces than the compiled cap).  `save_palette` / `load_palette` write and read the reference's palette files.  The weight LUT -- the
+Tan-2016/2018 "ASAP" weights of the 32 768 five-bit bins, palette/utils.py:235-245 -- is
 `weight_lut` (`pnr_lut_weights`: hull, projection and barycentrics in float64, one launch, nothing uploaded but the palette), and
 `palette_weights` is the same for any device array of colours.  `weight_lut_per_op` is the same statement in numpy on the host, kept to
 measure and test against.  The `extract-radiance-raw.png` debugging image of palette/utils.py:196-203 needs every sample on the host and is
-not produced.  `extract_centers_per_op` is the reference's own sequence, kept to measure and test against.  There is no fallback: on a CPU
-tensor or without the HIP library the device functions raise."""
+not produced, nor are the hull simplification's OBJ files and `extract-palette.png`.  `extract_centers_per_op` is the reference's own sequence,
+kept to measure and test against.  There is no fallback: on a CPU tensor or without the HIP library the device functions raise."""
 import ctypes
 import itertools
 
@@ -462,7 +470,7 @@ def initialize_from_extraction(model, palette, normalize_input=False):
 
 
 def load_palette(path):
-    """The palette the reference's hull simplification wrote: `palette.npz` / `*-palette.npz` (key 'palette') or `*-palette.txt` (one colour a
+    """The palette a hull simplification wrote (the reference's, or save_palette): `palette.npz` / `*-palette.npz` (key 'palette') or `*-palette.txt` (one colour a
     line, three numbers: write_palette_txt, rgbsg/hull_simplification_posternerf.py:86-95).  Returns float64 [M,3]."""
     if str(path).endswith(".npz"):
         with np.load(path) as z:
@@ -608,3 +616,215 @@ def weight_lut_per_op(palette, normalize_input=False):
     weight_lut is measured and tested against.  The reference's own loop needs scipy, cvxopt and a Cython module; this needs numpy."""
     W = palette_weights_per_op(bin_centers_of(5).astype(np.float64), palette, normalize_input=normalize_input)
     return W.reshape(32, 32, 32, W.shape[1])
+
+
+# ---------------------------------------------------------------- the hull simplification (pnr_hull_simplify, include/pnr_hull.h)
+_HULL_STATUS_TEXT = {_lib.HULL_COPLANAR: "a supporting plane of a hull carries a fourth point within 1e-9 (the triangulation of that facet is qhull's choice)",
+                     _lib.HULL_FLAT: "a point set has no point off the plane of any triple (no hull)",
+                     _lib.HULL_DENSE: f"an edge has more than {_lib.HULL_MAX_RELATED} related faces (the compiled cap)"}
+_HULL_HEAD = 3 * _lib.HULL_MAX_M + 8 + 4           # float64 words read back by every call: palette | errors | info (8 int32)
+
+
+def _hull_inputs(centers, center_weights, error_thres, target_size, keep_device=False):
+    """(centers [K,3], weights [K], error_thres, target) checked: float64 host arrays, or with keep_device a device tensor as it is."""
+    def rows(a, shape):
+        if keep_device and torch.is_tensor(a) and a.is_cuda:
+            return a.detach().reshape(shape)
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        return np.ascontiguousarray(a, dtype=np.float64).reshape(shape)
+    c, w = rows(centers, (-1, 3)), rows(center_weights, (-1,))
+    if not 4 <= c.shape[0] <= _lib.EXTRACT_MAX_K or w.shape[0] != c.shape[0]:
+        raise ValueError(f"simplify_hull: 4..{_lib.EXTRACT_MAX_K} centres [K,3] with their K weights are needed, got {c.shape[0]} and {w.shape[0]}")
+    if not float(error_thres) >= 0:
+        raise ValueError("simplify_hull: error_thres is negative or NaN")
+    target = 0 if target_size is None else int(target_size)
+    if target and not 4 <= target <= _lib.HULL_MAX_M:
+        raise ValueError(f"simplify_hull: target_size is None or 4..{_lib.HULL_MAX_M}")
+    return c, w, float(error_thres), target
+
+
+def _launch_hull(centers, center_weights, error_thres, target, want_trace=False):
+    """ONE launch of pnr_hull_simplify and one read-back of 480 bytes (the set beyond 16 rows and the trace: a second one, only when they are
+    needed).  -> {"info": [8] ints, "palette": [16,3], "errors": [8], "vertices": [info[1],3] or None, "trace": [collapses,4] or None}."""
+    dev = next((a.device for a in (centers, center_weights) if torch.is_tensor(a) and a.is_cuda), None)
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("simplify_hull needs the HIP path (a CUDA/HIP device); there is no CPU fallback")
+        dev = torch.device("cuda")
+
+    def on_device(a, shape):
+        t = a.detach() if torch.is_tensor(a) else torch.tensor(np.asarray(a, dtype=np.float64))
+        return t.to(dev, torch.float64).reshape(shape).contiguous()
+    c, w = on_device(centers, (-1, 3)), on_device(center_weights, (-1,))
+    K = c.shape[0]
+    out = torch.zeros(_HULL_HEAD + 3 * K + 2 * K, dtype=torch.float64, device=dev)
+    base = out.data_ptr()
+    a = _lib.HullSimplifyArgs()
+    a.centers, a.center_weights, a.K, a.error_thres, a.target_size = c.data_ptr(), w.data_ptr(), K, error_thres, target
+    a.palette, a.errors, a.info = base, base + 8 * 3 * _lib.HULL_MAX_M, base + 8 * (3 * _lib.HULL_MAX_M + 8)
+    a.vertices, a.trace = base + 8 * _HULL_HEAD, base + 8 * (_HULL_HEAD + 3 * K)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().pnr_hull_simplify(ctypes.byref(a), stream_ptr()), "pnr_hull_simplify")
+    head = out[:_HULL_HEAD].cpu().numpy()
+    info = [int(v) for v in head[3 * _lib.HULL_MAX_M + 8:].view(np.int32)]
+    res = {"info": info, "palette": head[:3 * _lib.HULL_MAX_M].reshape(-1, 3).copy(), "errors": head[3 * _lib.HULL_MAX_M:3 * _lib.HULL_MAX_M + 8].copy(),
+           "vertices": None, "trace": None}
+    if info[0] != _lib.HULL_OK or info[1] > _lib.HULL_MAX_M or want_trace:
+        rest = out[_HULL_HEAD:].cpu().numpy()
+        res["vertices"] = rest[:3 * info[1]].reshape(-1, 3).copy()
+        res["trace"] = rest[3 * K:].view(np.int32).reshape(K, 4)[:info[2]].copy()
+    return res
+
+
+def simplify_hull(centers, center_weights, error_thres=5 / 255, target_size=None, return_info=False):
+    """Hull_Simplification_posternerf(centers, prefix, pixel_counts=center_weights, error_thres, target_size) (palette/utils.py:230-234) on the
+    device: the convex hull of the K-means centres, one edge collapse after the other -- each the cheapest of the edges' linear programs --
+    until the reconstruction error of the centres passes error_thres (or the hull has target_size vertices).  centers [K,3], center_weights
+    [K], 4 <= K <= 128, device tensors (extract_centers' without a copy) or host arrays; ONE launch, 480 bytes read back.  Returns the palette
+    [M,3] float64 (numpy), with return_info also a dict: status, M, collapses, initial (the first hull's vertices), stop ("error", "target",
+    "unchanged", "four"), related (the largest related-face count of an edge), errors {V: error}, trace [(v1, v2, V after, candidates)],
+    handed_over (False, or the status text: the kernel met a coplanar facet or an edge above its related-face cap, and the loop was finished
+    on the host by simplify_hull_per_op from the vertex set it returned).  A flat set has no hull on the host either: RuntimeError."""
+    c, w, thres, target = _hull_inputs(centers, center_weights, error_thres, target_size, keep_device=True)
+    raw = _launch_hull(c, w, thres, target, want_trace=bool(return_info))
+    status, M, collapses, initial, stop, related = raw["info"][:6]
+    errors = {V: (None if raw["errors"][10 - V] == _lib.HULL_ERROR_FAIL else float(raw["errors"][10 - V]))
+              for V in range(10, 3, -1) if raw["errors"][10 - V] != _lib.HULL_ERROR_NONE}
+    info = {"status": status, "M": M, "collapses": collapses, "initial": initial, "stop": _lib.HULL_STOP[stop], "related": related,
+            "errors": errors, "trace": [] if raw["trace"] is None else [tuple(int(v) for v in row) for row in raw["trace"]], "handed_over": False}
+    if status == _lib.HULL_FLAT:
+        raise RuntimeError(f"pnr_hull_simplify: {_HULL_STATUS_TEXT[status]}")
+    if status != _lib.HULL_OK:
+        start = raw["vertices"] if raw["vertices"] is not None else raw["palette"][:M]
+        palette, rest = simplify_hull_per_op(c, w, thres, target_size, return_info=True, start=start)
+        info.update(M=palette.shape[0], collapses=collapses + rest["collapses"], stop=rest["stop"], related=max(related, rest["related"]),
+                    errors={**errors, **rest["errors"]}, trace=info["trace"] + rest["trace"], handed_over=_HULL_STATUS_TEXT[status])
+        if collapses == 0:
+            info["initial"] = rest["initial"]
+    else:
+        palette = raw["palette"][:M].copy() if M <= _lib.HULL_MAX_M else raw["vertices"]
+    return (palette, info) if return_info else palette
+
+
+def _scipy_hull(points):
+    """scipy's hull of a point set as the reference writes it to its OBJ file: (vertices [V,3] in ascending input order, faces [F,3] in the
+    vertices' numbering turned outwards)."""
+    from scipy.spatial import ConvexHull
+    hull = ConvexHull(points)
+    verts = np.sort(hull.vertices)
+    renum = np.full(points.shape[0], -1)
+    renum[verts] = np.arange(verts.shape[0])
+    faces = renum[hull.simplices]
+    V = hull.points[verts]
+    inward = _dot3(_cross3(V[faces[:, 1]] - V[faces[:, 0]], V[faces[:, 2]] - V[faces[:, 0]]), hull.equations[:, :3]) < 0
+    faces[inward] = faces[inward][:, [0, 2, 1]]
+    return V, faces
+
+
+def _collapse_per_op(V, faces):
+    """remove_one_edge_by_finding_smallest_adding_volume_with_test_conditions(mesh, option=2) (Convexhull_simplification.py:149-322) with
+    scipy's HiGHS for cvxopt's GLPK: -> (v1, v2, new point, candidates, largest related-face count), or (None, None, None, 0, largest)."""
+    from scipy.optimize import linprog
+    edges = sorted({(int(min(u, v)), int(max(u, v))) for f in faces for u, v in ((f[0], f[1]), (f[1], f[2]), (f[2], f[0]))})
+    best, cands, most = None, 0, 0
+    for v1, v2 in edges:
+        rel = [f for f in faces if v1 in f or v2 in f]
+        most = max(most, len(rel))
+        A, b, c = [], [], np.zeros(3)
+        for f in rel:
+            n = np.cross(V[f[1]] - V[f[0]], V[f[2]] - V[f[0]])
+            n = n / np.sqrt(np.dot(n, n))
+            A.append(n)
+            b.append(np.dot(n, V[f[0]]))
+            c += n
+        res = linprog(c, A_ub=-np.asarray(A), b_ub=-np.asarray(b), bounds=(None, None), method="highs")
+        if res.status != 0:
+            continue
+        cands += 1
+        volume = np.asarray([abs(np.dot(np.cross(V[f[1]] - V[f[0]], V[f[2]] - V[f[0]]), res.x - V[f[0]])) / 6.0 for f in rel]).sum()
+        if best is None or volume < best[0]:
+            best = (volume, v1, v2, res.x)
+    if best is None:
+        return None, None, None, 0, most
+    return best[1], best[2], best[3], cands, most
+
+
+def _error_per_op(vertices, points, counts):
+    """outsidehull_points_distance_unique_data_version (Additive_mixing_layers_extraction.py:185-201); raises what qhull raises."""
+    from scipy.spatial import ConvexHull, Delaunay
+    hull = ConvexHull(vertices)
+    outside = Delaunay(vertices).find_simplex(points, tol=1e-8) < 0
+    if not outside.any():
+        return 0.0
+    tri = hull.points[hull.simplices]
+    q = _closest_on_triangles(points[outside], tri[:, 0], tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    e = points[outside][:, None, :] - q
+    dist = np.sqrt(_dot3(e, e)).min(axis=1)
+    return float((((dist ** 2) * counts[outside]).sum() / counts.sum()) ** 0.5)
+
+
+def simplify_hull_per_op(centers, center_weights, error_thres=5 / 255, target_size=None, return_info=False, start=None):
+    """Hull_Simplification_posternerf (rgbsg/hull_simplification_posternerf.py:19-77) on the host in its line order, with scipy.spatial.ConvexHull
+    and scipy.optimize.linprog(method="highs") where the reference has its OBJ round trip and cvxopt's GLPK (neither imports here): what
+    simplify_hull is measured and tested against, and what finishes its hand-overs (start: the vertex set to go on from; the error is always
+    taken against the centres).  Returns simplify_hull's results."""
+    c, w, thres, target = _hull_inputs(centers, center_weights, error_thres, target_size)
+    V, faces = _scipy_hull(c if start is None else np.ascontiguousarray(start, dtype=np.float64).reshape(-1, 3))
+    info = {"status": _lib.HULL_OK, "collapses": 0, "initial": V.shape[0], "related": 0, "errors": {}, "trace": [], "handed_over": False}
+
+    def done(Vset, stop):
+        palette = Vset.clip(0.0, 1.0).reshape(-1, 3)
+        info.update(M=palette.shape[0], stop=stop)
+        return (palette, info) if return_info else palette
+
+    for _ in range(5000):
+        old = V
+        v1, v2, x, cands, most = _collapse_per_op(V, faces)
+        info["related"] = max(info["related"], most)
+        if x is not None:
+            keep = [i for i in range(V.shape[0]) if i not in (v1, v2)]
+            V, faces = _scipy_hull(np.vstack((V[keep], x)))
+            info["collapses"] += 1
+            info["trace"].append((v1, v2, V.shape[0], cands))
+        n = V.shape[0]
+        if n <= 10:
+            if not target:
+                try:
+                    err = _error_per_op(V.clip(0.0, 1.0), c, w)
+                except Exception:       # noqa: BLE001 -- the reference's bare except around the same call: qhull refusing the clipped set
+                    err = None
+                info["errors"][n] = err
+                if err is None or err > thres:
+                    return done(old, "error")
+            elif n == target:
+                return done(V, "target")
+        if n == old.shape[0] or n == 4:
+            return done(V, "unchanged" if n == old.shape[0] else "four")
+    raise RuntimeError("simplify_hull_per_op: hull simplification failed")
+
+
+def save_palette(path, palette):
+    """The palette as the reference writes it: a path ending in .npz gets `palette.npz` (key 'palette', float64 [M,3]), any other path
+    write_palette_txt's text (rgbsg/hull_simplification_posternerf.py:86-95: "r g b" a line, str() of the float64, no newline after the last
+    line).  load_palette reads both back."""
+    p = np.asarray(palette.detach().cpu() if torch.is_tensor(palette) else palette, dtype=np.float64).reshape(-1, 3)
+    if str(path).endswith(".npz"):
+        np.savez(path, palette=p)
+    else:
+        with open(path, "w") as f:
+            f.write("\n".join(f"{c[0]} {c[1]} {c[2]}" for c in p))
+
+
+def extract_palette(model, poses, intrinsics, H, W, images, palette_model=None, palette_size=None, error_thres=5 / 255, normalize_input=False, **kw):
+    """The whole of step 2 (PaletteTrainer.extract_palette into palette_extraction, palette/utils.py:167-254): extract_centers ->
+    simplify_hull -> the weight LUT, which with a `palette_model` is handed to it (initialize_from_extraction) and otherwise built on the
+    NeRF model's device (weight_lut).  kw: extract_centers' (linear, thresh, tau, frames_in_flight, render arguments).  Returns (palette [M,3]
+    float64, the LUT float32 [1,M,32,32,32] on the device, extract_centers' result).  The reference's OBJ files and extract-palette.png are not
+    written; save_palette and save_lut write its palette and hist_weights files."""
+    res = extract_centers(model, poses, intrinsics, H, W, images, **kw)
+    palette = simplify_hull(res["centers"], res["center_weights"], error_thres=error_thres, target_size=palette_size)
+    if palette_model is not None:
+        lut = initialize_from_extraction(palette_model, palette, normalize_input=normalize_input)
+    else:
+        lut = weight_lut(palette, normalize_input=normalize_input, device=next(model.parameters()).device)
+    return palette, lut, res
