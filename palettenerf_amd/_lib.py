@@ -385,6 +385,13 @@ class HullSimplifyArgs(ctypes.Structure):
                 ("palette", _ptr), ("info", _ptr), ("errors", _ptr), ("trace", _ptr), ("vertices", _ptr)]
 
 
+# include/pnr_distortion.h: the distortion loss on the ragged training rays.  A header and a table of its own, as the hull's.
+DISTORTION_SIGNATURES = {
+    "pnr_distortion_forward": [_ptr, _ptr, _ptr, _u32, _u32, _f32, _ptr, _ptr, _ptr, _ptr],
+    "pnr_distortion_backward": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _f32, _ptr, _ptr],
+}
+
+
 _lib = None
 
 
@@ -398,7 +405,7 @@ def load():
             f"palettenerf_amd: {LIB_PATH} is missing. Build it with `python -m palettenerf_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU or PyTorch fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in (*SIGNATURES.items(), *HULL_SIGNATURES.items()):
+    for name, argtypes in (*SIGNATURES.items(), *HULL_SIGNATURES.items(), *DISTORTION_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

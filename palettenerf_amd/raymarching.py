@@ -316,6 +316,46 @@ def composite_rays_train_norm(sigmas, rgbs, deltas, rays, rays_gt, T_thresh=1e-4
     return _composite_rays_train_norm.apply(sigmas, rgbs, deltas, rays, rays_gt, T_thresh)
 
 
+class _distortion_loss(Function):
+    """The mip-NeRF 360 distortion loss of every training ray (the reference's unused loss.py:29-76 with m = t, interval = dt), on the ragged
+    rays and with the weights and the stop rule of composite_rays_train -- one launch each way (pnr_distortion_*, include/pnr_distortion.h).
+    Only sigmas gets a gradient; there is no double backward."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, sigmas, deltas, rays, T_thresh=1e-4):
+        sigmas, deltas = sigmas.contiguous(), deltas.contiguous()
+        M, N = sigmas.shape[0], rays.shape[0]
+        dist, w_sum, wm_sum = (torch.empty(N, dtype=sigmas.dtype, device=sigmas.device) for _ in range(3))
+        call("pnr_distortion_forward", ptr(require(sigmas, torch.float32, "sigmas")), ptr(require(deltas, torch.float32, "deltas")),
+             ptr(require(rays, torch.int32, "rays")), _u32(M), _u32(N), _f32(T_thresh), ptr(dist), ptr(w_sum), ptr(wm_sum))
+        ctx.save_for_backward(sigmas, deltas, rays, dist, w_sum, wm_sum)
+        ctx.dims = [M, N, T_thresh]
+        ctx.set_materialize_grads(False)
+        return dist
+
+    @staticmethod
+    @_bwd
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_dist):
+        if grad_dist is None:
+            return None, None, None, None
+        sigmas, deltas, rays, dist, w_sum, wm_sum = ctx.saved_tensors
+        M, N, T_thresh = ctx.dims
+        if N == 0 or M == 0:
+            return torch.zeros_like(sigmas), None, None, None
+        grad_dist = grad_dist.contiguous()
+        grad_sigmas = torch.empty_like(sigmas)   # the entry writes every element
+        call("pnr_distortion_backward", ptr(require(grad_dist, torch.float32, "grad_dist")), ptr(sigmas), ptr(deltas), ptr(rays), ptr(dist),
+             ptr(w_sum), ptr(wm_sum), _u32(M), _u32(N), _f32(T_thresh), ptr(grad_sigmas))
+        return grad_sigmas, None, None, None
+
+
+def distortion_loss(sigmas, deltas, rays, T_thresh=1e-4):
+    """-> dist [N], indexed by ray id as weights_sum is; see _distortion_loss.  Its mean over the rays is EffDistLoss's value."""
+    return _distortion_loss.apply(sigmas, deltas, rays, T_thresh)
+
+
 class _composite_rays_flex_train(Function):
     """raymarching/raymarching.py:294-341"""
 

@@ -616,8 +616,9 @@ class NeRFRenderer(_OccupancyMaintenance, _RendererBase):
         return {"depth": depth.view(*prefix), "image": image.view(*prefix, 3), "weights_sum": weights_sum}
 
     def run_cuda(self, rays_o, rays_d, rays_gt=None, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024,
-                 T_thresh=1e-4, **kwargs):
-        """nerf/renderer.py:258-393"""
+                 T_thresh=1e-4, distortion=False, **kwargs):
+        """nerf/renderer.py:258-393.  distortion=True (training only; ignored otherwise) adds results["distortion"] [N]: the distortion loss
+        of every ray (raymarching.distortion_loss) from the sigmas / deltas / rays the composite reads, a launch of its own."""
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
         rays_d = rays_d.contiguous().view(-1, 3)
@@ -666,6 +667,8 @@ class NeRFRenderer(_OccupancyMaintenance, _RendererBase):
             results = TrainResults(RawTrain(weights_sum, depth, image, None, nears, fars, bg_color, tuple(prefix), 0, 0))
             results["rgb_norm"] = rgb_norm_map
             results["weights_sum"] = weights_sum
+            if distortion:
+                results["distortion"] = raymarching.distortion_loss(sigmas, deltas, rays, T_thresh)
             return results
         elif self.march_mode == "native":
             # device-driven loop: same schedule and arithmetic, no per-iteration host sync (pnr_nerf_render_frame)
@@ -833,8 +836,9 @@ class PaletteRenderer(_RendererBase):
         raise NotImplementedError()
 
     def run_cuda(self, rays_o, rays_d, dt_gamma=0, bg_color=None, perturb=False, force_all_rays=False, max_steps=1024, T_thresh=1e-4,
-                 gui_mode=False, **kwargs):
-        """palette/renderer.py:296-552"""
+                 gui_mode=False, distortion=False, **kwargs):
+        """palette/renderer.py:296-552.  distortion=True (training only; ignored otherwise) adds results["distortion"] [N] as the NeRF
+        renderer does; density is frozen in this stage, so it is a value without a gradient."""
         prefix = rays_o.shape[:-1]
         rays_o = rays_o.contiguous().view(-1, 3)
         rays_d = rays_d.contiguous().view(-1, 3)
@@ -936,6 +940,8 @@ class PaletteRenderer(_RendererBase):
             # train_loss() computes them, the loss and every gradient from results.raw in one launch each way instead
             results = TrainResults(RawTrain(weights_sum, depth, image, all_map, nears, fars, bg_color, tuple(prefix), nb, clip_dim))
             results["weights_sum"] = weights_sum
+            if distortion:
+                results["distortion"] = raymarching.distortion_loss(sigmas, deltas, rays, T_thresh)
             results["omega_sparsity"] = all_map[..., 0:1].view(*prefix)
             results["view_dep_norm"] = all_map[..., 1:2].view(*prefix)
             results["offsets_norm"] = all_map[..., 2:3].view(*prefix)

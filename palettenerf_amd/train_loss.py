@@ -171,7 +171,8 @@ class _train_loss(Function):
 
 
 def train_loss(results, gt_rgb, lambda_sparsity=0.0, lambda_offsets=0.0, lambda_view_dep=0.0, lambda_smooth=0.0, lambda_weight=0.0,
-               lambda_palette=0.0, gt_weights=None, gt_clip=None, basis_color=None, basis_color_origin=None, want_outputs=True, lambda_sparse=0.0):
+               lambda_palette=0.0, gt_weights=None, gt_clip=None, basis_color=None, basis_color_origin=None, want_outputs=True, lambda_sparse=0.0,
+               lambda_distort=0.0):
     """palette/utils.py:483-600 (`train_step` from `pred_rgb = outputs['image']` to `loss = loss.mean()`) on a TrainResults, MSE criterion:
     returns (loss, info) with info = {"terms": [10] tensor in TERM_NAMES order, "loss_ray": [N] per-ray colour error (the error map's input
     before the scalar terms), "image"/"depth"/"direct_rgb": detached renders for logging (None with want_outputs=False)}.
@@ -182,7 +183,10 @@ def train_loss(results, gt_rgb, lambda_sparsity=0.0, lambda_offsets=0.0, lambda_
     caller's).  With a non-zero weight and `results["rgb_norm"]` present, loss becomes loss + lambda_sparse * rgb_norm.mean(), info["loss_ray"]
     becomes loss_ray + lambda_sparse * rgb_norm (the per-ray value the reference's error map reads) and info["loss_sparse"] is the added
     scalar; `terms` keeps its ten entries (terms[0] is the loss without this term).  These are a few [N]-sized torch launches on purpose:
-    folding the term into pnr_train_loss_* needs new fields in pnr_train_loss_args, i.e. an ABI bump.  With lambda_sparse == 0 nothing changes."""
+    folding the term into pnr_train_loss_* needs new fields in pnr_train_loss_args, i.e. an ABI bump.  With lambda_sparse == 0 nothing changes.
+    lambda_distort: the distortion loss, by the same pattern.  With a non-zero weight and `results["distortion"]` present (render(...,
+    distortion=True)), loss becomes loss + lambda_distort * distortion.mean() -- the mean over rays is EffDistLoss's `/ n_rays` --
+    info["loss_ray"] gains lambda_distort * distortion and info["loss_distort"] is the added scalar.  With lambda_distort == 0 nothing changes."""
     raw = getattr(results, "raw", results)
     if not isinstance(raw, RawTrain):
         raise RuntimeError("train_loss needs the TrainResults of a training-mode run_cuda (results.raw)")
@@ -205,4 +209,11 @@ def train_loss(results, gt_rgb, lambda_sparsity=0.0, lambda_offsets=0.0, lambda_
         loss = loss + sparse
         info["loss_ray"] = info["loss_ray"] + lambda_sparse * rgb_norm.detach().view(*raw.prefix)
         info["loss_sparse"] = sparse.detach()
+    distortion = results.get("distortion") if lambda_distort != 0 and isinstance(results, dict) else None
+    if distortion is not None:
+        distortion = distortion.float()
+        distort = lambda_distort * distortion.mean()
+        loss = loss + distort
+        info["loss_ray"] = info["loss_ray"] + lambda_distort * distortion.detach().view(*raw.prefix)
+        info["loss_distort"] = distort.detach()
     return loss, info

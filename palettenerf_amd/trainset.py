@@ -213,13 +213,16 @@ class TrainSet:
 
 
 def train_step(model, batch, render_kwargs=None, lambda_sparsity=0.0, lambda_offsets=0.0, lambda_view_dep=0.0, lambda_smooth=0.0, lambda_weight=0.0,
-               lambda_palette=0.0, lambda_sparse=0.0, want_outputs=True):
+               lambda_palette=0.0, lambda_sparse=0.0, want_outputs=True, lambda_distort=0.0):
     """PaletteTrainer.train_step (palette/utils.py:481-608) / Trainer.train_step (nerf/utils.py:527-536) from the render on, on a TrainBatch:
     returns (pred_rgb, gt_rgb, loss, loss_dict) with loss_dict keyed by train_loss.TERM_NAMES (device scalars; 'loss_ray' [B,N] rides along for
     the error map).  A PaletteNeRF model renders with force_all_rays=True and gets the weight guide, the clip target and the palette anchor; a
     NeRF model renders with force_all_rays=False and rays_gt=gt_rgb, its rgb_norm term weighted by lambda_sparse.  render_kwargs: dt_gamma,
-    max_steps, ... as the reference passes **vars(opt).  lambda_weight and lambda_palette are the trainer's per-epoch values (:651-669)."""
+    max_steps, ... as the reference passes **vars(opt).  lambda_weight and lambda_palette are the trainer's per-epoch values (:651-669).
+    lambda_distort != 0 renders with distortion=True and adds the distortion loss (train_loss); with 0 the render is not told of it."""
     kw = dict(render_kwargs or {})
+    if lambda_distort != 0:
+        kw["distortion"] = True
     bg = batch.bg_color.reshape(-1, 3) if torch.is_tensor(batch.bg_color) and batch.bg_color.numel() > 3 else batch.bg_color
     palette = hasattr(model, "num_basis")
     if palette:
@@ -229,25 +232,28 @@ def train_step(model, batch, render_kwargs=None, lambda_sparsity=0.0, lambda_off
         loss, info = train_loss(out, batch.gt_rgb, lambda_sparsity=lambda_sparsity, lambda_offsets=lambda_offsets, lambda_view_dep=lambda_view_dep,
                                 lambda_smooth=smooth, lambda_weight=lambda_weight, lambda_palette=lambda_palette if origin is not None else 0.0,
                                 gt_weights=batch.gt_weights, gt_clip=batch.gt_clip if getattr(model.opt, "pred_clip", False) else None,
-                                basis_color=model.basis_color if origin is not None else None, basis_color_origin=origin, want_outputs=want_outputs)
+                                basis_color=model.basis_color if origin is not None else None, basis_color_origin=origin, want_outputs=want_outputs,
+                                lambda_distort=lambda_distort)
     else:
         out = model.render(batch.rays_o, batch.rays_d, rays_gt=batch.gt_rgb, staged=False, bg_color=bg, perturb=True, force_all_rays=False, **kw)
-        loss, info = train_loss(out, batch.gt_rgb, lambda_sparse=lambda_sparse, want_outputs=want_outputs)
+        loss, info = train_loss(out, batch.gt_rgb, lambda_sparse=lambda_sparse, want_outputs=want_outputs, lambda_distort=lambda_distort)
     loss_dict = {name: info["terms"][i] for i, name in enumerate(TERM_NAMES)}
-    if "loss_sparse" in info:
-        loss_dict["loss_sparse"] = info["loss_sparse"]
+    for extra in ("loss_sparse", "loss_distort"):
+        if extra in info:
+            loss_dict[extra] = info[extra]
     loss_dict["loss_ray"] = info["loss_ray"]
     return info["image"], batch.gt_rgb, loss, loss_dict
 
 
 def train_epoch(model, trainset, optimizer, scheduler=None, scaler=None, update_extra_interval=16, global_step=0, batch_size=1, fp16=False,
-                render_kwargs=None, generator=None, max_steps=None, ema=None, **lambdas):
+                render_kwargs=None, generator=None, max_steps=None, ema=None, lambda_distort=0.0, **lambdas):
     """train_one_epoch (palette/utils.py:684-767): one pass over the views in a shuffled order -- update_extra_state every update_extra_interval
     global steps, zero_grad, train_step, backward, optimiser step, the per-step scheduler, the error-map update.  The running loss is summed on the
     device and read back ONCE at the end (the reference's loss.item() per step is a synchronisation).  Returns (average loss, new global_step).
     The per-epoch rules -- the lambda_weight decay, the lambda_palette switch, the smooth-loss switch (:649-674) -- stay the caller's: pass the
-    epoch's numbers in **lambdas (train_step's keywords).  `ema` (an optim.ExponentialMovingAverage or torch_ema's) gets its update() where the
-    reference calls it: ONCE, after the pass (palette/utils.py:746-747, nerf/utils.py:920-921; train_gui: after its 16 steps, :789-790) -- not per step."""
+    epoch's numbers in **lambdas (train_step's keywords).  lambda_distort != 0 adds the distortion loss (the render is then asked for it:
+    distortion=True).  `ema` (an optim.ExponentialMovingAverage or torch_ema's) gets its update() where the reference calls it: ONCE, after the
+    pass (palette/utils.py:746-747, nerf/utils.py:920-921; train_gui: after its 16 steps, :789-790) -- not per step."""
     model.train()
     order = trainset.epoch_order(generator)
     total = torch.zeros((), dtype=torch.float32, device=trainset.images.device)
@@ -264,7 +270,7 @@ def train_epoch(model, trainset, optimizer, scheduler=None, scaler=None, update_
         optimizer.zero_grad(set_to_none=True)
         batch = trainset.batch(order[head:head + batch_size], model)
         with torch.autocast("cuda", dtype=torch.float16, enabled=fp16):
-            _, _, loss, loss_dict = train_step(model, batch, render_kwargs, want_outputs=False, **lambdas)
+            _, _, loss, loss_dict = train_step(model, batch, render_kwargs, want_outputs=False, lambda_distort=lambda_distort, **lambdas)
         if scaler is not None:
             scaler.scale(loss).backward()
             scaler.step(optimizer)
